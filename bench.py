@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- 512x512 / 50-step images per second of the IMAGDressing-v1 denoising hot path.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -14,7 +14,11 @@ timed region; weights are random-init of the SD1.5 architecture (no checkpoints 
 At N > 1 every rank runs its own shard of the images (weak scaling: per-GPU batch fixed) and the
 garment features are computed on rank 0 and broadcast (RCCL) once per step.
 
-Prints ONE JSON line on rank 0.
+A plain run sets up, warms up, times the ``--steps`` steps and prints ONE JSON line on rank 0 (``value`` images/s,
+``ms_per_step``, the roofline of the level-0 hybrid attention from events inside those steps).  ``--full`` adds every other
+leg: the other 16-bit element type, the 512x640 geometry, parity against the committed oracle outputs, batch-1 latency, the
+FLOP count, the other BASELINE configurations, power / live PMC traffic of the roofline kernel and the CPU baseline.
+``--dump-outputs DIR`` writes what the last timed step returned (``images.npy``, float32; ``latents.npy`` with --no-decode).
 """
 import argparse
 import json
@@ -36,6 +40,11 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=2)
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beyond the headline timing (other dtype / geometry / configs, parity, latency, FLOPs, power, live "
+                         "traffic, CPU baseline); the --no-* options below switch single legs of a --full run off")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the output of the last timed step as DIR/<name>.npy (float32; rank 0's images; a fixed seeded sample above 64 MB)")
     ap.add_argument("--batch", type=int, default=4, help="images per GPU sharing one garment")
     ap.add_argument("--res", type=int, default=512, help="width = height of the generated image (BASELINE configs[1]: 512)")
     ap.add_argument("--width", type=int, default=0, help="override --res (the reference scripts' default geometry is --width 512 --height 640)")
@@ -289,6 +298,24 @@ def run_other_config(cid, what, device, dtype, args, runs=3):
     return res
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays):
+    """name -> tensor, written as ``out_dir/<name>.npy`` in float32.  All together stay within DUMP_MAX_BYTES: a larger array is replaced
+    by a fixed sample of its flattened elements (seeded permutation, kept in index order), so two builds see the same positions."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    budget = DUMP_MAX_BYTES // max(len(arrays), 1)
+    for name, t in arrays.items():
+        a = t.detach().to("cpu", torch.float32).contiguous()
+        if a.numel() * 4 > budget:
+            keep = budget // 4
+            idx = torch.randperm(a.numel(), generator=torch.Generator().manual_seed(0))[:keep].sort().values
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), a.numpy())
+
+
 def self_launch(args):
     """``python bench.py --gpus N`` without a launcher: re-exec under ``torch.distributed.run`` with one rank per GPU
     (what the driver does explicitly), rendezvous on 127.0.0.1.  Returns the child's exit code."""
@@ -510,22 +537,25 @@ def main():
         # the ONE collective of the path: the packed garment-feature broadcast (23.1 MB at 512x512 in 16 bits), HIP-event timed
         nel = sum(t * c for c, t in ((320, 5 * (W0 // 8) * (H0 // 8)), (640, 5 * (W0 // 16) * (H0 // 16)), (1280, 5 * (W0 // 32) * (H0 // 32)),
                                      (1280, (W0 // 64) * (H0 // 64)))) + 1
-        buf = torch.zeros(nel, dtype=dtype, device=device)
         bms = []
-        for _ in range(4):
-            barrier()
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record(); dist.broadcast(buf, src=0); e1.record(); torch.cuda.synchronize()
-            bms.append(e0.elapsed_time(e1))
+        if args.full:
+            buf = torch.zeros(nel, dtype=dtype, device=device)
+            for _ in range(4):
+                barrier()
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record(); dist.broadcast(buf, src=0); e1.record(); torch.cuda.synchronize()
+                bms.append(e0.elapsed_time(e1))
         multi = dict(ranks_seen=len(idents), distinct_devices=distinct, devices=[f"rank{r}:cuda{d}:{i}" for r, d, i in idents],
                      backend=args.backend + (" (RCCL)" if args.backend == "nccl" else ""), broadcast_bytes=nel * 2,
-                     broadcast_ms=round(min(bms[1:]), 3))
+                     broadcast_ms=round(min(bms[1:]), 3) if bms else None)
 
-    primary = run_timed(dtype, W0, H0, args.batch, args.steps, args.warmup, args.decode)
+    primary = run_timed(dtype, W0, H0, args.batch, args.steps, args.warmup, args.decode, keep_output=args.dump_outputs is not None)
+    if args.dump_outputs is not None and rank == 0:
+        dump_outputs(args.dump_outputs, {"images" if args.decode else "latents": primary.pop("out")})
     secondary = None
     other = "fp16" if args.dtype == "bf16" else "bf16"
     odt = torch.float16 if other == "fp16" else torch.bfloat16
-    if not args.no_secondary:
+    if args.full and not args.no_secondary:
         r2 = run_timed(odt, W0, H0, args.batch, args.steps, args.warmup, args.decode)
         roof2 = roofline_of(r2, W0, H0, args.batch)
         secondary = {"dtype": other, "value": round(args.batch * world * args.steps / r2["elapsed"], 4), "unit": "images/s",
@@ -533,7 +563,7 @@ def main():
                      "roofline_frac": None if roof2 is None else roof2["frac"],
                      "note": "same binary, same workload, the other 16-bit element type (same MFMA rate)"}
     geometry = None
-    if not args.no_geometry_secondary and is_headline_geometry:
+    if args.full and not args.no_geometry_secondary and is_headline_geometry:
         gsteps = args.steps                       # same timed steps / warm-up as the headline (round 4; was 2 after 1)
         rg = run_timed(dtype, 512, 640, args.batch, gsteps, args.warmup, args.decode)
         roofg = roofline_of(rg, 512, 640, args.batch)
@@ -546,7 +576,7 @@ def main():
 
     # ---- everything below runs on rank 0 of a single-GPU run only (untimed diagnostics) ----
     parity = latency = flops = None
-    if world == 1 and not args.no_parity:
+    if world == 1 and args.full and not args.no_parity:
         try:
             from tests.unet_fixture import ipa_controlnet_forward_inputs, measure_unet_parity_timesteps, unet_forward_inputs
             import torch as _t
@@ -596,7 +626,7 @@ def main():
             ops.clear_workspaces(); torch.cuda.empty_cache()
         except Exception as e:       # noqa: BLE001
             parity = {"error": f"{type(e).__name__}: {e}"}
-    if world == 1 and not args.no_latency:
+    if world == 1 and args.full and not args.no_latency:
         try:
             le = run_timed(dtype, W0, H0, 1, 3, 1, args.decode, graph=False, hook_attention=False, keep_output=True)
             lg = run_timed(dtype, W0, H0, 1, 3, 1, args.decode, graph=True, hook_attention=False, keep_output=True)
@@ -608,7 +638,7 @@ def main():
         except Exception as e:       # noqa: BLE001
             latency = {"error": f"{type(e).__name__}: {e}"}
             ops.ATTN_EVENT_HOOK = None
-    if world == 1 and not args.no_flops:
+    if world == 1 and args.full and not args.no_flops:
         try:
             ops.FLOP_COUNTER = {}
             run_timed(dtype, W0, H0, args.batch, 1, 0, args.decode, hook_attention=False)
@@ -624,7 +654,7 @@ def main():
             flops = {"error": f"{type(e).__name__}: {e}"}
 
     other_configs = None
-    if world == 1 and not args.no_configs and is_headline_geometry:
+    if world == 1 and args.full and not args.no_configs and is_headline_geometry:
         other_configs = {}
         for key, cid, what in (("configs2", 3, "BASELINE configs[2]: + IP-Adapter face (LoRAIP, 77 + 4 tokens) + ControlNet-OpenPose, LoraRefS / LoRAIP processors with "
                                                "rank-128 LoRA folded into the weights, 512x512, 50 DDIM steps, batch 8, guidance 7.0 "
@@ -639,7 +669,7 @@ def main():
             ops.clear_workspaces(); torch.cuda.empty_cache()
 
     power = None
-    if world == 1 and not args.no_power and is_headline_geometry and args.batch == 4:
+    if world == 1 and args.full and not args.no_power and is_headline_geometry and args.batch == 4:
         # board power / shader clock while the level-0 hybrid-attention kernel runs back to back (rocm-smi, 20 Hz, ~2 s): the kernel is
         # POWER-capped -- with random operands the board sits at its cap and the governor lowers the clock, so the 2.5 PFLOP/s
         # datasheet peak (2.4 GHz) is not reachable by ANY kernel with this operand activity; roofline.frac stays priced against it
@@ -659,7 +689,7 @@ def main():
     if rank == 0:
         images = args.batch * world * args.steps
         elapsed, dec_ms = primary["elapsed"], primary["dec_ms"]
-        roof = roofline_of(primary, W0, H0, args.batch, measure_traffic=True)
+        roof = roofline_of(primary, W0, H0, args.batch, measure_traffic=args.full)
         if roof is not None and power is not None and power.get("sclk_mhz"):
             roof["power"] = power
             roof["frac_of_peak_at_sustained_clock"] = round(roof["achieved"] / (MFMA_PEAK_TFLOPS * power["sclk_mhz"] / 2400.0), 4)
@@ -683,6 +713,7 @@ def main():
             "metric": "512x512 50-step images/sec (whole node)", "value": round(images / elapsed, 4), "unit": "images/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 2),
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": args.dtype, "data": "synthetic",
+            "full": args.full,
             "config": {"workload": f"BASELINE configs[1]: SD1.5 {args.dtype}, {geo}, {args.ddim_steps} DDIM steps, "
                                    f"batch {args.batch}/GPU sharing one garment, garment cross-attn only (RefS + CAttn processors), "
                                    "random-init weights" + (", VAE decode of the final latents included" if args.decode else ""),
@@ -703,14 +734,14 @@ def main():
             "by_dtype": by_dtype,
             "other_configs": other_configs,
             "default_geometry_512x640": geometry,
-            "parity": parity if parity is not None else {"note": "measured on single-GPU runs only (tests/unet_fixture.py::measure_unet_parity)"},
+            "parity": parity if parity is not None else {"note": "measured by single-GPU --full runs only (tests/unet_fixture.py::measure_unet_parity)"},
             "latency_b1": latency,
             "flops": flops,
         }
         if world > 1:
             multi["ms_per_step_per_rank"] = [round(t / args.steps * 1e3, 2) for t in primary["per_rank"]]
             line["multi_gpu"] = multi
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(args)
             try:
                 line["cpu_baseline"]["kernel_level"] = kernel_level_baseline(device, dtype, line["cpu_baseline"]["cores"])

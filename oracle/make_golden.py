@@ -2,7 +2,7 @@
 (``/root/reference/adapter/attention_processor.py`` and ``adapter/resampler.py``, imported
 verbatim through ``oracle/ref_loader.py``) on seeded fp32 inputs (TEST INFRASTRUCTURE).
 
-Run in the build container only:   python -m oracle.make_golden [base|full|geometry|legacy|unet|timesteps|all|trajectory [case ...]]
+Run in the build container only:   python -m oracle.make_golden [base|full|geometry|legacy|unet|timesteps|surface|all|trajectory [case ...]]
 The fixtures pin ``oracle/processors.py`` and ``oracle/resampler.py`` (tests/test_oracle_golden.py)
 and are what the ``-m gpu`` parity tests compare the HIP path with when /root/reference is absent.
 
@@ -543,9 +543,51 @@ def main_trajectory(which=None):
     print("trajectory.pt", os.path.getsize(FILE) // 1024, "KiB")
 
 
+SURFACE_CTOR = {
+    "RefSAttnProcessor2_0": ("n", 64), "LoraRefSAttnProcessor2_0": ("n", 64), "RefLoraSAttnProcessor2_0": ("n", 64),
+    "CAttnProcessor2_0": ("n", 64, 96), "LoRAIPAttnProcessor2_0": (64, 96), "IPAttnProcessor2_0": (64, 96),
+    "SAttnProcessor2_0": ("n", 64), "BaseSAttnProcessor2_0": ("n", 64), "RefCAttnProcessor2_0": ("n", 64, 96),
+}
+SURFACE_RESAMPLER = dict(dim=64, depth=2, dim_head=16, heads=4, num_queries=4, embedding_dim=48, output_dim=32, ff_mult=4)
+SURFACE_PIPELINES = ("IMAGDressing_v1_pipeline", "IMAGDressing_v1_pipeline_controlnet", "IMAGDressing_v1_pipeline_ipa_controlnet",
+                     "IMAGDressing_v1_pipeline_controlnet_inpainting")
+
+
+def main_surface():
+    """tests/golden/reference_surface.json: the plugin surface of the reference (names only, no code) -- constructor parameter names and
+    state_dict shapes of the processor / Resampler / ProjPlusModel classes, and the parameter names of every pipeline's ``__init__`` /
+    ``__call__`` (read with ``ast``); tests/test_host_logic.py checks the shims against it."""
+    import ast
+    import inspect
+    import json
+    from .ref_loader import REFERENCE_ROOT
+    ap, rs = load_reference_adapter()
+
+    def shapes(m):
+        return {k: list(v.shape) for k, v in m.state_dict().items()}
+    out = {"processors": {}, "pipelines": {}}
+    for cls, args in SURFACE_CTOR.items():
+        c = getattr(ap, cls)
+        out["processors"][cls] = dict(args=list(args), init=list(inspect.signature(c.__init__).parameters), state_dict=shapes(c(*args)))
+    out["resampler"] = dict(cfg=SURFACE_RESAMPLER, init=list(inspect.signature(rs.Resampler.__init__).parameters),
+                            state_dict=shapes(rs.Resampler(**SURFACE_RESAMPLER)))
+    out["proj_plus"] = dict(forward=list(inspect.signature(rs.ProjPlusModel.forward).parameters), state_dict=shapes(rs.ProjPlusModel()))
+    for mod in SURFACE_PIPELINES:
+        with open(os.path.join(REFERENCE_ROOT, "dressing_sd", "pipelines", mod + ".py")) as f:
+            tree = ast.parse(f.read())
+        cls = [n for n in tree.body if isinstance(n, ast.ClassDef) and n.name == "IMAGDressing_v1"][0]
+        fns = {f.name: [a.arg for a in f.args.args] for f in cls.body if isinstance(f, ast.FunctionDef)}
+        out["pipelines"][mod] = {fn: fns[fn] for fn in ("__init__", "__call__")}
+    path = os.path.join(OUT, "reference_surface.json")
+    with open(path, "w") as f:
+        json.dump(out, f, indent=1, sort_keys=True)
+        f.write("\n")
+    print("reference_surface.json", os.path.getsize(path) // 1024, "KiB")
+
+
 if __name__ == "__main__":
     import sys
-    what = sys.argv[1] if len(sys.argv) > 1 else "all"          # base | full | geometry | unet | timesteps | all
+    what = sys.argv[1] if len(sys.argv) > 1 else "all"          # base | full | geometry | unet | timesteps | surface | all
     if what in ("base", "all"):
         main()
     if what in ("full", "all"):
@@ -558,5 +600,7 @@ if __name__ == "__main__":
         main_unet()
     if what in ("timesteps", "all"):
         main_timesteps()
+    if what in ("surface", "all"):
+        main_surface()
     if what == "trajectory":          # ~30 min of 8 cores; not part of "all"
         main_trajectory(sys.argv[2:] or None)

@@ -28,7 +28,7 @@ case "$task" in
   smoke)
     timeout 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" 2>&1 | tail -3 ;;
   bench)
-    tag="$1"; shift
+    tag="$1"; shift; set -- --full "$@"
     timeout 900 python bench.py "$@" > gpurun_out/${tag}_bench.json 2> gpurun_out/${tag}_bench.err; tail -c 6000 gpurun_out/${tag}_bench.json ;;
   quick)
     tag="$1"; shift
