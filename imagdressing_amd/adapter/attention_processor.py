@@ -403,7 +403,14 @@ class _RefMixin:
     def _garment_bdiv(self, B: int, ref: torch.Tensor) -> int:
         """Batch rows per garment: [1, M, C] is shared by the whole batch; [Bg, M, C] (the reference's own
         ``view(batch_size, ...)`` layout at :602-603, or several garments in one call) serves contiguous groups of
-        B / Bg rows.  Anything else would silently pair rows with the wrong garment, so it raises."""
+        B / Bg rows.  Anything else would silently pair rows with the wrong garment, so it raises.
+        ``B`` is the number of rows the garments are spread over: under ``sa_pair_layout`` the COND rows of the CFG batch only
+        (the caller passes half the batch), so that cond row b reads garment b // (B_cond / Bg) in every hybrid block, the
+        first (pair-half) block included.  The uncond rows then map past the last garment: they carry scale2 == 0, and no
+        form of the attention kernel forms a second-key-set address for such a row -- the generic kernel (attention.hip) and
+        the d = 40 kernels (attention_d40.hip, with or without the duplicated first-phase store or the fused out-projection;
+        attention_d40_fp8.hip) run the garment phase only when scale2[b] != 0, and the phase-split launch runs it for the rows
+        [0, phase2_rows) = the cond rows only."""
         Bg = ref.shape[0]
         if Bg < 1 or B % Bg:
             raise ValueError(f"sa_hidden_states[{self.name!r}] has batch {Bg}, which does not divide hidden_states batch {B}")
@@ -459,7 +466,9 @@ class RefSAttnProcessor2_0(nn.Module, _FusedBase, _RefMixin):
         if sa_hidden_states is not None:                                   # :597
             ref = sa_hidden_states[self.name]
             kv2 = self._garment_kv(ref, attn.heads, x.device, x.dtype)
-            bdiv2 = self._garment_bdiv(x.shape[0], ref)
+            # garments serve the cond rows: all of x in the pair-half block, its first half under sa_pair_layout elsewhere
+            cond_rows = x.shape[0] // 2 if (kwargs.get("sa_pair_layout") and not imd_pair_half and x.shape[0] % 2 == 0) else x.shape[0]
+            bdiv2 = self._garment_bdiv(cond_rows, ref)
             s2 = self._branch_weights(x.shape[0] * (2 if imd_pair_half else 1), sa_batch_mask, x.device)      # (pair_half: the kernel reads the cond rows' entries [0, B))
         if imd_pair_half and (kv2 is None or imd_residual is None or shape4 is not None):
             raise ValueError("imd_pair_half needs sa_hidden_states, the block residual and token-major hidden states (engine-internal)")

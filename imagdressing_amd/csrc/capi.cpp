@@ -266,6 +266,14 @@ int imd_ddim_cfg_step(const imd_ddim_params* p, void* stream) {
     return imd_launch_ddim_cfg_step(*p, (hipStream_t)stream);
 }
 
+int imd_ddim_cfg_step_rows(const imd_ddim_params* p, const float* guidance, void* stream) {
+    IMD_REQUIRE(p != nullptr, "ddim_cfg_step_rows: null params");
+    IMD_REQUIRE_SIZE(p, "ddim_cfg_step_rows");
+    IMD_REQUIRE(p->z && p->eps && guidance, "ddim_cfg_step_rows: null pointer");
+    IMD_REQUIRE(p->coefs != nullptr || p->sqrt_a_t > 0.f, "ddim_cfg_step_rows: sqrt(alpha_t) must be positive");
+    return imd_launch_ddim_cfg_step_rows(*p, guidance, (hipStream_t)stream);
+}
+
 int imd_timestep_embedding(const float* t, float* out, int B, int dim, void* stream) {
     IMD_REQUIRE(t && out, "timestep_embedding: null pointer");
     return imd_launch_timestep_embedding(t, out, B, dim, (hipStream_t)stream);

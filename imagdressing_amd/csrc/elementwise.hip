@@ -11,13 +11,18 @@
 //   uncond halves (torch.cat([latents]*2), :483-488; scale_model_input is the identity for DDIM).
 // Algorithmic traffic per latent element: 3 fp32 reads + 1 fp32 write (+3 reads with inpaint)
 // + 2 x 4 B of bf16 next-input writes.
+// Per-row guidance (imd_ddim_cfg_step_rows): the instantiation with ONE trailing `const float*` argument reads the guidance
+// scale of each latent row from that device [B] fp32 array instead of p.guidance -- one batched call serving requests with
+// different guidance scales.  The scalar instantiation (empty pack) keeps the one-argument signature, hence the same
+// kernarg layout and instruction stream as before the variant existed.
 #include "common.h"
 #include "imd_kernels.h"
 
 namespace {
 
-template <bool F16>
-__global__ __launch_bounds__(256) void ddim_cfg_step_kernel(const DdimParams p) {
+template <bool F16, typename... RowGuidance>
+__global__ __launch_bounds__(256) void ddim_cfg_step_kernel(const DdimParams p, const RowGuidance*... guidance_rows) {
+    static_assert(sizeof...(RowGuidance) <= 1, "scalar step (no array) or one per-row guidance array");
     const long total = (long)p.B * p.HW;                   // one thread per pixel (4 channels = 16 B)
     float sa_t = p.sqrt_a_t, s1_t = p.sqrt_1m_a_t, sa_p = p.sqrt_a_prev, s1_p = p.sqrt_1m_a_prev, sa_n = p.sqrt_a_next, s1_n = p.sqrt_1m_a_next;
     if (p.coefs) {                                         // schedule coefficients from device memory (HIP-graph replay of a step)
@@ -28,6 +33,8 @@ __global__ __launch_bounds__(256) void ddim_cfg_step_kernel(const DdimParams p) 
         const float4 ec = reinterpret_cast<const float4*>(p.eps)[i];
         const float4 eu = reinterpret_cast<const float4*>(p.eps)[i + total];
         float zz[4] = {z.x, z.y, z.z, z.w};
+        float g = p.guidance;
+        if constexpr (sizeof...(RowGuidance) == 1) g = (guidance_rows[i / p.HW], ...);     // the latent row of this pixel
         const float c[4] = {ec.x, ec.y, ec.z, ec.w};
         const float u[4] = {eu.x, eu.y, eu.z, eu.w};
         float mk = 1.f;
@@ -45,7 +52,7 @@ __global__ __launch_bounds__(256) void ddim_cfg_step_kernel(const DdimParams p) 
         }
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-            const float eps = u[e] + p.guidance * (c[e] - u[e]);
+            const float eps = u[e] + g * (c[e] - u[e]);
             const float x0 = (zz[e] - s1_t * eps) / sa_t;
             float zn = sa_p * x0 + s1_p * eps + vn[e];
             if (p.mask) {
@@ -203,14 +210,25 @@ inline unsigned grid_for(long work_items) {
 
 }  // namespace
 
-int imd_launch_ddim_cfg_step(const DdimParams& p, hipStream_t s) {
-    if (p.B <= 0 || p.HW <= 0) return imd_set_error("ddim_cfg_step: empty latent");
-    if (p.mask && (!p.z_img || !p.noise)) return imd_set_error("ddim_cfg_step: inpaint mask given without image latents / noise");
-    if (p.var_noise && p.coefs) return imd_set_error("ddim_cfg_step: the stochastic step (var_noise) takes host coefficients, not the device table");
-    if (p.dtype == IMD_DTYPE_F16) hipLaunchKernelGGL(ddim_cfg_step_kernel<true>, dim3(grid_for((long)p.B * p.HW)), dim3(256), 0, s, p);
-    else if (p.dtype == IMD_DTYPE_BF16) hipLaunchKernelGGL(ddim_cfg_step_kernel<false>, dim3(grid_for((long)p.B * p.HW)), dim3(256), 0, s, p);
-    else return imd_set_error("ddim_cfg_step: unknown dtype %d", p.dtype);
-    return imd_check_launch("ddim_cfg_step");
+namespace {
+// guidance_rows: none (the scalar step) or one device [B] fp32 array
+template <typename... RowGuidance>
+int launch_ddim_cfg_step(const DdimParams& p, hipStream_t s, const char* what, const RowGuidance*... guidance_rows) {
+    if (p.B <= 0 || p.HW <= 0) return imd_set_error("%s: empty latent", what);
+    if (p.mask && (!p.z_img || !p.noise)) return imd_set_error("%s: inpaint mask given without image latents / noise", what);
+    if (p.var_noise && p.coefs) return imd_set_error("%s: the stochastic step (var_noise) takes host coefficients, not the device table", what);
+    if (p.dtype == IMD_DTYPE_F16) hipLaunchKernelGGL((ddim_cfg_step_kernel<true, RowGuidance...>), dim3(grid_for((long)p.B * p.HW)), dim3(256), 0, s, p, guidance_rows...);
+    else if (p.dtype == IMD_DTYPE_BF16) hipLaunchKernelGGL((ddim_cfg_step_kernel<false, RowGuidance...>), dim3(grid_for((long)p.B * p.HW)), dim3(256), 0, s, p, guidance_rows...);
+    else return imd_set_error("%s: unknown dtype %d", what, p.dtype);
+    return imd_check_launch(what);
+}
+}  // namespace
+
+int imd_launch_ddim_cfg_step(const DdimParams& p, hipStream_t s) { return launch_ddim_cfg_step(p, s, "ddim_cfg_step"); }
+
+int imd_launch_ddim_cfg_step_rows(const DdimParams& p, const float* guidance, hipStream_t s) {
+    if (!guidance) return imd_set_error("ddim_cfg_step_rows: null guidance array");
+    return launch_ddim_cfg_step(p, s, "ddim_cfg_step_rows", guidance);
 }
 
 int imd_launch_timestep_embedding(const float* t, float* out, int B, int dim, hipStream_t s) {

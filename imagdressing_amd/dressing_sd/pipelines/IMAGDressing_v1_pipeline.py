@@ -6,7 +6,7 @@ from typing import Any, Callable, Dict, List, Optional, Union
 
 import torch
 
-from ._base import PipelineBase, RefSAttnProcessor2_0, StableDiffusionPipelineOutput, set_scale_by_type
+from ._base import PipelineBase, RefSAttnProcessor2_0, StableDiffusionPipelineOutput, min_guidance, per_call_value, set_scale_by_type
 
 
 class IMAGDressing_v1(PipelineBase):
@@ -31,28 +31,31 @@ class IMAGDressing_v1(PipelineBase):
                  # --- extensions: bypass the out-of-scope encoders / inject latents / shard over ranks ---
                  ref_clip_hidden_states: Optional[torch.Tensor] = None, ref_image_latents: Optional[torch.Tensor] = None,
                  latents: Optional[torch.Tensor] = None, shard_over_ranks: bool = False, trace: Optional[list] = None, **kwargs):
-        if guidance_scale <= 1.0:
+        R = self._request_count(dict(prompt=prompt, prompt_embeds=prompt_embeds, negative_prompt=negative_prompt, null_prompt=null_prompt,
+                                     negative_prompt_embeds=negative_prompt_embeds, ref_image=ref_image, ref_clip_image=ref_clip_image,
+                                     ref_clip_hidden_states=ref_clip_hidden_states, ref_image_latents=ref_image_latents,
+                                     guidance_scale=guidance_scale, image_scale=image_scale),
+                                dict(num_inference_steps=num_inference_steps, eta=eta), shard_over_ranks)
+        num_inference_steps, eta = per_call_value("num_inference_steps", num_inference_steps), per_call_value("eta", eta)
+        if min_guidance(guidance_scale) <= 1.0:
             # the reference cannot run this either: its loop indexes the CFG pair unconditionally (cache["hidden_states"][1] :476-479,
             # latent_model_input[1] :511) and null_prompt_embeds is only bound under do_classifier_free_guidance (:431-435)
             raise NotImplementedError("guidance_scale <= 1: the reference's loop indexes the CFG pair unconditionally "
                                       "(IMAGDressing_v1_pipeline.py:476-479, :511); sample with guidance_scale > 1")
-        self.set_scale(image_scale)                                        # :374
+        scale, scale_rows = self._image_scales(image_scale, R)
+        self.set_scale(scale)                                              # :374
         device = self.device
         self._cross_attention_kwargs = cross_attention_kwargs
-        prompt_embeds, negative_prompt_embeds = self.encode_prompt(
-            prompt, device, num_images_per_prompt, True, negative_prompt, prompt_embeds=prompt_embeds,
-            negative_prompt_embeds=negative_prompt_embeds, clip_skip=clip_skip)                     # :395-405
-        if ref_clip_image is None and ref_clip_hidden_states is None:
-            # the reference falls back to text "null prompt" tokens as garment-UNet context (:416-427)
-            cloth_tokens, _ = self.encode_prompt(null_prompt, device, 1, False)
-        else:
-            cloth_tokens = self._cloth_tokens(ref_clip_image, ref_clip_hidden_states, device)      # :409-415
-        lat = self.prepare_latents(num_images_per_prompt, 4, width, height, torch.float32, device, generator, latents)
+        prompt_embeds, negative_prompt_embeds = self._request_prompts(
+            R, prompt, negative_prompt, prompt_embeds, negative_prompt_embeds, device, clip_skip)      # :395-405
+        ref_lat, cloth_tokens, G = self._request_garments(R, null_prompt, ref_image, ref_image_latents, ref_clip_image,
+                                                          ref_clip_hidden_states, device)              # :409-427, :454-458
+        lat = self.prepare_latents(R * num_images_per_prompt, 4, width, height, torch.float32, device, generator, latents)
         lat = self._shard(lat, shard_over_ranks)
-        ref_lat = self._ref_latents(ref_image, ref_image_latents)                                   # :454-458
-        sa = self._sa_states(ref_lat, cloth_tokens, shard_over_ranks)                               # :465-480
+        sa = self._sa_states(ref_lat, cloth_tokens, shard_over_ranks, G)                             # :465-480
         out = self.denoise(latents=lat, prompt_embeds=prompt_embeds, negative_prompt_embeds=negative_prompt_embeds,
                            sa_hidden_states=sa, num_inference_steps=num_inference_steps, guidance_scale=guidance_scale,
                            callback=callback, callback_steps=callback_steps or 1, trace=trace,
-                           eta=eta, generator=generator, variance_noise=kwargs.get("variance_noise"))           # eta: :451, :530
+                           eta=eta, generator=generator, variance_noise=kwargs.get("variance_noise"),          # eta: :451, :530
+                           requests=R, image_scale=scale_rows)
         return self._decode(out, output_type, generator)                                            # :544-547

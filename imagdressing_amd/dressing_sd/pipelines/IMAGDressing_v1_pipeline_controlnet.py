@@ -6,7 +6,8 @@ from typing import Any, Callable, Dict, List, Optional, Union
 
 import torch
 
-from ._base import (PipelineBase, RefSAttnProcessor2_0, controlnet_keep, first, set_scale_by_type, to_image_tensor)
+from ._base import (PipelineBase, RefSAttnProcessor2_0, as_batch, controlnet_keep, first, min_guidance, per_call_value, set_scale_by_type,
+                    to_image_tensor)
 
 
 class IMAGDressing_v1(PipelineBase):
@@ -42,33 +43,37 @@ class IMAGDressing_v1(PipelineBase):
                  control_guidance_start: Union[float, List[float]] = 0.0, control_guidance_end: Union[float, List[float]] = 1.0,
                  ref_clip_hidden_states: Optional[torch.Tensor] = None, ref_image_latents: Optional[torch.Tensor] = None,
                  latents: Optional[torch.Tensor] = None, shard_over_ranks: bool = False, trace: Optional[list] = None, **kwargs):
-        if guess_mode or guidance_scale <= 1.0:
+        R = self._request_count(dict(prompt=prompt, prompt_embeds=prompt_embeds, negative_prompt=negative_prompt, null_prompt=null_prompt,
+                                     negative_prompt_embeds=negative_prompt_embeds, ref_image=ref_image, ref_clip_image=ref_clip_image,
+                                     ref_clip_hidden_states=ref_clip_hidden_states, ref_image_latents=ref_image_latents,
+                                     pose_image=pose_image, guidance_scale=guidance_scale, image_scale=image_scale),
+                                dict(num_inference_steps=num_inference_steps, eta=eta, controlnet_conditioning_scale=controlnet_conditioning_scale),
+                                shard_over_ranks)
+        num_inference_steps, eta = per_call_value("num_inference_steps", num_inference_steps), per_call_value("eta", eta)
+        if guess_mode or min_guidance(guidance_scale) <= 1.0:
             # neither runs in the reference: with guess_mode its ControlNet sees the cond half only and the loop then indexes
             # down_block[1] of a batch-1 tensor (..._ipa_controlnet.py:634-639, :662-665; the zero-padding lines are commented out);
             # without CFG latent_model_input[1] does not exist (:672, :690)
             raise NotImplementedError("guess_mode / guidance_scale <= 1: the reference's loop indexes the CFG pair of the ControlNet "
                                       "residuals and of the latents unconditionally (..._ipa_controlnet.py:662-690)")
-        self.set_scale(image_scale)
+        scale, scale_rows = self._image_scales(image_scale, R)
+        self.set_scale(scale)
         device = self.device
         self._cross_attention_kwargs = cross_attention_kwargs
-        prompt_embeds, negative_prompt_embeds = self.encode_prompt(
-            prompt, device, num_images_per_prompt, True, negative_prompt, prompt_embeds=prompt_embeds,
-            negative_prompt_embeds=negative_prompt_embeds, clip_skip=clip_skip)
-        if ref_clip_image is None and ref_clip_hidden_states is None:
-            cloth_tokens, _ = self.encode_prompt(null_prompt, device, 1, False)
-        else:
-            cloth_tokens = self._cloth_tokens(ref_clip_image, ref_clip_hidden_states, device)
-        control = self._control(pose_image, prompt_embeds, negative_prompt_embeds, num_inference_steps,
+        prompt_embeds, negative_prompt_embeds = self._request_prompts(
+            R, prompt, negative_prompt, prompt_embeds, negative_prompt_embeds, device, clip_skip)
+        ref_lat, cloth_tokens, G = self._request_garments(R, null_prompt, ref_image, ref_image_latents, ref_clip_image,
+                                                          ref_clip_hidden_states, device)
+        control = self._control(as_batch(pose_image, "pose_image"), prompt_embeds, negative_prompt_embeds, num_inference_steps,
                                 controlnet_conditioning_scale, control_guidance_start, control_guidance_end, device,
                                 size=(height, width))
         if control is not None:
             height, width = control["image"].shape[-2:]                     # :501
-        lat = self._shard(self.prepare_latents(num_images_per_prompt, 4, width, height, torch.float32, device, generator, latents),
+        lat = self._shard(self.prepare_latents(R * num_images_per_prompt, 4, width, height, torch.float32, device, generator, latents),
                           shard_over_ranks)
-        ref_lat = self._ref_latents(ref_image, ref_image_latents)
-        sa = self._sa_states(ref_lat, cloth_tokens, shard_over_ranks)
+        sa = self._sa_states(ref_lat, cloth_tokens, shard_over_ranks, G)
         out = self.denoise(latents=lat, prompt_embeds=prompt_embeds, negative_prompt_embeds=negative_prompt_embeds,
                            sa_hidden_states=sa, num_inference_steps=num_inference_steps, guidance_scale=guidance_scale,
                            control=control, callback=callback, callback_steps=callback_steps or 1, trace=trace,
-                           eta=eta, generator=generator, variance_noise=kwargs.get("variance_noise"))
+                           eta=eta, generator=generator, variance_noise=kwargs.get("variance_noise"), requests=R, image_scale=scale_rows)
         return self._decode(out, output_type, generator)

@@ -6,8 +6,8 @@ from typing import Any, Callable, Dict, List, Optional, Union
 
 import torch
 
-from ._base import (PipelineBase, RefSAttnProcessor2_0, controlnet_keep, first, randn_tensor, set_scale_by_type,
-                    to_image_tensor)
+from ._base import (PipelineBase, RefSAttnProcessor2_0, RequestLayout, as_batch, controlnet_keep, first, min_guidance, per_call_value,
+                    randn_tensor, set_scale_by_type, to_image_tensor)
 
 
 class IMAGDressing_v1(PipelineBase):
@@ -43,35 +43,43 @@ class IMAGDressing_v1(PipelineBase):
                  ref_clip_hidden_states: Optional[torch.Tensor] = None, ref_image_latents: Optional[torch.Tensor] = None,
                  image_latents: Optional[torch.Tensor] = None, mask_latents: Optional[torch.Tensor] = None,
                  noise: Optional[torch.Tensor] = None, shard_over_ranks: bool = False, trace: Optional[list] = None, **kwargs):
-        if guess_mode or guidance_scale <= 1.0 or padding_mask_crop is not None or timesteps:
+        R = self._request_count(dict(prompt=prompt, prompt_embeds=prompt_embeds, negative_prompt=negative_prompt, null_prompt=null_prompt,
+                                     negative_prompt_embeds=negative_prompt_embeds, ref_image=ref_image, ref_clip_image=ref_clip_image,
+                                     ref_clip_hidden_states=ref_clip_hidden_states, ref_image_latents=ref_image_latents,
+                                     control_image=control_image, image=image, mask_image=mask_image, image_latents=image_latents,
+                                     mask_latents=mask_latents, guidance_scale=guidance_scale, image_scale=image_scale),
+                                dict(num_inference_steps=num_inference_steps, strength=strength, eta=eta,
+                                     controlnet_conditioning_scale=controlnet_conditioning_scale), shard_over_ranks)
+        num_inference_steps, strength, eta = (per_call_value("num_inference_steps", num_inference_steps), per_call_value("strength", strength),
+                                              per_call_value("eta", eta))
+        if guess_mode or min_guidance(guidance_scale) <= 1.0 or padding_mask_crop is not None or timesteps:
             raise NotImplementedError("guess_mode, guidance_scale <= 1, padding_mask_crop and custom timesteps are not implemented "
                                       "(the reference script uses none of them)")
         if not 0.0 < float(strength) <= 1.0:
             raise ValueError(f"The value of strength should in (0.0, 1.0] but is {strength}")           # diffusers check_inputs (0.0 leaves no step)
         callback = kwargs.pop("callback", None)
         callback_steps = kwargs.pop("callback_steps", None) or 1
-        self.set_scale(image_scale)
+        scale, scale_rows = self._image_scales(image_scale, R)
+        self.set_scale(scale)
         device = self.device
         self._cross_attention_kwargs = cross_attention_kwargs
-        prompt_embeds, negative_prompt_embeds = self.encode_prompt(
-            prompt, device, num_images_per_prompt, True, negative_prompt, prompt_embeds=prompt_embeds,
-            negative_prompt_embeds=negative_prompt_embeds, clip_skip=clip_skip)
-        if ref_clip_image is None and ref_clip_hidden_states is None:
-            cloth_tokens, _ = self.encode_prompt(null_prompt, device, 1, False)
-        else:
-            cloth_tokens = self._cloth_tokens(ref_clip_image, ref_clip_hidden_states, device)
+        prompt_embeds, negative_prompt_embeds = self._request_prompts(
+            R, prompt, negative_prompt, prompt_embeds, negative_prompt_embeds, device, clip_skip)
+        ref_lat, cloth_tokens, G = self._request_garments(R, null_prompt, ref_image, ref_image_latents, ref_clip_image,
+                                                          ref_clip_hidden_states, device)
         steps_run = min(int(num_inference_steps * float(strength)), num_inference_steps)          # the gate is over the timesteps actually run (:376-381)
-        control = dict(image=to_image_tensor(control_image, device, normalize=False, size=(height, width), multiple=self.vae_scale_factor),
+        control = dict(image=to_image_tensor(as_batch(control_image, "control_image"), device, normalize=False, size=(height, width),
+                                             multiple=self.vae_scale_factor),
                        prompt_embeds=prompt_embeds,
                        negative_prompt_embeds=negative_prompt_embeds, scale=float(first(controlnet_conditioning_scale)),
                        keep=controlnet_keep(max(steps_run, 1), float(first(control_guidance_start)), float(first(control_guidance_end))))
-        B = num_images_per_prompt
+        B = R * num_images_per_prompt
         h, w = height // self.vae_scale_factor, width // self.vae_scale_factor
         # strength == 1.0: start from pure noise; the SAME noise re-noises the original latents in the blend (:496-498).
         # strength < 1.0 (:316-341 -> diffusers get_timesteps / prepare_latents): run the last int(steps * strength) timesteps,
         # starting from add_noise(image_latents, noise, first of them).  Explicit ``latents`` are taken as the noise, as diffusers does.
         if image_latents is None:                                             # (before the noise draw, like diffusers' prepare_latents)
-            image_latents = self._image_latents(image, device, generator, size=(height, width))
+            image_latents = self._image_latents(as_batch(image, "image"), device, generator, size=(height, width))
         if noise is None:
             noise = latents if latents is not None else randn_tensor((B, 4, h, w), generator=generator, device=device, dtype=torch.float32)
         init_steps = min(int(num_inference_steps * float(strength)), num_inference_steps)
@@ -85,17 +93,19 @@ class IMAGDressing_v1(PipelineBase):
             self.scheduler.set_timesteps(num_inference_steps, device=device)
             t0 = int(self.scheduler.timesteps[t_start * getattr(self.scheduler, "order", 1)])
             il = image_latents.to(device=device, dtype=torch.float32)
-            lat = self.scheduler.add_noise(il.expand(B, -1, -1, -1) if il.shape[0] != B else il, noise.to(device=device, dtype=torch.float32), t0)
+            if il.shape[0] != B:                                              # one person image shared, or one per request (request-major rows)
+                il = il.expand(B, -1, -1, -1) if il.shape[0] == 1 else RequestLayout(R, num_images_per_prompt).expand(il, "image / image_latents")
+            lat = self.scheduler.add_noise(il, noise.to(device=device, dtype=torch.float32), t0)
         if mask_latents is None:                                              # prepare_mask_latents: nearest resize to h x w
-            m = to_image_tensor(mask_image, device, normalize=False)[:, :1]
+            m = to_image_tensor(as_batch(mask_image, "mask_image"), device, normalize=False)[:, :1]
             m = (m >= 0.5).float()
             mask_latents = torch.nn.functional.interpolate(m, size=(h, w))
         lat, noise_s = self._shard(lat, shard_over_ranks), self._shard(noise.to(device), shard_over_ranks)
-        ref_lat = self._ref_latents(ref_image, ref_image_latents)
-        sa = self._sa_states(ref_lat, cloth_tokens, shard_over_ranks)
+        sa = self._sa_states(ref_lat, cloth_tokens, shard_over_ranks, G)
         inpaint = dict(mask=mask_latents, image_latents=image_latents, noise=noise_s)
         out = self.denoise(latents=lat, prompt_embeds=prompt_embeds, negative_prompt_embeds=negative_prompt_embeds,
                            sa_hidden_states=sa, num_inference_steps=num_inference_steps, guidance_scale=guidance_scale,
                            control=control, inpaint=inpaint, callback=callback, callback_steps=callback_steps, trace=trace,
-                           eta=eta, generator=generator, variance_noise=kwargs.get("variance_noise"), t_start=t_start)
+                           eta=eta, generator=generator, variance_noise=kwargs.get("variance_noise"), t_start=t_start,
+                           requests=R, image_scale=scale_rows)
         return self._decode(out, output_type, generator)

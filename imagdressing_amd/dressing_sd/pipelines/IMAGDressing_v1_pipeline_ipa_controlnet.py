@@ -8,8 +8,19 @@ from typing import Any, Callable, Dict, List, Optional, Union
 import torch
 
 from ...adapter.resampler import ProjPlusModel
-from ._base import (IPAttnProcessor2_0, LoRAIPAttnProcessor2_0, LoraRefSAttnProcessor2_0, PipelineBase, controlnet_keep, first,
-                    set_scale_by_type, to_image_tensor)
+from ._base import (IPAttnProcessor2_0, LoRAIPAttnProcessor2_0, LoraRefSAttnProcessor2_0, PipelineBase, as_batch, controlnet_keep, first,
+                    min_guidance, per_call_value, request_rows, set_scale_by_type, to_image_tensor)
+
+
+def _faces(name, value):
+    """a per-request face argument: a list whose entries are all None is no face; a list mixing None and faces raises"""
+    if isinstance(value, (list, tuple)):
+        present = [v is not None for v in value]
+        if any(present) and not all(present):
+            raise ValueError(f"{name} mixes requests with and without a face: one IP-Adapter call is all with faces or all without")
+        if not any(present):
+            return None
+    return as_batch(value, name)
 
 
 class IMAGDressing_v1(PipelineBase):
@@ -82,27 +93,45 @@ class IMAGDressing_v1(PipelineBase):
                  ref_clip_hidden_states: Optional[torch.Tensor] = None, ref_image_latents: Optional[torch.Tensor] = None,
                  face_clip_hidden_states: Optional[torch.Tensor] = None, face_uncond_clip_hidden_states: Optional[torch.Tensor] = None,
                  latents: Optional[torch.Tensor] = None, shard_over_ranks: bool = False, trace: Optional[list] = None, **kwargs):
-        if guess_mode or guidance_scale <= 1.0:
+        R = self._request_count(dict(prompt=prompt, prompt_embeds=prompt_embeds, negative_prompt=negative_prompt, null_prompt=null_prompt,
+                                     negative_prompt_embeds=negative_prompt_embeds, ref_image=ref_image, ref_clip_image=ref_clip_image,
+                                     ref_clip_hidden_states=ref_clip_hidden_states, ref_image_latents=ref_image_latents,
+                                     pose_image=pose_image, face_clip_image=face_clip_image, faceid_embeds=faceid_embeds,
+                                     face_clip_hidden_states=face_clip_hidden_states,
+                                     face_uncond_clip_hidden_states=face_uncond_clip_hidden_states,
+                                     guidance_scale=guidance_scale, image_scale=image_scale),
+                                dict(num_inference_steps=num_inference_steps, eta=eta, ipa_scale=ipa_scale, s_lora_scale=s_lora_scale,
+                                     c_lora_scale=c_lora_scale, controlnet_conditioning_scale=controlnet_conditioning_scale), shard_over_ranks)
+        num_inference_steps, eta = per_call_value("num_inference_steps", num_inference_steps), per_call_value("eta", eta)
+        if R > 1:
+            ipa_scale, s_lora_scale, c_lora_scale = (per_call_value("ipa_scale", ipa_scale), per_call_value("s_lora_scale", s_lora_scale),
+                                                     per_call_value("c_lora_scale", c_lora_scale))
+        if guess_mode or min_guidance(guidance_scale) <= 1.0:
             # neither runs in the reference: with guess_mode its ControlNet sees the cond half only and the loop then indexes
             # down_block[1] of a batch-1 tensor (..._ipa_controlnet.py:634-639, :662-665; the zero-padding lines are commented out);
             # without CFG latent_model_input[1] does not exist (:672, :690)
             raise NotImplementedError("guess_mode / guidance_scale <= 1: the reference's loop indexes the CFG pair of the ControlNet "
                                       "residuals and of the latents unconditionally (..._ipa_controlnet.py:662-690)")
+        # the face tokens ride in the text context of every row: one call has a face for every request or for none
+        face_clip_image, faceid_embeds = _faces("face_clip_image", face_clip_image), _faces("faceid_embeds", faceid_embeds)
+        face_clip_hidden_states = _faces("face_clip_hidden_states", face_clip_hidden_states)
+        face_uncond_clip_hidden_states = _faces("face_uncond_clip_hidden_states", face_uncond_clip_hidden_states)
         has_face = face_clip_image is not None or face_clip_hidden_states is not None
+        scale, scale_rows = self._image_scales(image_scale, R)
         if not has_face:                                                      # :432-437
-            self.set_scale(image_scale, lora_scale=0.0)
+            self.set_scale(scale, lora_scale=0.0)
             self.set_ipa_scale(ipa_scale=0.0, lora_scale=0.0)
         else:
-            self.set_scale(image_scale, lora_scale=s_lora_scale)
+            self.set_scale(scale, lora_scale=s_lora_scale)
             self.set_ipa_scale(ipa_scale, lora_scale=c_lora_scale)
         device = self.device
         self._cross_attention_kwargs = cross_attention_kwargs
-        prompt_embeds, negative_prompt_embeds = self.encode_prompt(
-            prompt, device, num_images_per_prompt, True, negative_prompt, prompt_embeds=prompt_embeds,
-            negative_prompt_embeds=negative_prompt_embeds, clip_skip=clip_skip)
+        prompt_embeds, negative_prompt_embeds = self._request_prompts(
+            R, prompt, negative_prompt, prompt_embeds, negative_prompt_embeds, device, clip_skip)
         control = None
         if pose_image is not None:                                            # ControlNet sees the 77 text tokens only (:550)
-            control = dict(image=to_image_tensor(pose_image, device, normalize=False, size=(height, width), multiple=self.vae_scale_factor),
+            control = dict(image=to_image_tensor(as_batch(pose_image, "pose_image"), device, normalize=False, size=(height, width),
+                                                 multiple=self.vae_scale_factor),
                            prompt_embeds=prompt_embeds,
                            negative_prompt_embeds=negative_prompt_embeds, scale=float(first(controlnet_conditioning_scale)),
                            keep=controlnet_keep(num_inference_steps, float(first(control_guidance_start)),
@@ -110,18 +139,17 @@ class IMAGDressing_v1(PipelineBase):
             height, width = control["image"].shape[-2:]
         if has_face:                                                          # :513-521, :555-557
             pos, neg = self.get_image_embeds(face_clip_image, faceid_embeds, face_clip_hidden_states, face_uncond_clip_hidden_states)
+            if R > 1:                                                         # one face per request (or one shared by all)
+                pos, neg = request_rows(pos, R, "face tokens"), request_rows(neg, R, "uncond face tokens")
             prompt_embeds = torch.cat([prompt_embeds.to(device), pos.to(prompt_embeds.dtype)], dim=1)
             negative_prompt_embeds = torch.cat([negative_prompt_embeds.to(device), neg.to(negative_prompt_embeds.dtype)], dim=1)
-        if ref_clip_image is None and ref_clip_hidden_states is None:
-            cloth_tokens, _ = self.encode_prompt(null_prompt, device, 1, False)
-        else:
-            cloth_tokens = self._cloth_tokens(ref_clip_image, ref_clip_hidden_states, device)
-        lat = self._shard(self.prepare_latents(num_images_per_prompt, 4, width, height, torch.float32, device, generator, latents),
+        ref_lat, cloth_tokens, G = self._request_garments(R, null_prompt, ref_image, ref_image_latents, ref_clip_image,
+                                                          ref_clip_hidden_states, device)
+        lat = self._shard(self.prepare_latents(R * num_images_per_prompt, 4, width, height, torch.float32, device, generator, latents),
                           shard_over_ranks)
-        ref_lat = self._ref_latents(ref_image, ref_image_latents)
-        sa = self._sa_states(ref_lat, cloth_tokens, shard_over_ranks)
+        sa = self._sa_states(ref_lat, cloth_tokens, shard_over_ranks, G)
         out = self.denoise(latents=lat, prompt_embeds=prompt_embeds, negative_prompt_embeds=negative_prompt_embeds,
                            sa_hidden_states=sa, num_inference_steps=num_inference_steps, guidance_scale=guidance_scale,
                            control=control, callback=callback, callback_steps=callback_steps or 1, trace=trace,
-                           eta=eta, generator=generator, variance_noise=kwargs.get("variance_noise"))
+                           eta=eta, generator=generator, variance_noise=kwargs.get("variance_noise"), requests=R, image_scale=scale_rows)
         return self._decode(out, output_type, generator)

@@ -23,7 +23,7 @@ modules supplied by the caller, or bypassed with pre-computed tensors (``prompt_
 from __future__ import annotations
 
 from dataclasses import dataclass
-from typing import Any, Callable, Dict, List, Optional, Union
+from typing import Any, Callable, Dict, List, Optional, Sequence, Union
 
 import torch
 
@@ -175,16 +175,26 @@ class PipelineBase:
 
     # ---- garment features (A2 of SURVEY 8a) ----
     @torch.no_grad()
-    def garment_features(self, ref_image_latents: torch.Tensor, cloth_proj_embed: torch.Tensor) -> Dict[str, torch.Tensor]:
+    def garment_features(self, ref_image_latents: torch.Tensor, cloth_proj_embed: torch.Tensor, garments: int = 1) -> Dict[str, torch.Tensor]:
         """Garment UNet once at t = 0 with the 16 resampler tokens as context; returns the (post-LayerNorm)
-        input of every attention layer, [1, M, C] each (IMAGDressing_v1_pipeline.py:465-480)."""
+        input of every attention layer, [1, M, C] each (IMAGDressing_v1_pipeline.py:465-480) -- or [G, M, C] for ``garments`` = G
+        distinct garments of a request-batched call (one garment-UNet forward at batch G)."""
         with ops.tuning_scope(**(getattr(self, "_tuning", None) or {})):
-            return self._garment_features(ref_image_latents, cloth_proj_embed)
+            return self._garment_features(ref_image_latents, cloth_proj_embed, garments)
 
-    def _garment_features(self, ref_image_latents, cloth_proj_embed):
+    def _garment_features(self, ref_image_latents, cloth_proj_embed, garments: int = 1):
+        """``garments`` = G > 1 (a request-batched call): ``ref_image_latents`` / ``cloth_proj_embed`` hold one row per garment and the
+        garment UNet runs ONE forward at batch G -> [G, M, C] per layer (row g = garment g)."""
         dt = self.reference_unet.dtype
-        x = nchw_to_nhwc8(ref_image_latents[:1].to(self.device), dt)
-        ehs = cloth_proj_embed[-1:].to(device=self.device, dtype=dt).contiguous()     # the cond half ([1] of the CFG pair)
+        if garments > 1:
+            if ref_image_latents.shape[0] != garments or cloth_proj_embed.shape[0] != garments:
+                raise ValueError(f"{garments} garments: ref_image_latents has {ref_image_latents.shape[0]} rows and the garment tokens "
+                                 f"{cloth_proj_embed.shape[0]}")
+            x = nchw_to_nhwc8(ref_image_latents.to(self.device), dt)
+            ehs = cloth_proj_embed.to(device=self.device, dtype=dt).contiguous()
+        else:
+            x = nchw_to_nhwc8(ref_image_latents[:1].to(self.device), dt)
+            ehs = cloth_proj_embed[-1:].to(device=self.device, dtype=dt).contiguous()     # the cond half ([1] of the CFG pair)
         self.reference_unet.forward_nhwc(x, 0, ehs)
         out = {}
         for name, proc in self.reference_unet.attn_processors.items():
@@ -199,11 +209,19 @@ class PipelineBase:
             return self._denoise(**kw)
 
     def _denoise(self, *, latents: torch.Tensor, prompt_embeds: torch.Tensor, negative_prompt_embeds: torch.Tensor,
-                sa_hidden_states: Dict[str, torch.Tensor], num_inference_steps: int, guidance_scale: float,
+                sa_hidden_states: Dict[str, torch.Tensor], num_inference_steps: int, guidance_scale: Union[float, Sequence[float]],
                 control: Optional[dict] = None, inpaint: Optional[dict] = None,
                 callback: Optional[Callable] = None, callback_steps: int = 1, trace: Optional[list] = None,
-                eta: float = 0.0, generator=None, variance_noise: Optional[List[torch.Tensor]] = None, t_start: int = 0) -> torch.Tensor:
+                eta: float = 0.0, generator=None, variance_noise: Optional[List[torch.Tensor]] = None, t_start: int = 0,
+                requests: int = 1, image_scale: Optional[Sequence[float]] = None) -> torch.Tensor:
         """latents [B, 4, h, w] fp32 -> final latents [B, 4, h, w] fp32.
+
+        ``requests`` = R > 1: a request-batched call (:class:`RequestLayout`) -- latent rows [r n, (r+1) n) belong to request r
+        (n = B / R); ``prompt_embeds`` / ``negative_prompt_embeds`` (and the ControlNet's) hold R rows (or 1, shared); garment
+        tensors in ``sa_hidden_states`` hold R rows (or 1, shared); ``guidance_scale`` may be a sequence of R values (the per-row
+        fused step, ``imd_ddim_cfg_step_rows``, when they differ) and ``image_scale`` a sequence of R garment-branch weights
+        (carried in the ``sa_batch_mask`` rows; the processors' own ``scale`` is then expected to be 1).  ``control["image"]`` and
+        the ``inpaint`` tensors hold 1, R or B rows.
 
         ``eta`` > 0 (DDIM only; other schedulers ignore it, like ``prepare_extra_step_kwargs``, IMAGDressing_v1_pipeline.py:102-119):
         the stochastic step, noise per step = ``variance_noise[i]`` [B, 4, h, w] or a draw of that shape in the UNet's element type
@@ -218,6 +236,17 @@ class PipelineBase:
         dev = self.device
         B, Cl, h, w = latents.shape
         HW = h * w
+        lay = RequestLayout(int(requests), B // max(int(requests), 1))
+        if lay.requests < 1 or lay.rows != B:
+            raise ValueError(f"{B} latent rows cannot be split into {requests} requests")
+        gs = per_request_floats("guidance_scale", guidance_scale, lay.requests)
+        multistep = hasattr(self.scheduler, "step_guided")        # UniPC: latent updates are host-computed linear combinations
+        if len(set(gs)) > 1 and multistep:
+            raise ValueError("guidance_scale differs between the requests: the per-request guidance step is the fused DDIM step; "
+                             "UniPC takes one guidance scale per call")
+        # uniform guidance: the scalar step (a single-request call is unchanged); otherwise one fp32 value per latent row, alive for the
+        # whole call (a captured step graph reads it at every replay)
+        g_arg = gs[0] if len(set(gs)) == 1 else lay.per_row(gs).to(dev)
         sch = self.scheduler
         sch.set_timesteps(num_inference_steps, device=dev)
         timesteps = [int(t) for t in sch.timesteps][int(t_start) * getattr(sch, "order", 1):]
@@ -227,27 +256,30 @@ class PipelineBase:
         dt = self.unet.dtype
         x_in = torch.zeros(2 * B, h, w, 8, dtype=dt, device=dev)
         x_in[..., :Cl] = torch.cat([z, z]).view(2 * B, h, w, Cl)
-        # rows [0,B): prompt (+garment), rows [B,2B): negative prompt, no garment -> ehs rows shared per half
-        ehs = torch.cat([prompt_embeds[:1], negative_prompt_embeds[:1]]).to(device=dev, dtype=dt).contiguous()
-        mask_rows = torch.cat([torch.ones(B), torch.zeros(B)]).to(device=dev, dtype=torch.float32)
+        # rows [0,B): prompt (+garment), rows [B,2B): negative prompt, no garment -> ehs rows shared per half (R > 1: [R prompts; R negatives],
+        # the processors' kv bdiv = n then maps cond row b to prompt b // n and uncond row B + j to negative j // n -- RequestLayout.ehs_row)
+        ehs = lay.text_context(prompt_embeds, negative_prompt_embeds).to(device=dev, dtype=dt).contiguous()
+        cond_w = torch.ones(B) if image_scale is None else lay.per_row(per_request_floats("image_scale", image_scale, lay.requests))
+        mask_rows = torch.cat([cond_w, torch.zeros(B)]).to(device=dev, dtype=torch.float32)
         # sa_pair_layout: the mask above IS "garment on for rows [0, B), off for rows [B, 2B)" -- together with cfg_pair (identical latents in
         # the two halves) it lets the engine run the first hybrid block's self-attention phase once per image (unet.call_pair_half)
         cak = {"sa_hidden_states": sa_hidden_states, "sa_batch_mask": mask_rows, "sa_pair_layout": True}
         ctrl_img = ctrl_ehs = None
         if control is not None:
             img = control["image"]
+            if lay.requests > 1 and img.shape[0] > 1:          # one control image per request (or per image): the ControlNet batch is 2B rows
+                img = lay.expand(img, "control image").repeat(2, *([1] * (img.dim() - 1)))
             ctrl_img = img if (img.dim() == 4 and img.shape[-1] == 8 and img.dtype == dt) else nchw_to_nhwc8(img.to(dev), dt)
-            ctrl_ehs = torch.cat([control["prompt_embeds"][:1], control["negative_prompt_embeds"][:1]]).to(device=dev, dtype=dt).contiguous()
+            ctrl_ehs = lay.text_context(control["prompt_embeds"], control["negative_prompt_embeds"]).to(device=dev, dtype=dt).contiguous()
         inp = None
         if inpaint is not None:
             def nhwc(t, c):
                 t = t.to(device=dev, dtype=torch.float32)
                 if t.shape[0] != B:
-                    t = t.expand(B, -1, -1, -1)
+                    t = t.expand(B, -1, -1, -1) if t.shape[0] == 1 else lay.expand(t, "inpaint input")
                 return t.permute(0, 2, 3, 1).reshape(B, HW, c).contiguous()
             inp = dict(mask=nhwc(inpaint["mask"], 1).view(B, HW).contiguous(), z_img=nhwc(inpaint["image_latents"], Cl),
                        noise=nhwc(inpaint["noise"], Cl))
-        multistep = hasattr(sch, "step_guided")        # UniPC: latent updates are host-computed linear combinations
         if multistep and inp is not None:
             raise NotImplementedError("the inpainting blend is defined on the DDIM step (…inpainting.py:487-500)")
         keeps = None if control is None else [control.get("keep", [1.0] * len(timesteps))[i] for i in range(len(timesteps))]
@@ -267,7 +299,7 @@ class PipelineBase:
             if inp is not None:
                 kw = dict(mask=inp["mask"], z_img=inp["z_img"], noise=inp["noise"])
             if coefs is not None:
-                ops.ddim_cfg_step(z, eps, x_in.view(2 * B, HW, 8), guidance=float(guidance_scale), coefs=coefs, **kw)
+                ops.ddim_cfg_step(z, eps, x_in.view(2 * B, HW, 8), guidance=g_arg, coefs=coefs, **kw)
             else:
                 if inp is not None:
                     kw["a_next"] = sch.alpha(timesteps[i + 1]) if i < len(timesteps) - 1 else None
@@ -275,7 +307,7 @@ class PipelineBase:
                     vn = variance_noise[i] if variance_noise is not None else randn_tensor((B, Cl, h, w), generator=generator, device=dev, dtype=dt)
                     kw["var_noise"] = vn.to(device=dev, dtype=torch.float32).permute(0, 2, 3, 1).reshape(B, HW, Cl).contiguous()
                     kw["sigma"] = sch.sigma(timesteps[i], eta)
-                ops.ddim_cfg_step(z, eps, x_in.view(2 * B, HW, 8), guidance=float(guidance_scale), a_t=sch.alpha(timesteps[i]),
+                ops.ddim_cfg_step(z, eps, x_in.view(2 * B, HW, 8), guidance=g_arg, a_t=sch.alpha(timesteps[i]),
                                   a_prev=sch.alpha_prev(timesteps[i]), **kw)
 
         # The time-embedding chain depends on the timestep only: one pass over the whole schedule here, every forward of the loop picks its row
@@ -335,7 +367,7 @@ class PipelineBase:
                     if control is not None:
                         down, mid = self.controlnet.forward_nhwc(x_in, t, ctrl_ehs, ctrl_img, ctrl_scale * keeps[i])
                     eps = self.unet.forward_nhwc(x_in, t, ehs, cak, down, mid, cfg_pair=True)
-                    z = sch.step_guided(eps.view(2 * B, HW, Cl), z, float(guidance_scale))
+                    z = sch.step_guided(eps.view(2 * B, HW, Cl), z, gs[0])
                     # emit the next 16-bit UNet input (both CFG halves) from z: the fused step with eps = 0, alpha = 1 is the identity on z
                     ops.ddim_cfg_step(z, ops.workspace("zero_eps", (2 * B, HW, Cl), torch.float32, dev), x_in.view(2 * B, HW, 8),
                                       guidance=1.0, a_t=1.0, a_prev=1.0)
@@ -352,6 +384,40 @@ class PipelineBase:
         finally:
             for e in encs:
                 e.clear_time_embeddings()
+
+    # ---- request-batched calls (RequestLayout) ----
+    def _request_count(self, args: Dict[str, Any], per_call: Dict[str, Any], shard_over_ranks: bool) -> int:
+        return request_count(args, per_call, shard_over_ranks=shard_over_ranks, scheduler=self.scheduler)
+
+    def _request_prompts(self, R, prompt, negative_prompt, prompt_embeds, negative_prompt_embeds, device, clip_skip=None):
+        """(prompt embeds, negative embeds): [1 | R, T, C] each -- R rows as soon as either side speaks per request"""
+        pe, ne = self.encode_prompt(prompt, device, 1, True, negative_prompt, prompt_embeds=prompt_embeds,
+                                    negative_prompt_embeds=negative_prompt_embeds, clip_skip=clip_skip)
+        if R > 1:
+            pe, ne = request_rows(pe, R, "prompt / prompt_embeds"), request_rows(ne, R, "negative_prompt / negative_prompt_embeds")
+        return pe, ne
+
+    def _request_garments(self, R, null_prompt, ref_image, ref_image_latents, ref_clip_image, ref_clip_hidden_states, device):
+        """(garment latents, garment tokens, G): G = R distinct garments when a garment argument speaks per request, else 1 (one garment
+        shared by every request, the single-request path)."""
+        if ref_clip_image is None and ref_clip_hidden_states is None:
+            # the reference falls back to text "null prompt" tokens as garment-UNet context (:416-427)
+            cloth_tokens, _ = self.encode_prompt(null_prompt, device, 1, False)
+        else:
+            cloth_tokens = self._cloth_tokens(as_batch(ref_clip_image, "ref_clip_image"), ref_clip_hidden_states, device)      # :409-415
+        ref_lat = self._ref_latents(as_batch(ref_image, "ref_image"), ref_image_latents)                                     # :454-458
+        if R > 1 and (ref_lat.shape[0] == R or cloth_tokens.shape[0] == R):
+            return request_rows(ref_lat, R, "ref_image / ref_image_latents"), request_rows(cloth_tokens, R, "garment tokens"), R
+        return ref_lat, cloth_tokens, 1
+
+    @staticmethod
+    def _image_scales(image_scale, R):
+        """-> (the scale the processors get through set_scale, per-request weights for the loop or None).  Equal values (and a scalar) keep
+        the reference's set_scale behaviour; differing ones ride in the sa_batch_mask rows with the processors' scale at 1."""
+        if not _is_seq(image_scale):
+            return image_scale, None
+        vals = per_request_floats("image_scale", image_scale, R)
+        return (vals[0], None) if len(set(vals)) == 1 else (1.0, vals)
 
     # ---- shared front / back end ----
     def _cloth_tokens(self, ref_clip_image, ref_clip_hidden_states, device):
@@ -386,11 +452,159 @@ class PipelineBase:
         from ... import dist as imd_dist
         return imd_dist.shard_rows(latents) if shard else latents
 
-    def _sa_states(self, ref_latents, cloth_tokens, shard: bool):
+    def _sa_states(self, ref_latents, cloth_tokens, shard: bool, garments: int = 1):
         from ... import dist as imd_dist
+        if garments > 1:          # (request-batched calls refuse shard_over_ranks up front: request_count)
+            return self.garment_features(ref_latents, cloth_tokens, garments)
         if shard and imd_dist.world_size() > 1:
             return imd_dist.garment_features_broadcast(self, ref_latents, cloth_tokens)
         return self.garment_features(ref_latents, cloth_tokens)
+
+
+# ---- request-batched calls: R distinct (garment, prompt, pose / mask / face) requests in one pipeline call ----
+@dataclass(frozen=True)
+class RequestLayout:
+    """Row layout of a call with ``requests`` = R requests of ``images_per_request`` = n images each.
+
+    Latent rows are request-major: request r owns rows [r n, (r+1) n).  The UNet runs the CFG batch of 2 R n rows -- [0, Rn) cond,
+    [Rn, 2Rn) uncond -- against the text context [R prompts; R negatives] (``text_context``): the processors' kv batch divisor
+    (rows / context rows = n) maps UNet row b to context row :meth:`ehs_row`.  Garment tensors [R, M, C] serve the cond rows
+    (``sa_pair_layout``): cond row b reads garment :meth:`garment_of_row`; uncond rows have no garment branch.  R = 1 is today's
+    single-request layout: context [prompt, negative], one garment."""
+    requests: int
+    images_per_request: int
+
+    @property
+    def rows(self) -> int:
+        return self.requests * self.images_per_request
+
+    def request_of_row(self, b: int) -> int:
+        """request of latent row b (= of cond row b and of uncond row rows + b)"""
+        return (b % self.rows) // self.images_per_request
+
+    def ehs_row(self, b: int) -> int:
+        """text-context row of UNet row b of the CFG batch"""
+        return b // self.images_per_request
+
+    def garment_of_row(self, b: int) -> Optional[int]:
+        """garment of UNet row b (None: an uncond row, garment branch off)"""
+        return b // self.images_per_request if b < self.rows else None
+
+    def per_row(self, values: Sequence[float]) -> torch.Tensor:
+        """R per-request values -> [rows] fp32, one per latent row"""
+        return torch.tensor([float(v) for v in values], dtype=torch.float32).repeat_interleave(self.images_per_request)
+
+    def expand(self, t: torch.Tensor, name: str) -> torch.Tensor:
+        """[1 | R | rows, ...] -> [rows, ...] (request-major)"""
+        if t.shape[0] == self.rows:
+            return t
+        if t.shape[0] == 1:
+            return t.expand(self.rows, *t.shape[1:])
+        if t.shape[0] == self.requests:
+            return t.repeat_interleave(self.images_per_request, 0)
+        raise ValueError(f"{name} has {t.shape[0]} rows; expected 1, {self.requests} (one per request) or {self.rows} (one per image)")
+
+    def text_context(self, prompt_embeds: torch.Tensor, negative_prompt_embeds: torch.Tensor) -> torch.Tensor:
+        """[prompts; negatives]: [2, T, C] for one request (row 0 of each, as the single-request loop always took), [2R, T, C] otherwise"""
+        if self.requests == 1:
+            return torch.cat([prompt_embeds[:1], negative_prompt_embeds[:1]])
+        return torch.cat([request_rows(prompt_embeds, self.requests, "prompt_embeds"),
+                          request_rows(negative_prompt_embeds, self.requests, "negative_prompt_embeds")])
+
+
+def request_rows(t: torch.Tensor, R: int, name: str) -> torch.Tensor:
+    """[1 | R, ...] -> [R, ...]: one shared entry or one per request"""
+    if t.shape[0] == R:
+        return t
+    if t.shape[0] == 1:
+        return t.expand(R, *t.shape[1:])
+    raise ValueError(f"{name} has {t.shape[0]} entries for {R} requests (give one, shared, or one per request)")
+
+
+def _is_seq(v) -> bool:
+    return isinstance(v, (list, tuple))
+
+
+def per_request_floats(name: str, value, R: int) -> List[float]:
+    """a float or a sequence of 1 or R floats -> R floats"""
+    vals = [float(v) for v in value] if _is_seq(value) else [float(value)]
+    if len(vals) == 1:
+        return vals * R
+    if len(vals) != R:
+        raise ValueError(f"{name} has {len(vals)} entries for {R} requests")
+    return vals
+
+
+def per_call_value(name: str, value):
+    """Arguments folded into weights or shared by the schedule (steps, strength, eta, LoRA / IP-Adapter / ControlNet scales) stay per call:
+    a sequence is accepted only if its entries agree."""
+    if not _is_seq(value):
+        return value
+    if len(value) == 0 or any(v != value[0] for v in value):
+        raise ValueError(f"{name} is per call (it is folded into weights or shared by the schedule), got differing values {list(value)}")
+    return value[0]
+
+
+# batched rank of the tensor form of each per-request argument (a tensor of lower rank is ONE entry)
+_BATCHED_NDIM = dict(ref_image=4, ref_clip_image=4, ref_clip_hidden_states=3, ref_image_latents=4, prompt_embeds=3, negative_prompt_embeds=3,
+                     control_image=4, pose_image=4, image=4, mask_image=4, image_latents=4, mask_latents=4, face_clip_image=4, faceid_embeds=2,
+                     face_clip_hidden_states=3, face_uncond_clip_hidden_states=3)
+
+
+def entries(name: str, value) -> Optional[int]:
+    """How many requests an argument speaks for: a list's length, a tensor's / array's batch, None for a single value (str, float, image)."""
+    if value is None or isinstance(value, (str, bytes, int, float)):
+        return None
+    if _is_seq(value):
+        return len(value)
+    shape = getattr(value, "shape", None)
+    if shape is not None and len(shape) == _BATCHED_NDIM.get(name, -1):
+        return int(shape[0])
+    return None
+
+
+# the arguments R is inferred from (garment and prompt)
+REQUEST_KEYS = ("prompt", "prompt_embeds", "ref_image", "ref_clip_image", "ref_clip_hidden_states", "ref_image_latents")
+PER_CALL_KEYS = ("num_inference_steps", "strength", "eta", "ipa_scale", "s_lora_scale", "c_lora_scale", "controlnet_conditioning_scale")
+
+
+def request_count(args: Dict[str, Any], per_call: Optional[Dict[str, Any]] = None, *, shard_over_ranks: bool = False,
+                  scheduler=None) -> int:
+    """R of a call and the checks of a request-batched one.  R = the largest entry count of the garment / prompt arguments
+    (``REQUEST_KEYS``; 1 when all are single).  Every per-request argument in ``args`` has 1 entry (shared) or R, else ValueError
+    naming it; the per-call arguments in ``per_call`` must not differ; ``shard_over_ranks`` and UniPC with differing guidance raise."""
+    counts = {k: entries(k, v) for k, v in args.items()}
+    R = max([c for k, c in counts.items() if k in REQUEST_KEYS and c is not None] or [1])
+    for k, c in counts.items():
+        if c is not None and c not in (1, R):
+            raise ValueError(f"{k} has {c} entries for {R} requests (give one, shared, or one per request)")
+    if R > 1:
+        for k, v in (per_call or {}).items():
+            per_call_value(k, v)
+        if shard_over_ranks:
+            raise NotImplementedError("shard_over_ranks with several requests in one call: sharding requests over ranks needs a garment "
+                                      "UNet per rank (dist.garment_features_broadcast serves one garment); call per request instead")
+    g = args.get("guidance_scale")
+    if g is not None and _is_seq(g):
+        gs = per_request_floats("guidance_scale", g, R)
+        if scheduler is not None and hasattr(scheduler, "step_guided") and len(set(gs)) > 1:
+            raise ValueError("guidance_scale differs between the requests: UniPC takes one guidance scale per call (the per-request "
+                             "guidance step is the fused DDIM step)")
+    if "image_scale" in args and _is_seq(args["image_scale"]):
+        per_request_floats("image_scale", args["image_scale"], R)
+    return R
+
+
+def as_batch(value, name: str):
+    """A per-request image argument as ONE batched tensor: a list of tensors is concatenated ([C, H, W] entries get a batch axis);
+    anything else (a tensor, a PIL image or a list of them, None) is returned as is."""
+    if _is_seq(value) and value and all(isinstance(v, torch.Tensor) for v in value):
+        return torch.cat([v if v.dim() == _BATCHED_NDIM.get(name, v.dim()) else v.unsqueeze(0) for v in value])
+    return value
+
+
+def min_guidance(guidance_scale) -> float:
+    return min(float(v) for v in guidance_scale) if _is_seq(guidance_scale) else float(guidance_scale)
 
 
 def controlnet_keep(num_steps: int, start: float, end: float) -> List[float]:
@@ -444,5 +658,6 @@ def set_scale_by_type(unet, cls, **attrs):
                 setattr(proc, k, v)
 
 
-__all__ = ["controlnet_keep", "first", "to_image_tensor", "PipelineBase", "StableDiffusionPipelineOutput", "randn_tensor", "set_scale_by_type",
+__all__ = ["RequestLayout", "request_count", "request_rows", "per_request_floats", "per_call_value", "as_batch", "min_guidance", "entries",
+           "controlnet_keep", "first", "to_image_tensor", "PipelineBase", "StableDiffusionPipelineOutput", "randn_tensor", "set_scale_by_type",
            "RefSAttnProcessor2_0", "LoraRefSAttnProcessor2_0", "LoRAIPAttnProcessor2_0", "IPAttnProcessor2_0"]

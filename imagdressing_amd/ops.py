@@ -864,9 +864,18 @@ def ddim_cfg_step(z, eps, x_next, *, guidance, a_t=1.0, a_prev=1.0, mask=None, z
     """z [B,HW,4] fp32 (in place); eps [2B,HW,4] fp32; x_next [2B,HW,8] bf16 or None.  ``coefs``: device fp32 [6]
     (:func:`ddim_coefs`) read by the kernel instead of a_t / a_prev / a_next (HIP-graph replay of a step).
     ``var_noise`` [B,HW,4] fp32 + ``sigma``: the stochastic DDIM step (eta > 0) -- diffusers' ``DDIMScheduler.step``:
-    direction coefficient sqrt(1 - a_prev - sigma^2), ``+ sigma * var_noise``."""
+    direction coefficient sqrt(1 - a_prev - sigma^2), ``+ sigma * var_noise``.
+    ``guidance``: a float (``imd_ddim_cfg_step``), or a device fp32 tensor [B] -- the scale of each latent row
+    (``imd_ddim_cfg_step_rows``: a batch of requests with different guidance scales)."""
     ensure_device(z.device)
     B, HW = z.shape[0], z.shape[1]
+    rows = None
+    if isinstance(guidance, torch.Tensor):
+        if guidance.dtype != torch.float32 or guidance.numel() != B or not guidance.is_contiguous():
+            raise L.ImdError(f"ddim_cfg_step: per-row guidance must be a contiguous fp32 tensor of {B} values, got "
+                             f"{guidance.dtype} {tuple(guidance.shape)}")
+        rows = _dev(guidance, torch.float32, "guidance")
+        guidance = 0.0                           # (ignored by the per-row entry point)
     p = L.DdimParams()
     p.z, p.eps = _dev(z, torch.float32, "z"), _dev(eps, torch.float32, "eps")
     p.dtype = 0 if x_next is None else _code(x_next, "x_next")
@@ -891,7 +900,10 @@ def ddim_cfg_step(z, eps, x_next, *, guidance, a_t=1.0, a_prev=1.0, mask=None, z
     p.coefs = _opt(coefs, torch.float32, "coefs")
     if coefs is not None and coefs.numel() < 6:
         raise L.ImdError("ddim_cfg_step: coefs needs 6 fp32 values")
-    L.check(L.load().imd_ddim_cfg_step(C.byref(p), _stream()))
+    if rows is None:
+        L.check(L.load().imd_ddim_cfg_step(C.byref(p), _stream()))
+    else:
+        L.check(L.load().imd_ddim_cfg_step_rows(C.byref(p), rows, _stream()))
     return z
 
 

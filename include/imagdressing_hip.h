@@ -379,6 +379,11 @@ int imd_softmax_rows(const float* s, int s_ld, uint16_t* p, int p_ld, int rows, 
 /* CFG combine + DDIM step (+ inpaint blend) + next UNet input:
  * IMAGDressing_v1_pipeline.py:483-488,521-532; ..._pipeline_controlnet_inpainting.py:487-500. */
 int imd_ddim_cfg_step(const imd_ddim_params* p, void* stream);
+/* The same fused step with the guidance scale read PER LATENT ROW: guidance is a DEVICE [B] fp32 array (row b of z / the
+ * cond-uncond pair b, B + b of eps) and p->guidance is ignored; everything else -- coefs, var_noise, the inpaint blend, x_next --
+ * as imd_ddim_cfg_step.  One call then serves a batch of requests with different guidance scales (the pipelines'
+ * request-batched call).  With every entry equal to g it is bit-identical to imd_ddim_cfg_step with guidance = g. */
+int imd_ddim_cfg_step_rows(const imd_ddim_params* p, const float* guidance, void* stream);
 
 /* diffusers Timesteps(dim, flip_sin_to_cos=True, freq_shift=0): out[B, dim] fp32 = [cos | sin]. */
 int imd_timestep_embedding(const float* t, float* out, int B, int dim, void* stream);
