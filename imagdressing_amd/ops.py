@@ -182,7 +182,7 @@ TEMB_TABLE = _os.environ.get("IMD_TEMB_TABLE", "1") != "0"
 FUSED_GN_PROJ_CFGS = tuple(int(c) for c in _os.environ.get("IMD_FUSED_GN_PROJ_CFGS", "12,13,14").split(",") if c)
 CFG_PAIR_ATTN = _os.environ.get("IMD_CFG_PAIR_ATTN", "1") != "0"     # ... and the first hybrid block up to its self-attention phase (unet.Transformer2D.call_pair_half; A/B switch)
 FUSED_LN = True            # engines hand `LayerNorm -> attn2.to_q` on 320 channels to the row-resident kernel as ONE launch (A/B switch)
-GEMM_TRACE = None          # tools/gemm_tune.py sets this to a list to record the shapes a forward pass launches
+GEMM_TRACE = None          # tools/gemm_tune.py and tests/test_dispatch_sweep_gpu.py set this to a list to record the problems (shape + epilogue) a forward pass launches
 GEMM_EVENT_HOOK = None     # tools/insitu_conv.py sets this to a dict: every conv_gemm launch is bracketed by HIP events, keyed by (shape key, cfg, split)
 _GEMM_TABLE = None
 _CFG_DECISIONS: Dict[Tuple, Tuple[int, int]] = {}      # conv_gemm: problem description -> (tile config, K slices), see there
@@ -352,7 +352,13 @@ def conv_gemm(
     splittable = heads is None and act != ACT_GEGLU
     if GEMM_TRACE is not None:
         GEMM_TRACE.append(dict(M=M, N=N, K=K, Cin=Cin, taps=taps, Hin=Hin, Win=Win, Hout=Hout, Wout=Wout, stride=stride,
-                               ups=int(ups), splittable=splittable, dtype=str(dt)))
+                               ups=int(ups), splittable=splittable, dtype=str(dt),
+                               # the epilogue, so that a traced problem can be replayed standalone (tests/test_dispatch_sweep_gpu.py)
+                               bias=bias is not None, rowvec=rowvec is not None, rowvec_stride=rowvec_stride, res=res is not None, res_rows=res_rows, act=act, out_f32=bool(out_f32),
+                               heads=None if heads is None else dict(C=heads["C"], H=heads["H"], D=heads["D"],
+                                                                     dests=[(t is not None, kind, DP, Ltok, scale) for t, kind, DP, Ltok, scale in heads["dests"]]),
+                               gn_stats_groups=gn_stats_groups, x_pix_stride=p.x_pix_stride, out_scale=out_scale, pad_br_only=bool(pad_br_only),
+                               out_ld=p.out_ld, res_ld=p.res_ld, gn=gn is not None, gn_in=gn_in is not None, gn_out=gn_out is not None))
     # (round 6) the (tile config, K slices) decision of a call site is a pure function of the problem description: remembered per description, so
     # that a repeated layer pays neither the table key formatting nor the library's *_supported queries again (~5 of the ~75 us a processor call
     # costs on the host at the small levels).  Dropped with the tuning table (IMD_GEMM_TUNING / _GEMM_TABLE reset) and by clear_workspaces().

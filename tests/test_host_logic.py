@@ -420,6 +420,100 @@ def test_tuning_table_only_names_known_tile_configs():
         assert ent["split"] >= 1 and (ent["split"] == 1 or ent["cfg"] not in (12, 13, 14, 15, 16)), (key, ent)
 
 
+def test_dispatch_sweep_cases_cover_every_table_entry():
+    """tests/dispatch_cases.py (the plan of tests/test_dispatch_sweep_gpu.py): every key of the shipped table is launched by at least one case,
+    in every form its entry has, at a consistent geometry; a plain 3x3 key runs at a map the table does not hold, so the lookup lands on it."""
+    from collections import Counter
+    from tests import dispatch_cases as DC
+    table = DC.load_table()
+    cs = DC.cases(table)
+    ids = Counter(c.id for c in cs)
+    assert not [i for i, n in ids.items() if n > 1], "case ids repeat"
+    by_key = {}
+    for c in cs:
+        by_key.setdefault(c.key, []).append(c)
+    missing = [k for k in table if k not in by_key]
+    assert not missing, f"table entries no case launches: {missing}"
+    assert set(by_key) == set(table)
+    for key, ent in table.items():
+        forms = {c.form: c for c in by_key[key]}
+        _, (M, N, K, taps, stride, ups), hw = DC.parse_key(key)
+        assert "split" in forms and (forms["split"].table_cfg, forms["split"].table_split) == (ent["cfg"], ent["split"]), key
+        assert ("geglu" in forms) == (taps == 1 and (ent["cfg_nosplit"], 1) != (ent["cfg"], ent["split"])), key
+        assert ("heads" in forms) == (taps == 1 and N == 3 * K), key
+        for f in ("geglu", "heads"):
+            if f in forms:
+                assert (forms[f].table_cfg, forms[f].table_split) == (ent["cfg_nosplit"], 1), key
+        assert forms["split"].rowvec == (taps == 9 and stride == 1), key
+        assert forms["split"].gn_groups == (32 if taps == 9 and stride == 1 and N % 32 == 0 else 0), key
+        assert forms["split"].plain == (taps == 9 and hw is None), key
+    for c in cs:
+        assert c.M == c.B * c.Hout * c.Wout and c.K == c.taps * c.Cin and c.B >= 1 and c.form in DC.FORMS, c
+        assert (c.M, c.N, c.K, c.taps, c.stride, c.ups) == DC.parse_key(c.key)[1], c
+        if c.taps == 9:
+            assert (c.Hin, c.Win) == ((c.Hout // 2, c.Wout // 2) if c.ups else (c.Hout * c.stride, c.Wout * c.stride)), c
+            assert not c.ups or (c.Hout % 2 == 0 and c.Wout % 2 == 0), c
+            # the key conv_gemm finds for this geometry is the case's own key (for a plain key: the map really is off the table)
+            assert DC.lookup_key(table, c.M, c.N, c.K, c.taps, c.stride, c.ups, c.Hout, c.Wout) == c.key, c
+            if c.plain:
+                assert f"{c.key}|{c.Hout}x{c.Wout}" not in table, c
+        elif c.form == "heads":
+            assert c.Win == c.Wout == 1 and c.Hin == c.Hout == c.M // c.B and c.B == (1 if c.M % 2 else 2), c
+        else:
+            assert c.Hin == c.Win == c.Hout == c.Wout == 1, c
+
+
+@pytest.mark.parametrize("bad_key,ent", [
+    ("1000,64,576,9,1,0", dict(cfg=5, split=1, cfg_nosplit=5)),            # a plain 3x3 key without a geometry-keyed sibling
+    ("1000,64,576,9,1,0|30x30", dict(cfg=5, split=1, cfg_nosplit=5)),      # rows that are not whole maps
+    ("1024,64,576,9,1,1|31x33", dict(cfg=5, split=1, cfg_nosplit=5)),      # an upsample onto an odd map
+    ("64,64,576,5,1,0", dict(cfg=0, split=1, cfg_nosplit=0)),              # a tap count nobody launches
+    ("64,68,64,1,1,0", dict(cfg=0, split=2, cfg_nosplit=0)),               # cfg_nosplit differs but N % 8 != 0: no GEGLU form reaches it
+])
+def test_dispatch_sweep_cases_refuse_an_entry_they_cannot_launch(bad_key, ent):
+    """a regenerated table with an entry the rules cannot turn into a launch fails with that key in the message, never by dropping it"""
+    from tests import dispatch_cases as DC
+    table = dict(DC.load_table())
+    table[bad_key] = ent
+    import re
+    with pytest.raises(ValueError, match=re.escape(bad_key)):
+        DC.cases(table)
+
+
+@pytest.mark.parametrize("taps,stride,ups,B,Hin,Win,Cin,N", [
+    (1, 1, 0, 1, 1, 1, 24, 10),          # linear
+    (9, 1, 0, 1, 6, 6, 5, 7),            # 3x3 stride 1
+    (9, 2, 0, 1, 8, 8, 4, 6),            # stride 2
+    (9, 1, 1, 1, 4, 4, 3, 5),            # fused nearest 2x upsample
+    (9, 1, 0, 1, 5, 9, 4, 3),            # a non-square map
+    (9, 2, 0, 3, 4, 6, 2, 4), (9, 1, 1, 2, 3, 2, 4, 3),      # B > 1
+])
+def test_dispatch_sweep_reference_is_the_convolution(taps, stride, ups, B, Hin, Win, Cin, N):
+    """the tap-by-tap fp32 reference of tests/test_dispatch_sweep_gpu.py == F.conv2d / F.linear in fp64 (weights [N, tap, Cin] as the kernels read them).
+    rtol 1e-5 on fp32 inputs; the same figure as atol, because sums of up to 45 O(1) products cancel to near zero while their fp32 accumulation
+    error stays near 45 * 2^-24 ~ 3e-6 absolute."""
+    import torch.nn.functional as F
+    from tests.test_dispatch_sweep_gpu import ref_gemm
+    g = torch.Generator().manual_seed(5)
+    if taps == 1:
+        x = torch.randn(37, Cin, generator=g)
+        w = torch.randn(N, Cin, generator=g)
+        got = ref_gemm(x, w, taps=1, stride=1, ups=0, B=37, Hin=1, Win=1, Hout=1, Wout=1, Cin=Cin)
+        ref = F.linear(x.double(), w.double())
+    else:
+        x = torch.randn(B, Hin, Win, Cin, generator=g)
+        w4 = torch.randn(N, Cin, 3, 3, generator=g)
+        w = w4.permute(0, 2, 3, 1).reshape(N, 9 * Cin).contiguous()
+        Hout, Wout = (2 * Hin, 2 * Win) if ups else (Hin // stride, Win // stride)
+        got = ref_gemm(x, w, taps=9, stride=stride, ups=ups, B=B, Hin=Hin, Win=Win, Hout=Hout, Wout=Wout, Cin=Cin)
+        xin = x.double().permute(0, 3, 1, 2)
+        if ups:
+            xin = F.interpolate(xin, scale_factor=2.0, mode="nearest")
+        ref = F.conv2d(xin, w4.double(), stride=stride, padding=1).permute(0, 2, 3, 1).reshape(B * Hout * Wout, N)
+    assert got.dtype == torch.float32 and got.shape == ref.shape
+    assert torch.allclose(got.double(), ref, rtol=1e-5, atol=1e-5), float((got.double() - ref).abs().max())
+
+
 def test_fold_layernorm_affine_is_exact_algebra():
     """LN_affine(x) W^T + b == LN_plain(x) W'^T + b' with (W', b') = ops.fold_layernorm_affine (the host side of the fused
     LayerNorm -> linear launches)"""
