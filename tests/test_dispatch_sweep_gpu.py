@@ -4,7 +4,10 @@ dispatcher reads ``gemm_tuning.json``) and compared over the WHOLE output with a
 Per case (tests/dispatch_cases.py turns the table into cases): which kernel ran (one launch; its (tile config, K slices) against the
 table's choice), values at the bar of tests/test_kernels_gpu.py, GroupNorm statistics where the launch hands them on, a sentinel tail
 behind the output, and a second identical call.  The shapes the table does NOT hold are collected from one denoising step of each
-benchmarked workload (``ops.GEMM_TRACE``) and replayed the same way.  The last test prints the module's summary (``-rA``)."""
+benchmarked workload (``ops.GEMM_TRACE``) and replayed the same way.  The full-width workloads OFF the benchmarked geometries
+(tests/geometry_cases.py) are traced too: there EVERY distinct problem is replayed, table hits included -- a hit from another map is the
+dispatcher's ``*_supported`` back-out path -- and two of them once more with the decision cache kept across problems.  The last test prints
+the module's summary (``-rA``)."""
 import time
 import zlib
 
@@ -13,6 +16,7 @@ import torch
 import torch.nn.functional as F
 
 from tests.dispatch_cases import HEADS, cases, load_table, lookup_key
+from tests.geometry_cases import GEOMETRY_CASES, workload_kwargs
 from tests.test_kernels_gpu import TOL, assert_close
 
 pytestmark = pytest.mark.gpu
@@ -28,6 +32,8 @@ Q_SCALE = 0.3
 
 RECORDS = {}            # (dtype name, case id) -> dict(launched=(cfg, split), tabulated=bool, stats=str)
 MISSES = {}             # workload -> list of untabulated problem descriptions
+REFUSED = []            # launches of a tile config whose *_supported query refuses the problem: (key, cfg, split, query)
+CACHE_KEPT = {}         # workload -> problems replayed with the decision cache kept
 T0 = []
 
 
@@ -74,16 +80,50 @@ def _randn(g, *shape, scale=1.0, dt=torch.float32):
     return (t * scale if scale != 1.0 else t).to(dt)
 
 
-def _launch(ops_mod, kwargs_fn):
-    """One dispatcher call under the event hook, decision cache cleared: (result, [(key, cfg, split), ...] launches)."""
+# the library's own answer to "does this tile config take this problem" (the queries ops.conv_gemm re-checks a table entry with)
+SUPPORT_QUERY = {5: "imd_conv_patch_supported", 21: "imd_conv_patch2_supported", 22: "imd_conv_patch3_supported", 23: "imd_conv_patch4_supported",
+                 24: "imd_conv_img_supported", **{c: "imd_row_linear_supported" for c in (12, 13, 14, 15)},
+                 **{c: "imd_gemm_dma_supported" for c in (16, 17, 19, 25, 27, 30, 31, 32)}}
+
+
+class _QueryingLib:
+    """The loaded library with ``imd_conv_gemm`` preceded by the ``*_supported`` query of the tile config about to run, on the very parameter block."""
+
+    def __init__(self, lib, log):
+        self._lib, self._log = lib, log
+
+    def __getattr__(self, name):
+        return getattr(self._lib, name)
+
+    def imd_conv_gemm(self, pref, cfg, stream):
+        q = SUPPORT_QUERY.get(cfg)
+        p = pref._obj
+        split = p.split_k
+        if q == "imd_gemm_dma_supported" and cfg != 16:     # only the 256 x 256 tile (16) excludes K slices: the library asks on behalf of the other tiles with split_k = 1 (gemm_dma.hip)
+            p.split_k = 1
+        ok = q is None or bool(getattr(self._lib, q)(pref))
+        p.split_k = split
+        if not ok:
+            self._log.append((f"{p.M},{p.N},{p.K},{p.taps},{p.stride},{p.ups}|{p.Hout}x{p.Wout}", cfg, p.split_k, q))
+        return self._lib.imd_conv_gemm(pref, cfg, stream)
+
+
+def _launch(ops_mod, kwargs_fn, keep_cache=False):
+    """One dispatcher call under the event hook, decision cache cleared (or kept): (result, [(key, cfg, split), ...] launches).  A launch the
+    library's own ``*_supported`` query refuses lands in ``REFUSED``."""
     hook = ops_mod.GEMM_EVENT_HOOK
-    ops_mod._CFG_DECISIONS.clear()
+    if not keep_cache:
+        ops_mod._CFG_DECISIONS.clear()
     ops_mod.GEMM_EVENT_HOOK = {}
+    load = ops_mod.L.load
+    proxy = _QueryingLib(load(), REFUSED)
+    ops_mod.L.load = lambda: proxy
     try:
         r = kwargs_fn()
         seen = [k for k, ev in ops_mod.GEMM_EVENT_HOOK.items() for _ in ev]
     finally:
         ops_mod.GEMM_EVENT_HOOK = hook
+        ops_mod.L.load = load
     return r, seen
 
 
@@ -121,11 +161,21 @@ def _act(ops, act, t):
 
 
 def run_problem(ops, dt, tag, *, M, N, Cin, taps, stride, ups, B, Hin, Win, Hout, Wout, bias=True, res=True, res_rows=0, rowvec=False,
-                rowvec_shared=False, act=0, gn_groups=0, heads=None, out_scale=1.0, out_f32=False, pad_br_only=False, x_pix_stride=None):
+                rowvec_shared=False, act=0, gn_groups=0, heads=None, out_scale=1.0, out_f32=False, pad_br_only=False, x_pix_stride=None, keep_cache=False):
     """Seeded operands, one dispatcher launch (cfg=-1, split_k=0), the fp32 reference, and every check but the dispatch assertion: values over the
     whole output, the sentinel behind it, statistics, a second identical call.  ``heads`` = (C, H, D, [(kind, DP, L, scale), ...]).
+    ``keep_cache``: that launch runs with the decisions earlier problems left in ``ops._CFG_DECISIONS``; one more launch with the cache cleared
+    (the cache is put back afterwards) must then run the same (cfg, split) and store the same bits.
     Returns (launches seen by the event hook, kind of statistics found)."""
     from imagdressing_amd import ops as ops_mod
+
+    def cleared(call):
+        kept = dict(ops_mod._CFG_DECISIONS)
+        try:
+            return _launch(ops_mod, call)
+        finally:
+            ops_mod._CFG_DECISIONS.clear()
+            ops_mod._CFG_DECISIONS.update(kept)
     K = taps * Cin
     g = _gen(tag, dt)
     rows_in = B * Hin * Win if taps == 9 else M
@@ -151,7 +201,7 @@ def run_problem(ops, dt, tag, *, M, N, Cin, taps, stride, ups, B, Hin, Win, Hout
             bufs = [torch.zeros((B, H, L, DP) if kind == 0 else (B, H, DP, L), dtype=dt, device=DEV) for kind, DP, L, _ in dests]
             ops.conv_gemm(xk, w, heads=dict(C=Cc, H=H, D=D, dests=[(t, kind, DP, L, sc) for t, (kind, DP, L, sc) in zip(bufs, dests)]), **geo)
             return bufs
-        bufs, seen = _launch(ops_mod, call)
+        bufs, seen = _launch(ops_mod, call, keep_cache)
         ref = base.view(B, HW, len(dests), H, D)
         for j, (t, (kind, DP, L, sc)) in enumerate(zip(bufs, dests)):
             if kind == 0:       # [B, H, L, DP] rows (Q / K)
@@ -162,6 +212,10 @@ def run_problem(ops, dt, tag, *, M, N, Cin, taps, stride, ups, B, Hin, Win, Hout
                 pads = (t[:, :, D:, :], t[:, :, :, HW:])
             assert all(pz.numel() == 0 or float(pz.abs().max()) == 0.0 for pz in pads), f"{what}: dest {j}: the padding around the {HW} x {D} block was written"
         assert all(torch.equal(u, v) for u, v in zip(bufs, call())), f"{what}: second call differs"
+        if keep_cache:
+            bufs_c, seen_c = cleared(call)
+            assert seen_c == seen, f"{what}: {seen} launched with the decision cache kept, {seen_c} with it cleared"
+            assert all(torch.equal(u, v) for u, v in zip(bufs, bufs_c)), f"{what}: the launch with the decision cache kept stored other bits"
         return seen, "none"
     kw = dict(geo, act=act, out_scale=out_scale, out_f32=out_f32)
     ref = base
@@ -184,7 +238,7 @@ def run_problem(ops, dt, tag, *, M, N, Cin, taps, stride, ups, B, Hin, Win, Hout
         buf = torch.full((M + 64, n_out), SENTINEL, dtype=odt, device=DEV)
         out = ops.conv_gemm(xk, w, out=buf[:M], gn_stats_groups=gn_groups, **kw)
         return out, buf
-    (out, buf), seen = _launch(ops_mod, call)
+    (out, buf), seen = _launch(ops_mod, call, keep_cache)
     assert out.data_ptr() == buf.data_ptr() and out.dtype == odt
     assert_close(out, ref, atol=TOL[dt], rtol=TOL[dt], what=what)
     assert bool((buf[M:] == SENTINEL).all()), f"{what}: rows behind the output were written"
@@ -193,6 +247,10 @@ def run_problem(ops, dt, tag, *, M, N, Cin, taps, stride, ups, B, Hin, Win, Hout
         stats = _check_stats(out, B, Hout * Wout, N, seen[0][2] if len(seen) == 1 else 1, what)
     out2, _ = call()
     assert torch.equal(out, out2), f"{what}: second call differs"
+    if keep_cache:
+        (out_c, _), seen_c = cleared(call)
+        assert seen_c == seen, f"{what}: {seen} launched with the decision cache kept, {seen_c} with it cleared"
+        assert torch.equal(out, out_c), f"{what}: the launch with the decision cache kept stored other bits"
     return seen, stats
 
 
@@ -243,7 +301,12 @@ WORKLOADS = {
     "configs[2] batch 8": dict(config=3, batch=8),
     "configs[4] 768x576 batch 4": dict(config=5, batch=4),
 }
+# full width, off the benchmarked geometries (tests/geometry_cases.py): the table was timed on none of these maps
+GEOMETRY_WORKLOADS = {f"configs[1] latent {c.id}": workload_kwargs(c) for c in GEOMETRY_CASES}
+WORKLOADS.update(GEOMETRY_WORKLOADS)
+CACHE_KEPT_WORKLOADS = ("configs[1] latent 24x40 x3", "configs[1] latent 8x8")
 CASE_KEYS = {c.key for c in CASES}
+TRACES = {}             # workload -> (conv_gemm problems, attention launches) of one denoising step; tests/test_geometry_gpu.py replays the attention launches
 
 
 def _configs_module():
@@ -256,19 +319,36 @@ def _configs_module():
     return mod
 
 
-def _trace(ops_mod, config, batch, width=512, height=512, requests=0):
-    """One denoising step of a full-width random-weight pipeline with ``ops.GEMM_TRACE`` on; the pipeline is gone when this returns."""
+def _trace(ops_mod, config, batch, width=512, height=512, requests=0, garment=None):
+    """One denoising step of a full-width random-weight pipeline with ``ops.GEMM_TRACE`` on and ``ops.attention`` recorded (shapes and flags only:
+    ``GEMM_TRACE`` does not see attention launches); the pipeline is gone when this returns.  ``garment`` = (h, w): a garment latent of that size
+    instead of the generation size.  -> (conv_gemm problems, attention launches)"""
     import gc
     dev = torch.device("cuda", 0)
     pipe, kw = _configs_module().build(config, dev, bf16, batch, steps=1, width=width, height=height)
+    if garment is not None:
+        kw["ref_image_latents"] = torch.randn(1, 4, *garment, generator=torch.Generator().manual_seed(78)).to(dev)
     if requests:        # R distinct (garment, prompt, latent, guidance, image scale) requests, as tests/test_multi_request_gpu.py::_Requests builds the call
         g = torch.Generator().manual_seed(77)
         rep = lambda t: (t.repeat(requests, *([1] * (t.dim() - 1))).float().cpu() + 0.1 * torch.randn(requests, *t.shape[1:], generator=g)).to(device=t.device, dtype=t.dtype)      # noqa: E731
         for name in ("prompt_embeds", "negative_prompt_embeds", "ref_clip_hidden_states", "ref_image_latents", "latents"):
             kw[name] = rep(kw[name])
         kw.update(guidance_scale=[5.0, 7.5, 9.0, 6.0][:requests], image_scale=[1.0, 0.6, 1.3, 0.8][:requests], num_images_per_prompt=1)
+    attn = []
+    real_attention = ops_mod.attention
+
+    def recording_attention(q, k1, v1t, out, *, B, H, N, D, L1, L1P, kv1_bdiv=1, k2=None, v2t=None, scale2=None, L2=0, L2P=0, kv2_bdiv=1, out_ld=None,
+                            causal=False, k_pad_one=False, proj=None, out_dup=None, phase2_rows=0):
+        hybrid = k2 is not None and scale2 is not None
+        attn.append(dict(B=B, H=H, N=N, D=D, L1=L1, L1P=L1P, kv1_bdiv=kv1_bdiv, L2=L2 if hybrid else 0, L2P=L2P if hybrid else 0, kv2_bdiv=kv2_bdiv if hybrid else 1,
+                         scale2_rows=tuple(i for i, v in enumerate(scale2.tolist()) if v != 0.0) if hybrid else (), k_pad_one=bool(k_pad_one),
+                         out_dup=out_dup is not None, phase2_rows=int(phase2_rows), causal=bool(causal), proj=proj is not None, out_ld=out_ld,
+                         Bk1=k1.shape[0], Bk2=k2.shape[0] if hybrid else 0, dtype=str(q.dtype)))
+        return real_attention(q, k1, v1t, out, B=B, H=H, N=N, D=D, L1=L1, L1P=L1P, kv1_bdiv=kv1_bdiv, k2=k2, v2t=v2t, scale2=scale2, L2=L2, L2P=L2P,
+                              kv2_bdiv=kv2_bdiv, out_ld=out_ld, causal=causal, k_pad_one=k_pad_one, proj=proj, out_dup=out_dup, phase2_rows=phase2_rows)
     prev = ops_mod.GEMM_TRACE
     ops_mod.GEMM_TRACE = []
+    ops_mod.attention = recording_attention
     try:
         with torch.no_grad():
             pipe(**kw)
@@ -276,11 +356,19 @@ def _trace(ops_mod, config, batch, width=512, height=512, requests=0):
         tr = ops_mod.GEMM_TRACE
     finally:
         ops_mod.GEMM_TRACE = prev
+        ops_mod.attention = real_attention
     del pipe, kw
     gc.collect()
     ops_mod.clear_workspaces()
     torch.cuda.empty_cache()
-    return tr
+    return tr, attn
+
+
+def traced(ops_mod, workload):
+    """The trace of a workload, taken once per session."""
+    if workload not in TRACES:
+        TRACES[workload] = _trace(ops_mod, **WORKLOADS[workload])
+    return TRACES[workload]
 
 
 def _problem_id(t):
@@ -293,42 +381,87 @@ def _problem_id(t):
             + (f" xps {t['x_pix_stride']}" if t["x_pix_stride"] != t["Cin"] else "") + ("" if t["rowvec_stride"] or not t["rowvec"] else " shared rowvec"))
 
 
-@pytest.mark.parametrize("workload", list(WORKLOADS))
-def test_untabulated_problems_of_a_workload(ops, workload):
-    """Every problem one denoising step launches through the dispatcher is either a table entry (then the sweep above has a case for its key)
-    or is replayed standalone in its traced geometry and epilogue: values over the whole output, sentinel, second call."""
-    from imagdressing_amd import ops as ops_mod
-    tr = _trace(ops_mod, **WORKLOADS[workload])
-    assert tr, "the workload launched nothing through ops.conv_gemm"
+def _distinct_problems(tr):
     distinct = {}
     for t in tr:
         if t["gn"]:             # GroupNorm of the input inside the conv: the caller names the kernel, nothing is dispatched (own tests)
             continue
         distinct.setdefault(_problem_id(t), t)
-    hits, misses, failures = 0, [], []
+    return distinct
+
+
+def _replay(ops, workload, pid, t, keep_cache=False):
+    """One traced problem standalone in its traced geometry and epilogue (``run_problem``) -> the launches the event hook saw."""
+    heads = None
+    if t["heads"] is not None:
+        h = t["heads"]
+        assert all(d[0] for d in h["dests"]), f"{pid}: a head-split launch with an absent destination"
+        heads = (h["C"], h["H"], h["D"], [(kind, DP, L, sc) for _, kind, DP, L, sc in h["dests"]])
+    n_out = t["N"] // 2 if t["act"] == ops.ACT_GEGLU else t["N"]
+    assert (heads is not None or t["out_ld"] == n_out) and (not t["res"] or t["res_ld"] == t["N"]), f"{pid}: a strided output or residual, which this replay does not build"
+    seen, _ = run_problem(ops, bf16, f"{workload}: {pid}", M=t["M"], N=t["N"], Cin=t["Cin"], taps=t["taps"], stride=t["stride"], ups=t["ups"],
+                          B=t["M"] // (t["Hout"] * t["Wout"]), Hin=t["Hin"], Win=t["Win"], Hout=t["Hout"], Wout=t["Wout"], bias=t["bias"], res=t["res"],
+                          res_rows=t["res_rows"], rowvec=t["rowvec"], rowvec_shared=t["rowvec_stride"] == 0, act=t["act"], gn_groups=t["gn_stats_groups"],
+                          heads=heads, out_scale=t["out_scale"], out_f32=t["out_f32"], pad_br_only=t["pad_br_only"], x_pix_stride=t["x_pix_stride"],
+                          keep_cache=keep_cache)
+    return seen
+
+
+@pytest.mark.parametrize("workload", list(WORKLOADS))
+def test_untabulated_problems_of_a_workload(ops, workload):
+    """Every problem one denoising step launches through the dispatcher is either a table entry (then the sweep above has a case for its key)
+    or is replayed standalone in its traced geometry and epilogue: values over the whole output, sentinel, second call.
+    The workloads off the benchmarked geometries replay their table hits as well: the sweep above launches an entry on the map it was timed on,
+    here the same key arrives from another map (or another image count), and whatever (cfg, split) runs must be one the library's own
+    ``*_supported`` query accepts for that problem."""
+    tr, _ = traced(ops, workload)
+    assert tr, "the workload launched nothing through ops.conv_gemm"
+    foreign = workload in GEOMETRY_WORKLOADS
+    distinct = _distinct_problems(tr)
+    hits, misses, failures, ran = [], [], [], {}
+    n_refused = len(REFUSED)
     for pid, t in distinct.items():
         key = lookup_key(TABLE, t["M"], t["N"], t["K"], t["taps"], t["stride"], t["ups"], t["Hout"], t["Wout"])
         if key is not None:
             assert key in CASE_KEYS, f"{workload}: table entry {key} is launched by the product but by no case of the sweep"
-            hits += 1
-            continue
-        misses.append(pid)
-        heads = None
-        if t["heads"] is not None:
-            h = t["heads"]
-            assert all(d[0] for d in h["dests"]), f"{pid}: a head-split launch with an absent destination"
-            heads = (h["C"], h["H"], h["D"], [(kind, DP, L, sc) for _, kind, DP, L, sc in h["dests"]])
-        n_out = t["N"] // 2 if t["act"] == ops.ACT_GEGLU else t["N"]
-        assert (heads is not None or t["out_ld"] == n_out) and (not t["res"] or t["res_ld"] == t["N"]), f"{pid}: a strided output or residual, which this replay does not build"
+            hits.append(pid)
+            if not foreign:
+                continue
+        else:
+            misses.append(pid)
         try:
-            run_problem(ops, bf16, f"{workload}: {pid}", M=t["M"], N=t["N"], Cin=t["Cin"], taps=t["taps"], stride=t["stride"], ups=t["ups"],
-                        B=t["M"] // (t["Hout"] * t["Wout"]), Hin=t["Hin"], Win=t["Win"], Hout=t["Hout"], Wout=t["Wout"], bias=t["bias"], res=t["res"],
-                        res_rows=t["res_rows"], rowvec=t["rowvec"], rowvec_shared=t["rowvec_stride"] == 0, act=t["act"], gn_groups=t["gn_stats_groups"],
-                        heads=heads, out_scale=t["out_scale"], out_f32=t["out_f32"], pad_br_only=t["pad_br_only"], x_pix_stride=t["x_pix_stride"])
+            seen = _replay(ops, workload, pid, t)
+            assert len(seen) == 1, f"{workload}: {pid}: expected one launch, the hook saw {seen}"
+            ran[pid] = seen[0][1:]
         except AssertionError as e:
             failures.append(str(e))
-    MISSES[workload] = dict(launches=len(tr), distinct=len(distinct), tabulated=hits, misses=misses)
-    assert not failures, f"{len(failures)} of {len(misses)} untabulated problems of {workload} failed:\n" + "\n".join(failures)
+    MISSES[workload] = dict(launches=len(tr), distinct=len(distinct), tabulated=len(hits), misses=misses, foreign_hits=hits if foreign else [], ran=ran)
+    assert not failures, f"{len(failures)} of {len(ran) + len(failures)} replayed problems of {workload} failed:\n" + "\n".join(failures)
+    assert len(REFUSED) == n_refused, f"{workload}: launched although the tile config's *_supported query refuses the problem: {REFUSED[n_refused:]}"
+
+
+@pytest.mark.parametrize("workload", CACHE_KEPT_WORKLOADS)
+def test_decision_cache_kept_across_the_problems_of_a_workload(ops, workload):
+    """``ops._CFG_DECISIONS`` remembers (cfg, split) per problem description, and that description leaves out ``gn`` / ``gn_in`` / ``gn_out`` /
+    ``gn_stats_groups`` / ``res_rows`` / ``rowvec_stride``; every replay above clears it first.  Here the distinct problems of two workloads run
+    back to back (the second workload finds the first one's decisions) with the cache KEPT: each problem must launch the (cfg, split) it launches with
+    a cleared cache, store the same bits, meet the same value / sentinel / statistics checks, and never run a tile config whose ``*_supported``
+    query refuses it."""
+    from imagdressing_amd import ops as ops_mod
+    if not CACHE_KEPT:
+        ops_mod._CFG_DECISIONS.clear()
+    tr, _ = traced(ops, workload)
+    distinct = _distinct_problems(tr)
+    failures, n_refused, hits_before = [], len(REFUSED), len(ops_mod._CFG_DECISIONS)
+    for pid, t in distinct.items():
+        try:
+            _replay(ops, workload, pid, t, keep_cache=True)
+        except AssertionError as e:
+            failures.append(str(e))
+    CACHE_KEPT[workload] = dict(problems=len(distinct), decisions_before=hits_before, decisions_after=len(ops_mod._CFG_DECISIONS))
+    assert len(ops_mod._CFG_DECISIONS) > hits_before, "the replay left no decision in the cache: it is not exercised"
+    assert not failures, f"{len(failures)} of {len(distinct)} problems of {workload} differ with the decision cache kept:\n" + "\n".join(failures)
+    assert len(REFUSED) == n_refused, f"{workload}: launched although the tile config's *_supported query refuses the problem: {REFUSED[n_refused:]}"
 
 
 def test_zz_summary(ops):
@@ -351,8 +484,19 @@ def test_zz_summary(ops):
             back = [f"{byid[cid].key} -> {recs[cid]['launched']}" for cid in ran if not recs[cid]["tabulated"]]
             lines.append(f"  {name}: {len(ran) - len(back)} ran the tabulated kernel, {len(back)} fell back to the heuristic" + (": " + "; ".join(back) if back else ""))
     for wl, m in MISSES.items():
+        if wl in GEOMETRY_WORKLOADS:
+            lines.append(f"{wl}: {m['launches']} launches, {m['distinct']} distinct problems, {len(m['foreign_hits'])} table hits on a foreign map, {len(m['misses'])} table misses, "
+                         f"{len(m['ran'])} replayed; (cfg, split) per problem:" + "".join(f"\n    {p} -> {m['ran'].get(p)}" + (" [table hit]" if p in m["foreign_hits"] else "")
+                                                                                       for p in m["foreign_hits"] + m["misses"]))
+            continue
         lines.append(f"{wl}: {m['launches']} launches, {m['distinct']} distinct problems, {m['tabulated']} tabulated, {len(m['misses'])} replayed table misses"
                      + ("".join("\n    " + p for p in m["misses"])))
+    for wl, m in CACHE_KEPT.items():
+        lines.append(f"decision cache kept, {wl}: {m['problems']} problems, {m['decisions_before']} -> {m['decisions_after']} remembered decisions")
+    for wl, (_, at) in TRACES.items():
+        if wl in GEOMETRY_WORKLOADS:
+            lines.append(f"{wl}: {len(at)} attention launches, {len({tuple(sorted((k, str(v)) for k, v in a.items())) for a in at})} distinct")
+    lines.append(f"launches of a tile config whose own *_supported query refuses the problem: {len(REFUSED)}" + "".join(f"\n    {r}" for r in REFUSED[:20]))
     lines.append(f"wall time of the module: {time.time() - T0[0]:.0f} s")
     print("\n".join(lines))
     ran = {cid for (d, cid) in RECORDS if d == "bfloat16"}

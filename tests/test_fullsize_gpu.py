@@ -34,50 +34,83 @@ def rnd(seed, *shape, scale=1.0, device="cpu"):
 # full-width UNet forward vs the fp32 CPU oracle
 # ----------------------------------------------------------------------------------------------------------------
 # latent (rows, cols): 512x512 -> 64x64 (BASELINE configs[1]); the reference scripts' own default, width 512 x height 640 with a
-# 640x512 garment (inference_IMAGdressing.py:182-183) -> 80x64, N = M = 5120 / 1280 / 320 / 80
-@pytest.fixture(scope="module", params=[(64, 64), (80, 64)], ids=["512x512", "512x640"])
+# 640x512 garment (inference_IMAGdressing.py:182-183) -> 80x64, N = M = 5120 / 1280 / 320 / 80; then four geometries OFF the tuned table
+# (tests/geometry_cases.py): 8x8 (N = 64 / 16 / 4 / 1), 16x32 (N = 512 exactly), 24x40 (N = 960 / 240 / 60 / 15: odd maps, W % 16 != 0) and
+# 24x24 with a 16x24 garment (N = 576 / 144 / 36 / 9 against M = 384 / 96 / 24 / 6)
+_FULL_ORACLE_PARAMS = [(64, 64, None), (80, 64, None), (8, 8, None), (16, 32, None), (24, 40, None), (24, 24, (16, 24))]
+_FULL_ORACLE_MODEL = {}         # the fp32 oracle with the seeded weights does not depend on the geometry: built once per session (28 s)
+
+
+@pytest.fixture(scope="module", params=_FULL_ORACLE_PARAMS,
+                ids=["512x512", "512x640", "latent8x8", "latent16x32", "latent24x40", "latent24x24-garment16x24"])
 def full_oracle(request):
-    """(state dict, inputs, fp32 oracle output) of ONE full-width SD1.5 UNet forward, batch 1."""
+    """(state dict, inputs, fp32 oracle output) of ONE full-width SD1.5 UNet forward, batch 1; the garment latent has the generation size unless
+    the parameter names another."""
     if not torch.cuda.is_available():
         pytest.skip("needs a GPU")
-    lh, lw = request.param
+    lh, lw, garment = request.param
+    gh, gw = garment or (lh, lw)
     from imagdressing_amd import unet as E
-    from oracle import processors as OP
-    from oracle import sd15
-    sd = E.random_state_dict(E.unet_param_shapes(E.SD15_CONFIG), 0)
-    o = sd15.UNet2DConditionModel({})
-    o.load_state_dict(sd, strict=True)
+    from tests.harness import hidden_size_of, ref_weights
     boc = E.SD15_CONFIG["block_out_channels"]
-    from tests.harness import hidden_size_of
-    o.set_attn_processor({n: (OP.RefSAttn(n, hidden_size_of(n, boc)) if n.endswith("attn1.processor")
-                              else OP.CAttn(n, hidden_size_of(n, boc), 768)) for n in o.attn_processors.keys()})
+    if not _FULL_ORACLE_MODEL:
+        from oracle import processors as OP
+        from oracle import sd15
+        sd = E.random_state_dict(E.unet_param_shapes(E.SD15_CONFIG), 0)
+        o = sd15.UNet2DConditionModel({})
+        o.load_state_dict(sd, strict=True)
+        o.set_attn_processor({n: (OP.RefSAttn(n, hidden_size_of(n, boc)) if n.endswith("attn1.processor")
+                                  else OP.CAttn(n, hidden_size_of(n, boc), 768)) for n in o.attn_processors.keys()})
+        names = [n for n in o.attn_processors.keys() if n.endswith("attn1.processor")]
+        rw = ref_weights(names, boc, 7)         # seeded to_k_ref / to_v_ref
+        with torch.no_grad():
+            for n in names:
+                o.attn_processors[n].to_k_ref.weight.copy_(rw[n]["k"]); o.attn_processors[n].to_v_ref.weight.copy_(rw[n]["v"])
+        _FULL_ORACLE_MODEL.update(sd=sd, o=o, names=names, rw=rw)
+    sd, o, names, rw = (_FULL_ORACLE_MODEL[k] for k in ("sd", "o", "names", "rw"))
     x = rnd(1, 1, 4, lh, lw)
     ehs = rnd(2, 1, 77, 768, scale=0.5)
-    # garment tokens of every attn1 layer ([1, M_l, C_l], M_l = N_l: garment at the generation resolution) and seeded to_k_ref / to_v_ref
-    names = [n for n in o.attn_processors.keys() if n.endswith("attn1.processor")]
-    from tests.harness import ref_weights
-    rw = ref_weights(names, boc, 7)
-    tokens = {320: lh * lw, 640: lh * lw // 4, 1280: lh * lw // 16}
+    # garment tokens of every attn1 layer ([1, M_l, C_l]; M_l = N_l where the garment has the generation resolution)
+    tokens = {320: gh * gw, 640: gh * gw // 4, 1280: gh * gw // 16}
     sa = {}
     for j, n in enumerate(names):
         c = hidden_size_of(n, boc)
-        m = lh * lw // 64 if n.startswith("mid_block") else tokens[c]
+        m = gh * gw // 64 if n.startswith("mid_block") else tokens[c]
         sa[n] = rnd(100 + j, 1, m, c)
-        with torch.no_grad():
-            o.attn_processors[n].to_k_ref.weight.copy_(rw[n]["k"]); o.attn_processors[n].to_v_ref.weight.copy_(rw[n]["v"])
     with torch.no_grad():
         ref = o(x, 481, ehs)
         ref_cond = o(x, 481, ehs, cross_attention_kwargs={"sa_hidden_states": sa})
-    del o
-    return dict(sd=sd, x=x, ehs=ehs, ref=ref, ref_cond=ref_cond, sa=sa, rw=rw)
+    return dict(sd=sd, x=x, ehs=ehs, ref=ref, ref_cond=ref_cond, sa=sa, rw=rw, latent=(lh, lw), garment=(gh, gw))
 
 
 @pytest.mark.parametrize("dtype", [torch.float16, torch.bfloat16], ids=["f16", "bf16"])
 @torch.no_grad()
 def test_full_width_unet_forward_vs_oracle(full_oracle, dtype):
     """859.5 M-parameter UNet, 64x64 latent (BASELINE configs[1]) and 80x64 (the reference scripts' default 512x640): the HIP
-    engine against the fp32 oracle on identical seeded weights.
-    Bars: fp16 rms 0.5 % and worst element 2e-2 x output std; bf16 rms 2.5 % / 0.12 x std (8 mantissa bits)."""
+    engine against the fp32 oracle on identical seeded weights; and the same at four geometries off the tuned table (latents 8x8, 16x32,
+    24x40, 24x24 with a 16x24 garment: tests/geometry_cases.py says which geometry-conditional fast paths each leaves).
+    Bars: fp16 rms 0.5 % and worst element 2e-2 x output std; bf16 rms 2.5 % / 0.12 x std (8 mantissa bits).  The oracle's own sensitivity to
+    16-bit rounding of weights and inputs does not depend on the map size (bf16 rel rms 1e-2, fp16 1.3e-3 from 8x8 to 64x64), so the bars set
+    at 64x64 hold unchanged for the small maps.
+    Where level 0 has N >= 512 tokens the CFG batch runs once more through ``forward_nhwc(cfg_pair=True)`` under the pipeline's
+    ``sa_pair_layout``: the first hybrid block once per image (``Transformer2D.call_pair_half``; really taken: the hook sees the B-row
+    launch) against the same oracle passes at the same bars, and against the same call with ``CFG_PAIR_ATTN`` off at the bars of
+    ``test_full_pipeline_first_hybrid_block_once_per_image_is_bit_identical`` (same arithmetic, other launch geometries).
+    Measured on an MI355X (rel_rms / max_abs over ref_std for the plain, cond and uncond passes; then the rel rms between the once-per-image form
+    and the same call with ``CFG_PAIR_ATTN`` off; the once-per-image passes measure like the cond / uncond ones); each run prints its own:
+      fp16  64x64            1.80e-3 / 7.1e-3   1.80e-3 / 8.0e-3   1.79e-3 / 7.2e-3   on vs off 1.74e-3
+            80x64            1.86e-3 / 9.2e-3   1.81e-3 / 7.7e-3   1.83e-3 / 8.3e-3   on vs off 1.77e-3
+            8x8              1.95e-3 / 6.4e-3   2.03e-3 / 6.9e-3   1.93e-3 / 5.7e-3
+            16x32            1.95e-3 / 7.5e-3   1.95e-3 / 7.0e-3   1.98e-3 / 7.7e-3   on vs off 1.96e-3
+            24x40            1.81e-3 / 7.4e-3   1.79e-3 / 7.2e-3   1.83e-3 / 8.0e-3   on vs off 1.79e-3
+            24x24 (g 16x24)  1.86e-3 / 6.5e-3   1.79e-3 / 6.8e-3   1.88e-3 / 6.9e-3   on vs off 1.77e-3
+      bf16  64x64            1.43e-2 / 6.3e-2   1.40e-2 / 6.1e-2   1.44e-2 / 5.6e-2   on vs off 1.38e-2
+            80x64            1.46e-2 / 6.1e-2   1.44e-2 / 5.8e-2   1.47e-2 / 6.1e-2   on vs off 1.40e-2
+            8x8              1.65e-2 / 5.0e-2   1.58e-2 / 5.9e-2   1.74e-2 / 5.0e-2
+            16x32            1.57e-2 / 5.6e-2   1.53e-2 / 4.9e-2   1.55e-2 / 5.9e-2   on vs off 1.51e-2
+            24x40            1.44e-2 / 6.2e-2   1.43e-2 / 5.8e-2   1.42e-2 / 5.7e-2   on vs off 1.42e-2
+            24x24 (g 16x24)  1.43e-2 / 7.6e-2   1.39e-2 / 5.2e-2   1.43e-2 / 5.8e-2   on vs off 1.43e-2"""
+    from imagdressing_amd import ops
     from imagdressing_amd import unet as E
     from imagdressing_amd.adapter import attention_processor as AP
     from tests.harness import err_stats, hidden_size_of
@@ -88,6 +121,9 @@ def test_full_width_unet_forward_vs_oracle(full_oracle, dtype):
                               else AP.CAttnProcessor2_0(n, hidden_size_of(n, boc), 768)) for n in e.attn_processors.keys()})
     got = e(fo["x"].cuda(), 481, fo["ehs"].cuda())[0]
     st = err_stats(got, fo["ref"])
+    tag = f"latent {fo['latent'][0]}x{fo['latent'][1]} garment {fo['garment'][0]}x{fo['garment'][1]} {str(dtype).split('.')[-1]}"
+    show = lambda name, s: print(f"err_stats {tag} {name}: rel_rms {s['rel_rms']:.3e} max_abs/ref_std {s['max_abs'] / s['ref_std']:.3e}")      # noqa: E731
+    show("plain", st)
     assert torch.isfinite(got).all()
     bar = dict(rel_rms=5e-3, max_rel=2e-2) if dtype == torch.float16 else dict(rel_rms=2.5e-2, max_rel=0.12)
     assert st["rel_rms"] < bar["rel_rms"] and st["max_abs"] < bar["max_rel"] * st["ref_std"], st
@@ -98,14 +134,44 @@ def test_full_width_unet_forward_vs_oracle(full_oracle, dtype):
             p.to_k_ref.weight.copy_(fo["rw"][n]["k"]); p.to_v_ref.weight.copy_(fo["rw"][n]["v"])
     sa = {n: t.cuda() for n, t in fo["sa"].items()}
     x2 = torch.cat([fo["x"], fo["x"]]).cuda()
-    both = e(x2, 481, fo["ehs"].cuda(), cross_attention_kwargs={"sa_hidden_states": sa,
-                                                                  "sa_batch_mask": torch.tensor([1.0, 0.0], device="cuda")})[0]
+    mask = torch.tensor([1.0, 0.0], device="cuda")
+    both = e(x2, 481, fo["ehs"].cuda(), cross_attention_kwargs={"sa_hidden_states": sa, "sa_batch_mask": mask})[0]
     st_c, st_u = err_stats(both[0:1], fo["ref_cond"]), err_stats(both[1:2], fo["ref"])
+    show("cond", st_c); show("uncond", st_u)
     for st2 in (st_c, st_u):
         assert st2["rel_rms"] < bar["rel_rms"] and st2["max_abs"] < bar["max_rel"] * st2["ref_std"], (st_c, st_u)
     # the garment branch matters at this size (the cond and uncond oracle passes differ by 11 % rms, several times the error bar)
     gap = err_stats(fo["ref_cond"], fo["ref"])
     assert gap["rel_rms"] > 3 * bar["rel_rms"] and gap["rel_rms"] > 0.05, gap
+    # ---- the sampling loop's form of the same CFG batch: conv_in, the first resnet and the first hybrid block up to its self-attention once per image
+    lh, lw = fo["latent"]
+    N0, M0 = lh * lw, fo["garment"][0] * fo["garment"][1]
+    if N0 >= 512:
+        cak = {"sa_hidden_states": sa, "sa_batch_mask": mask, "sa_pair_layout": True}
+        xn = E.nchw_to_nhwc8(x2, dtype)
+        ehs = fo["ehs"].to(device="cuda", dtype=dtype).contiguous()
+        seen = []
+
+        def run():
+            seen.clear()
+            ops.ATTN_EVENT_HOOK = {"match": lambda **kw: (seen.append((kw["B"], kw["N"], kw["L2"])) or False), "events": []}
+            try:
+                return e.forward_nhwc(xn, 481, ehs, cak, cfg_pair=True).view(2, lh, lw, 4).permute(0, 3, 1, 2).float()
+            finally:
+                ops.ATTN_EVENT_HOOK = None
+        assert ops.CFG_PAIR_ATTN and ops.CFG_PAIR_DEDUP
+        on = run()
+        assert (1, N0, M0) in seen and (2, N0, M0) in seen, seen       # the de-duplicated first block and the ordinary ones
+        st_pc, st_pu = err_stats(on[0:1], fo["ref_cond"]), err_stats(on[1:2], fo["ref"])
+        show("once-per-image cond", st_pc); show("once-per-image uncond", st_pu)
+        for st2 in (st_pc, st_pu):
+            assert st2["rel_rms"] < bar["rel_rms"] and st2["max_abs"] < bar["max_rel"] * st2["ref_std"], (st_pc, st_pu)
+        ops.CFG_PAIR_ATTN = False       # (the autouse fixture of tests/conftest.py puts it back)
+        off = run()
+        assert (1, N0, M0) not in seen and (2, N0, M0) in seen, seen
+        rel = ((on - off).pow(2).mean().sqrt() / off.pow(2).mean().sqrt()).item()
+        print(f"err_stats {tag} once-per-image on vs off: rel_rms {rel:.3e}")
+        assert torch.isfinite(on).all() and rel < (4e-2 if dtype == torch.bfloat16 else 6e-3), rel
     del e
     torch.cuda.empty_cache()
 

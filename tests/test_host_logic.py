@@ -480,6 +480,52 @@ def test_dispatch_sweep_cases_refuse_an_entry_they_cannot_launch(bad_key, ent):
         DC.cases(table)
 
 
+# what every case of tests/geometry_cases.py contributes: a case that is deleted, renamed or resized fails the test below even where another case
+# still covers its conditions
+GEOMETRY_CASE_CONDITIONS = {
+    "16x16": {"b", "e", "f-short", "h", "k"},
+    "8x8": {"a", "b", "e", "f-short", "g-1x1", "g-odd", "h", "k"},
+    "16x32": {"c-512", "e", "f-short", "h", "k"},
+    "24x40 x3": {"a", "c-ragged", "d", "e", "g-odd", "h", "i"},
+    "24x24 garment 16x24": {"a", "c-ragged", "d", "e", "g-odd", "h", "i", "j"},
+    "32x8": {"b", "e", "f-tall", "g-odd", "h", "k"},
+    "32x32 x5": {"e", "f-short", "h", "k"},
+}
+
+
+def test_geometry_cases_cover_every_off_table_condition():
+    """tests/geometry_cases.py (the plan of the off-table geometry tests): the list as a whole leaves the tuned road on every geometry-conditional
+    branch (``CONDITIONS``), every case is a geometry the UNet can represent, and each case contributes exactly what is written above."""
+    from tests import dispatch_cases as DC
+    from tests import geometry_cases as GC
+    table = DC.load_table()
+    got = {c.id: GC.describe(c, table) for c in GC.GEOMETRY_CASES}
+    assert len(got) == len(GC.GEOMETRY_CASES), "case ids repeat"
+    union = set().union(*(d["conditions"] for d in got.values()))
+    assert union == set(GC.CONDITIONS), f"conditions no case hits: {sorted(set(GC.CONDITIONS) - union)}"
+    assert {i: d["conditions"] for i, d in got.items()} == GEOMETRY_CASE_CONDITIONS
+    tabulated = {(64, 64), (80, 64), (96, 72)}          # 512x512, 512x640, 768x576
+    for c in GC.GEOMETRY_CASES:
+        d = got[c.id]
+        assert (c.h, c.w) not in tabulated and c.h % 8 == 0 and c.w % 8 == 0 and c.images >= 1, c
+        assert [L.channels for L in d["levels"]] == list(E.SD15_CONFIG["block_out_channels"]), c
+        for lv, L in enumerate(d["levels"]):
+            assert (L.H, L.W) == (c.h // 2 ** lv, c.w // 2 ** lv) and L.tokens == L.H * L.W and L.cfg_rows == 2 * c.images * L.tokens, (c, L)
+            assert L.head_dim == (40, 80, 160, 160)[lv] and L.garment_tokens == (L.tokens if c.garment is None else (c.garment[0] >> lv) * (c.garment[1] >> lv)), (c, L)
+        # condition (k) is computed from the shipped table: every collision really is a plain key the dispatcher finds for a problem on that map
+        for key in d["collisions"]:
+            _, (M, N, K, taps, stride, ups), hw = DC.parse_key(key)
+            Ls = [L for L in d["levels"] if L.cfg_rows == M and L.channels in (N, K // taps)]
+            assert hw is None and Ls and all(DC.lookup_key(table, M, N, K, taps, stride, ups, L.H, L.W) == key for L in Ls), (c, key)
+    # the attention shapes the replay must include fall out of the list: query counts, and garment counts against them
+    toks = {L.tokens for d in got.values() for L in d["levels"]}
+    assert {1, 4, 9, 15, 36, 60, 512, 576, 960} <= toks
+    pairs = {(L.garment_tokens, L.tokens) for d in got.values() for L in d["levels"]}
+    assert {(6, 9), (24, 36), (96, 144), (384, 576)} <= pairs
+    with pytest.raises(ValueError):
+        GC.levels(GC.GeoCase("12x16", 12, 16, 1, None))
+
+
 @pytest.mark.parametrize("taps,stride,ups,B,Hin,Win,Cin,N", [
     (1, 1, 0, 1, 1, 1, 24, 10),          # linear
     (9, 1, 0, 1, 6, 6, 5, 7),            # 3x3 stride 1
