@@ -581,29 +581,87 @@ int launch_cfg(const ConvGemmParams& p, hipStream_t s) {
     if (int rc_attr = imd_lds_attr(reinterpret_cast<const void*>(kern), lds, "conv_gemm")) return rc_attr;
     const long mt = (p.M + BM - 1) / BM, nt = (p.N + BN - 1) / BN;
     hipLaunchKernelGGL(kern, dim3((unsigned)(mt * nt), (unsigned)p.split_k), dim3(WM * WN * 64), lds, s, p);
-    int rc = imd_check_launch("conv_gemm");
-    if (rc || p.split_k <= 1 || p.splitk_counters != nullptr) return rc;
-    return launch_splitk_finish(p, s, "conv_gemm split-K finish");
+    return imd_check_launch("conv_gemm");
 }
 
+// the register-staged tile kernel (this file) in both element types
+template <int BM, int BN, int BK, int WM, int WN, int DEPTH = 2>
+int launch_tile(const ConvGemmParams& p, hipStream_t s) {
+    return p.dtype == IMD_DTYPE_F16 ? launch_cfg<true, BM, BN, BK, WM, WN, DEPTH>(p, s) : launch_cfg<false, BM, BN, BK, WM, WN, DEPTH>(p, s);
+}
+
+// ------------------------------------------------------------------------------------------
+// THE tile-config table: everything the host code knows about a config number (public: gemm_tuning.json, include/imagdressing_hip.h), one
+// row per number.  The Python side keeps its own table of how a tabulated entry is re-validated (ops.py: TILE_SUPPORT).
+// ------------------------------------------------------------------------------------------
+enum StatsEpilogue { ST_NONE, ST_TILE, ST_PATCH, ST_PATCH3_W4, ST_PATCH3_W8 };     // GroupNorm statistics of the output from the un-split epilogue (K slices: the finish launch writes them, for every config)
+
+struct TileConfig {
+    int bm, bn;                 // output tile, rows x columns (0: the row-resident kernels -- no grid of tiles; sizing heuristics then assume 128 x 128)
+    int order_bk;               // Cin granularity at which a 3x3 conv may take the tap-inner K order (flags bit 0)
+    int (*launch)(const ConvGemmParams&, hipStream_t);
+    const char* finish;         // label of the finish launch of its K slices
+    bool finish_always;         // K slices always end with the shared finish launch; false: splitk_counters survives (the in-kernel sum of the register-staged tiles and
+                                // of config 5 -- the row-resident kernels and config 16 take no K slices at all)
+    int taps;                   // 1 | 9: takes only that (0: both)
+    bool slices_only;           // writes K-slice slabs only (split_k >= 2)
+    StatsEpilogue stats;
+};
+
+#define IMD_L(call) [](const ConvGemmParams& p, hipStream_t s) -> int { return call; }
+const char F_TILE[] = "conv_gemm split-K finish", F_PATCH[] = "conv_patch split-K finish", F_DMA128[] = "gemm_dma128 split-K finish", F_DMA256[] = "gemm_dma256 split-K finish";
+const TileConfig TILE_CONFIGS[] = {
+    /*  0 */ {128, 128, 64, launch_tile<128, 128, 64, 2, 2>, F_TILE, false, 0, false, ST_TILE},
+    /*  1 */ {128, 64, 64, launch_tile<128, 64, 64, 2, 2>, F_TILE, false, 0, false, ST_TILE},
+    /*  2 */ {64, 64, 64, launch_tile<64, 64, 64, 2, 2>, F_TILE, false, 0, false, ST_TILE},
+    /*  3 */ {64, 64, 64, launch_tile<64, 64, 64, 2, 2, 4>, F_TILE, false, 0, false, ST_TILE},            // 4 tiles in flight
+    /*  4 */ {128, 128, 32, launch_tile<128, 128, 32, 2, 2>, F_TILE, false, 0, false, ST_TILE},           // 41 KB LDS: 3 workgroups / CU
+    /*  5 */ {128, 128, 64, imd_launch_conv_patch, F_PATCH, false, 0, false, ST_PATCH},                   // LDS-resident halo patch (conv_patch.hip): 3x3 stride-1 only, optional fused GroupNorm prologue
+    /*  6 */ {64, 320, 64, launch_tile<64, 320, 32, 2, 2>, F_TILE, false, 0, false, ST_NONE},             // N % 320 == 0: no idle columns, A read once
+    /*  7 */ {64, 64, 64, launch_tile<64, 64, 32, 2, 2, 4>, F_TILE, false, 0, false, ST_TILE},            // 20 KB LDS: 8 workgroups / CU
+    /*  8 */ {128, 128, 64, launch_tile<128, 128, 32, 2, 2, 4>, F_TILE, false, 0, false, ST_NONE},
+    /*  9 */ {256, 128, 64, launch_tile<256, 128, 32, 4, 2>, F_TILE, false, 0, false, ST_NONE},           // 8 waves: operand bytes per MFMA -25 %
+    /* 10 */ {256, 256, 64, launch_tile<256, 256, 32, 4, 2>, F_TILE, false, 0, false, ST_NONE},           // 8 waves, 64x128 per wave: -50 %
+    /* 11 */ {128, 320, 64, launch_tile<128, 320, 64, 4, 2>, F_TILE, false, 0, false, ST_NONE},           // N = 320 k: one full-width row block per CU
+    /* 12 */ {0, 0, 64, IMD_L(imd_launch_row_linear(p, 0, 0.f, s)), F_TILE, false, 0, false, ST_NONE},         // row-resident kernel (row_linear.hip): K = 320, N <= 320
+    /* 13 */ {0, 0, 64, IMD_L(imd_launch_row_linear_k640(p, 0, 0.f, s)), F_TILE, false, 0, false, ST_NONE},    // row-resident split-K kernel (row_linear_k640.hip): K = 640, N % 160 == 0
+    /* 14 */ {0, 0, 64, IMD_L(imd_launch_row_linear_k1280(p, 0, 0.f, s)), F_TILE, false, 0, false, ST_NONE},   // row-resident 4-way split-K kernel (row_linear_k1280.hip): K = 1280, N % 160 == 0
+    /* 15 */ {0, 0, 64, IMD_L(imd_launch_row_qkv(p, 0, 0.f, s)), F_TILE, false, 0, false, ST_NONE},            // row-resident q/k/v projection of a 320-channel block (row_qkv.hip)
+    /* 16 */ {256, 256, 64, imd_launch_gemm_dma, F_TILE, false, 0, false, ST_NONE},                       // 256 x 256 x 64 LDS-DMA tile kernel for the large linears (gemm_dma.hip)
+    // 128 x 128 x 32 LDS-DMA tiles (gemm_dma.hip): 17 / 18 three-stage ring, 3 workgroups / CU; 19 / 20 four stages, 2 / CU; 17, 19: plain linears, 18, 20: 3x3 convs gathered per tile
+    /* 17 */ {128, 128, 64, IMD_L(imd_launch_gemm_dma128(p, 3, 32, s)), F_DMA128, true, 1, false, ST_NONE},
+    /* 18 */ {128, 128, 64, IMD_L(imd_launch_gemm_dma128(p, 3, 32, s)), F_DMA128, true, 9, false, ST_NONE},
+    /* 19 */ {128, 128, 64, IMD_L(imd_launch_gemm_dma128(p, 4, 32, s)), F_DMA128, true, 1, false, ST_NONE},
+    /* 20 */ {128, 128, 64, IMD_L(imd_launch_gemm_dma128(p, 4, 32, s)), F_DMA128, true, 9, false, ST_NONE},
+    /* 21 */ {256, 128, 64, imd_launch_conv_patch2, "conv_patch2 split-K finish", true, 0, false, ST_NONE},      // halo patch, 16 x 16 pixel tiles (conv_patch2.hip)
+    // halo patch x 160 channels (conv_patch3.hip): 22 = 8 x 16 pixels, four waves; 23 = 16 x 16 pixels, eight waves (one weight tile per 256 pixels)
+    /* 22 */ {128, 160, 64, imd_launch_conv_patch3, "conv_patch3 split-K finish", true, 0, false, ST_PATCH3_W4},
+    /* 23 */ {256, 160, 64, imd_launch_conv_patch4, "conv_patch3 split-K finish", true, 0, false, ST_PATCH3_W8},
+    /* 24 */ {512, 64, 64, imd_launch_conv_img, "conv_img split-K finish", true, 0, true, ST_NONE},       // whole small maps (8 pixels wide) x 64 channels x one K slice per workgroup (conv_img.hip): every weight byte fetched once
+    // the 128 x 128 LDS-DMA tiles with 128-BYTE rows (BK = 64): 25 / 27 plain linears with two / three stages, 26 / 28 3x3 convs
+    /* 25 */ {128, 128, 64, IMD_L(imd_launch_gemm_dma128(p, 2, 64, s)), F_DMA128, true, 1, false, ST_NONE},
+    /* 26 */ {128, 128, 64, IMD_L(imd_launch_gemm_dma128(p, 2, 64, s)), F_DMA128, true, 9, false, ST_NONE},
+    /* 27 */ {128, 128, 64, IMD_L(imd_launch_gemm_dma128(p, 3, 64, s)), F_DMA128, true, 1, false, ST_NONE},
+    /* 28 */ {128, 128, 64, IMD_L(imd_launch_gemm_dma128(p, 3, 64, s)), F_DMA128, true, 9, false, ST_NONE},
+    /* 29 */ {128, 128, 64, imd_launch_conv_patch64, F_PATCH, true, 0, false, ST_PATCH},                  // the halo-patch kernel with 64-channel chunks: 128-byte rows, i.e. whole L2 lines (conv_patch.hip)
+    // LDS-DMA tiles with producer / consumer waves and a register epilogue (gemm_dma256.hip): 30 = 256 x 128 x 64, three stages, persistent over (tile, K slice)
+    // items; 31 = the same with one item per workgroup; 32 (round 6) = 192 x 128 x 64, persistent
+    /* 30 */ {256, 128, 64, IMD_L(imd_launch_gemm_dma256(p, 0, s)), F_DMA256, true, 0, false, ST_NONE},
+    /* 31 */ {256, 128, 64, IMD_L(imd_launch_gemm_dma256(p, 1, s)), F_DMA256, true, 0, false, ST_NONE},
+    /* 32 */ {192, 128, 64, IMD_L(imd_launch_gemm_dma256(p, 2, s)), F_DMA256, true, 0, false, ST_NONE},
+};
+#undef IMD_L
+
+const TileConfig* tile_config(int cfg) {
+    return cfg >= 0 && cfg < (int)(sizeof(TILE_CONFIGS) / sizeof(TILE_CONFIGS[0])) ? &TILE_CONFIGS[cfg] : nullptr;
+}
+
+// tile of `cfg` into (bm, bn); 1, (bm, bn) untouched, where the config has no grid of tiles
 int tile_dims(int cfg, int* bm, int* bn) {
-    switch (cfg) {
-        case 0: *bm = 128; *bn = 128; return 0;
-        case 1: *bm = 128; *bn = 64; return 0;
-        case 2: *bm = 64; *bn = 64; return 0;
-        case 4: case 5: case 8: case 29: *bm = 128; *bn = 128; return 0;
-        case 3: case 7: *bm = 64; *bn = 64; return 0;
-        case 6: *bm = 64; *bn = 320; return 0;
-        case 9: case 21: case 30: case 31: *bm = 256; *bn = 128; return 0;
-        case 32: *bm = 192; *bn = 128; return 0;
-        case 22: *bm = 128; *bn = 160; return 0;
-        case 23: *bm = 256; *bn = 160; return 0;
-        case 24: *bm = 512; *bn = 64; return 0;
-        case 10: case 16: *bm = 256; *bn = 256; return 0;
-        case 17: case 18: case 19: case 20: case 25: case 26: case 27: case 28: *bm = 128; *bn = 128; return 0;
-        case 11: *bm = 128; *bn = 320; return 0;
-        default: return 1;
-    }
+    const TileConfig* t = tile_config(cfg);
+    if (t == nullptr || t->bm == 0) return 1;
+    *bm = t->bm, *bn = t->bn;
+    return 0;
 }
 
 }  // namespace
@@ -627,21 +685,22 @@ int imd_conv_gemm_stats_parts_of(const ConvGemmParams& p_in, int cfg) {
     ConvGemmParams p = p_in;
     if (p.split_k < 1) p.split_k = 1;
     if (cfg < 0) cfg = imd_conv_gemm_choose_cfg(p.M, p.N);       // (as the launcher resolves it)
+    const TileConfig* t = tile_config(cfg);
     if (p.split_k > 1) {
-        if (cfg == 21 || cfg == 22 || cfg == 23 || cfg == 24 || cfg == 29 || (cfg >= 17 && cfg <= 20) || (cfg >= 25 && cfg <= 28) || (cfg >= 30 && cfg <= 32)) p.splitk_counters = nullptr;      // (these always finish with the second launch)
+        if (t != nullptr && t->finish_always) p.splitk_counters = nullptr;
         return splitk_stats_parts_of(p);
     }
-    if (cfg == 22 || cfg == 23) return imd_conv_patch3_stats_parts_of(p, cfg == 23 ? 8 : 4);
-    if (cfg == 5 || cfg == 29) return imd_conv_patch_stats_parts_of(p);
-    // the register-staged tiles whose epilogue threads keep their column block (conv_gemm_kernel's statistics epilogue): whole tiles of one image only
-    if (cfg == 0 || cfg == 1 || cfg == 2 || cfg == 3 || cfg == 4 || cfg == 7) {
-        int bm = 0, bn = 0;
-        tile_dims(cfg, &bm, &bn);
-        const int HW = p.Hout * p.Wout, G = p.gn_stats_groups;
-        if (p.out_f32 || p.mode != OUT_ROWMAJOR || p.act == ACT_GEGLU || G <= 0 || G > 64 || p.N % G || (p.N / G) < 8 || (p.N % 4) || HW <= 0 || HW % bm || p.M % HW) return 0;
-        return (HW / bm) * ((p.N + bn - 1) / bn);
+    switch (t != nullptr ? t->stats : ST_NONE) {
+        case ST_PATCH3_W4: return imd_conv_patch3_stats_parts_of(p, 4);
+        case ST_PATCH3_W8: return imd_conv_patch3_stats_parts_of(p, 8);
+        case ST_PATCH: return imd_conv_patch_stats_parts_of(p);
+        case ST_TILE: {     // the register-staged tiles whose epilogue threads keep their column block (conv_gemm_kernel's statistics epilogue): whole tiles of one image only
+            const int HW = p.Hout * p.Wout, G = p.gn_stats_groups;
+            if (p.out_f32 || p.mode != OUT_ROWMAJOR || p.act == ACT_GEGLU || G <= 0 || G > 64 || p.N % G || (p.N / G) < 8 || (p.N % 4) || HW <= 0 || HW % t->bm || p.M % HW) return 0;
+            return (HW / t->bm) * ((p.N + t->bn - 1) / t->bn);
+        }
+        default: return 0;
     }
-    return 0;
 }
 
 // can tile config `cfg` normalise its input rows as p.gn_in_* asks (the row-resident projections only)?
@@ -719,14 +778,12 @@ int imd_launch_conv_gemm(const ConvGemmParams& p_in, int cfg, hipStream_t s) {
     if (tag != 0 && tag != (unsigned)IMD_TUNING_PER_CALL)
         return imd_set_error("conv_gemm: flags = 0x%x on entry is neither 0 nor IMD_TUNING_PER_CALL | bits (an uninitialised parameter block?)", (unsigned)p_in.flags);
     const int gf = (tag == (unsigned)IMD_TUNING_PER_CALL) ? ((p_in.flags & 31) | (g_gemm_flags & ~31)) : g_gemm_flags;
-    {
-        const int bk = (cfg == 4) ? 32 : 64;
-        p.flags = 0;
-        // measured (profiles/r1g_gemm_flags_ab.jsonl): +8..17 % on the 64x64 / 32x32 feature maps, -2..4 % on 16x16 / 8x8
-        const bool big_map = p.taps == 9 && p.Wout >= 32;
-        if ((gf & 1) && big_map && (p.Cin % bk) == 0) p.flags |= 1;
-        if ((gf & 2) && big_map) p.flags |= 2;
-    }
+    const TileConfig* t = tile_config(cfg);         // (nullptr: refused below, behind the checks of the problem itself)
+    p.flags = 0;
+    // measured (profiles/r1g_gemm_flags_ab.jsonl): +8..17 % on the 64x64 / 32x32 feature maps, -2..4 % on 16x16 / 8x8
+    const bool big_map = p.taps == 9 && p.Wout >= 32;
+    if ((gf & 1) && big_map && (p.Cin % (t != nullptr ? t->order_bk : 64)) == 0) p.flags |= 1;
+    if ((gf & 2) && big_map) p.flags |= 2;
     if (gf & 4) {
         int bm = 128, bn = 128;
         tile_dims(cfg, &bm, &bn);
@@ -736,7 +793,8 @@ int imd_launch_conv_gemm(const ConvGemmParams& p_in, int cfg, hipStream_t s) {
 #ifdef IMD_ABLATIONS
     p.flags |= gf & 224;       // bits 5..7: timing ablations of gemm_dma256.hip (A/B only; WRONG results when set; imd_set_tuning refuses them otherwise)
 #endif
-    if (p.split_k <= 1) p.splitk_counters = nullptr;
+    // the ONE place the arrival counters are dropped: no K slices, or a family that always ends them with the shared finish launch
+    if (p.split_k <= 1 || (t != nullptr && t->finish_always)) p.splitk_counters = nullptr;
     // GroupNorm statistics of the output (ABI v6+): the halo-patch kernels' un-split epilogues (tile configs 5 / 22 / 23 / 29) and the finish
     // launch of any K-sliced problem produce them (imd_conv_gemm_stats_parts_of); every other request is an
     // ERROR -- a launch that silently skipped the write would leave the next imd_groupnorm(nparts > 0) reading uninitialised memory, and
@@ -754,9 +812,9 @@ int imd_launch_conv_gemm(const ConvGemmParams& p_in, int cfg, hipStream_t s) {
     if (p.gn_out_gamma != nullptr) p.splitk_counters = nullptr;
     if (p.splitk_counters != nullptr) {          // one counter per output tile; larger grids keep the two-launch path
         int bm = 128, bn = 128;
-        if (cfg == 5) { bm = 128; bn = 128; } else tile_dims(cfg, &bm, &bn);
-        const long tiles = (cfg == 5) ? (long)(p.M / (p.Hout * p.Wout)) * ((p.Hout + 7) / 8) * ((p.Wout + 15) / 16) * ((p.N + 127) / 128)
-                                      : (long)((p.M + bm - 1) / bm) * ((p.N + bn - 1) / bn);
+        tile_dims(cfg, &bm, &bn);
+        const long tiles = (t != nullptr && t->stats == ST_PATCH) ? (long)(p.M / (p.Hout * p.Wout)) * ((p.Hout + 7) / 8) * ((p.Wout + 15) / 16) * ((p.N + 127) / 128)   // (8 x 16 pixel patches)
+                                                                  : (long)((p.M + bm - 1) / bm) * ((p.N + bn - 1) / bn);
         if (tiles > IMD_SPLITK_COUNTERS || (size_t)p.M * p.N * 4 >= 0x80000000ull) p.splitk_counters = nullptr;
     }
     if (p.split_k > 1) {
@@ -771,76 +829,10 @@ int imd_launch_conv_gemm(const ConvGemmParams& p_in, int cfg, hipStream_t s) {
     if (p.gn_in_partial != nullptr && !imd_row_linear_gn_in_supported_of(p, cfg))
         return imd_set_error("conv_gemm: gn_in_* (GroupNorm of the input rows) exists in the row-resident projections only (tile configs 12 / 13 / 14 with H W a multiple of "
                              "their row block; got cfg=%d K=%d HW=%d): ask imd_row_linear_gn_in_supported() first", cfg, p.K, p.Hout * p.Wout);
-    const bool h = p.dtype == IMD_DTYPE_F16;
-    switch (cfg) {
-        case 0: return h ? launch_cfg<true, 128, 128, 64, 2, 2>(p, s) : launch_cfg<false, 128, 128, 64, 2, 2>(p, s);
-        case 1: return h ? launch_cfg<true, 128, 64, 64, 2, 2>(p, s) : launch_cfg<false, 128, 64, 64, 2, 2>(p, s);
-        case 2: return h ? launch_cfg<true, 64, 64, 64, 2, 2>(p, s) : launch_cfg<false, 64, 64, 64, 2, 2>(p, s);
-        case 3: return h ? launch_cfg<true, 64, 64, 64, 2, 2, 4>(p, s) : launch_cfg<false, 64, 64, 64, 2, 2, 4>(p, s);       // 4 tiles in flight
-        case 4: return h ? launch_cfg<true, 128, 128, 32, 2, 2>(p, s) : launch_cfg<false, 128, 128, 32, 2, 2>(p, s);         // 41 KB LDS: 3 workgroups / CU
-        case 6: return h ? launch_cfg<true, 64, 320, 32, 2, 2>(p, s) : launch_cfg<false, 64, 320, 32, 2, 2>(p, s);               // N % 320 == 0: no idle columns, A read once
-        case 7: return h ? launch_cfg<true, 64, 64, 32, 2, 2, 4>(p, s) : launch_cfg<false, 64, 64, 32, 2, 2, 4>(p, s);       // 20 KB LDS: 8 workgroups / CU
-        case 8: return h ? launch_cfg<true, 128, 128, 32, 2, 2, 4>(p, s) : launch_cfg<false, 128, 128, 32, 2, 2, 4>(p, s);
-        case 9: return h ? launch_cfg<true, 256, 128, 32, 4, 2>(p, s) : launch_cfg<false, 256, 128, 32, 4, 2>(p, s);             // 8 waves: operand bytes per MFMA -25 %
-        case 10: return h ? launch_cfg<true, 256, 256, 32, 4, 2>(p, s) : launch_cfg<false, 256, 256, 32, 4, 2>(p, s);            // 8 waves, 64x128 per wave: -50 %
-        case 11: return h ? launch_cfg<true, 128, 320, 64, 4, 2>(p, s) : launch_cfg<false, 128, 320, 64, 4, 2>(p, s);            // N = 320 k: one full-width row block per CU
-        case 5: {   // LDS-resident halo patch (conv_patch.hip): 3x3 stride-1 only, optional fused GroupNorm prologue
-            int rc = imd_launch_conv_patch(p, s);
-            if (rc || p.split_k <= 1 || p.splitk_counters != nullptr) return rc;
-            return launch_splitk_finish(p, s, "conv_patch split-K finish");
-        }
-        case 29: {  // the halo-patch kernel with 64-channel chunks: 128-byte rows, i.e. whole L2 lines (conv_patch.hip)
-            p.splitk_counters = nullptr;
-            int rc = imd_launch_conv_patch64(p, s);
-            if (rc || p.split_k <= 1) return rc;
-            return launch_splitk_finish(p, s, "conv_patch split-K finish");
-        }
-        case 21: {  // halo patch, 16 x 16 pixel tiles (conv_patch2.hip)
-            p.splitk_counters = nullptr;
-            int rc = imd_launch_conv_patch2(p, s);
-            if (rc || p.split_k <= 1) return rc;
-            return launch_splitk_finish(p, s, "conv_patch2 split-K finish");
-        }
-        case 22: case 23: {  // halo patch x 160 channels (conv_patch3.hip): 22 = 8 x 16 pixels, four waves; 23 = 16 x 16 pixels, eight waves (one weight tile per 256 pixels)
-            int rc = cfg == 22 ? imd_launch_conv_patch3(p, s) : imd_launch_conv_patch4(p, s);
-            if (rc || p.split_k <= 1) return rc;
-            p.splitk_counters = nullptr;
-            return launch_splitk_finish(p, s, "conv_patch3 split-K finish");
-        }
-        case 25: case 26: case 27: case 28: {   // the 128 x 128 LDS-DMA tiles with 128-BYTE rows (BK = 64): 25 / 27 plain linears with two / three stages, 26 / 28 3x3 convs
-            if ((cfg == 26 || cfg == 28) != (p.taps == 9)) return imd_set_error("conv_gemm: tile config %d does not take taps = %d", cfg, p.taps);
-            p.splitk_counters = nullptr;
-            int rc = imd_launch_gemm_dma128(p, cfg >= 27 ? 13 : 12, s);
-            if (rc || p.split_k <= 1) return rc;
-            return launch_splitk_finish(p, s, "gemm_dma128 split-K finish");
-        }
-        case 24: {  // whole small maps (8 pixels wide) x 64 channels x one K slice per workgroup (conv_img.hip): every weight byte fetched once
-            p.splitk_counters = nullptr;
-            if (p.split_k <= 1) return imd_set_error("conv_gemm: tile config 24 writes K-slice slabs only (split_k >= 2)");
-            int rc = imd_launch_conv_img(p, s);
-            if (rc) return rc;
-            return launch_splitk_finish(p, s, "conv_img split-K finish");
-        }
-        case 30: case 31: case 32: {   // LDS-DMA tiles with producer / consumer waves and a register epilogue (gemm_dma256.hip): 30 = 256 x 128 x 64, three stages,
-                              // persistent over (tile, K slice) items; 31 = the same with one item per workgroup; 32 (round 6) = 192 x 128 x 64, persistent
-            p.splitk_counters = nullptr;
-            int rc = imd_launch_gemm_dma256(p, cfg - 30, s);
-            if (rc || p.split_k <= 1) return rc;
-            return launch_splitk_finish(p, s, "gemm_dma256 split-K finish");
-        }
-        case 12: return imd_launch_row_linear(p, 0, 0.f, s);      // row-resident kernel (row_linear.hip): K = 320, N <= 320
-        case 13: return imd_launch_row_linear_k640(p, 0, 0.f, s); // row-resident split-K kernel (row_linear_k640.hip): K = 640, N % 160 == 0
-        case 14: return imd_launch_row_linear_k1280(p, 0, 0.f, s); // row-resident 4-way split-K kernel (row_linear_k1280.hip): K = 1280, N % 160 == 0
-        case 16: return imd_launch_gemm_dma(p, s);                 // 256 x 256 x 64 LDS-DMA tile kernel for the large linears (gemm_dma.hip)
-        case 15: return imd_launch_row_qkv(p, 0, 0.f, s);          // row-resident q/k/v projection of a 320-channel block (row_qkv.hip)
-        case 17: case 18: case 19: case 20: {   // 128 x 128 x 32 LDS-DMA tiles (gemm_dma.hip): 17 / 18 three-stage ring, 3 workgroups / CU; 19 / 20 four stages, 2 / CU;
-                                                // 17, 19: plain linears, 18, 20: 3x3 convs gathered per tile; K slices finish like the tiled kernels'
-            if ((cfg == 18 || cfg == 20) != (p.taps == 9)) return imd_set_error("conv_gemm: tile config %d does not take taps = %d", cfg, p.taps);
-            p.splitk_counters = nullptr;
-            int rc = imd_launch_gemm_dma128(p, cfg >= 19 ? 4 : 3, s);
-            if (rc || p.split_k <= 1) return rc;
-            return launch_splitk_finish(p, s, "gemm_dma128 split-K finish");
-        }
-        default: return imd_set_error("conv_gemm: unknown tile config %d", cfg);
-    }
+    if (t == nullptr) return imd_set_error("conv_gemm: unknown tile config %d", cfg);
+    if (t->taps != 0 && t->taps != p.taps) return imd_set_error("conv_gemm: tile config %d does not take taps = %d", cfg, p.taps);
+    if (t->slices_only && p.split_k <= 1) return imd_set_error("conv_gemm: tile config %d writes K-slice slabs only (split_k >= 2)", cfg);
+    const int rc = t->launch(p, s);
+    if (rc || p.split_k <= 1 || p.splitk_counters != nullptr) return rc;
+    return launch_splitk_finish(p, s, t->finish);
 }

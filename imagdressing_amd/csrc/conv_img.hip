@@ -263,9 +263,7 @@ bool imd_conv_img_supported(const ConvGemmParams& p) {
            (p.M % (p.Hout * p.Wout)) == 0;
 }
 
-int imd_launch_conv_img(const ConvGemmParams& p_in, hipStream_t s) {
-    ConvGemmParams p = p_in;
-    p.splitk_counters = nullptr;            // (the K slices always finish with the shared second launch)
+int imd_launch_conv_img(const ConvGemmParams& p, hipStream_t s) {
     if (!imd_conv_img_supported(p))
         return imd_set_error("conv_img: unsupported problem (needs 3x3 stride 1 on a map 8 wide and <= 12 high, Cin %% 32 == 0, N %% 64 == 0, "
                              "row-major 16-bit output, split_k >= 2 with a workspace, operands < 2 GiB)");

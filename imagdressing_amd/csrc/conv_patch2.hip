@@ -222,7 +222,6 @@ int imd_launch_conv_patch2(const ConvGemmParams& p_in, hipStream_t s) {
     if (!imd_conv_patch2_supported(p_in))
         return imd_set_error("conv_patch2: unsupported geometry (needs 3x3 stride 1, H >= 16, W >= 16, Cin %% 32 == 0, no fused GroupNorm prologue)");
     ConvGemmParams p = p_in;
-    p.splitk_counters = nullptr;               // K slices are summed by the shared finish launch
     p.gn_stats_out = nullptr;
     const bool h = p.dtype == IMD_DTYPE_F16;
     typedef void (*kern_t)(const ConvGemmParams);

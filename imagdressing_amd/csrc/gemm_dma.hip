@@ -360,27 +360,27 @@ static int launch_dma128(const ConvGemmParams& p, hipStream_t s, const char* wha
     const bool h = p.dtype == IMD_DTYPE_F16;
     typedef void (*kern_t)(const ConvGemmParams);
     const kern_t kern = h ? gemm_dma128_kernel<true, GATHER, NST, BK> : gemm_dma128_kernel<false, GATHER, NST, BK>;
-    if (int rc_attr = imd_lds_attr(reinterpret_cast<const void*>(kern), LDS, "%s")) return rc_attr;
+    if (int rc_attr = imd_lds_attr(reinterpret_cast<const void*>(kern), LDS, what)) return rc_attr;
     const long mt = (p.M + G1_BM - 1) / G1_BM, nt = (p.N + G1_BN - 1) / G1_BN;
     hipLaunchKernelGGL(kern, dim3((unsigned)(mt * nt), (unsigned)p.split_k), dim3(256), LDS, s, p);
     return imd_check_launch(what);
 }
 
-// tile configs 17 / 19 (plain linears, three / four ring stages) and 18 / 20 (3x3 convs, likewise); K slices allowed
-int imd_launch_gemm_dma128(const ConvGemmParams& p_in, int stages, hipStream_t s) {
-    ConvGemmParams p = p_in;
-    p.splitk_counters = nullptr;               // (the in-kernel reduction lives in the register-staged kernels only)
-    if (stages == 12 || stages == 13) {       // 128-byte rows (BK = 64): two | three ring stages
+// tile configs 17 / 19 / 25 / 27 (plain linears) and 18 / 20 / 26 / 28 (3x3 convs): a ring of `stages` K chunks of `bk` elements -- three | four of 32 (64-byte rows),
+// two | three of 64 (128-byte rows); K slices allowed, always finished by the caller's second launch (p.splitk_counters arrives null)
+int imd_launch_gemm_dma128(const ConvGemmParams& p, int stages, int bk, hipStream_t s) {
+    if (!((bk == 32 && (stages == 3 || stages == 4)) || (bk == 64 && (stages == 2 || stages == 3))))
+        return imd_set_error("gemm_dma128: %d ring stages of %d-element K chunks (3 | 4 of 32, 2 | 3 of 64)", stages, bk);
+    if (bk == 64) {
         if (p.taps == 9) {
             if (!imd_conv_dma_supported(p) || (p.Cin % 64)) return imd_set_error("conv_dma (128-byte rows): needs a 3x3 convolution with Cin %% 64 == 0 (got Cin=%d stride=%d)", p.Cin, p.stride);
-            return stages == 12 ? launch_dma128<true, 2, 64>(p, s, "conv_dma128 (BK 64)") : launch_dma128<true, 3, 64>(p, s, "conv_dma128 (BK 64, 3 stages)");
+            return stages == 2 ? launch_dma128<true, 2, 64>(p, s, "conv_dma128 (BK 64)") : launch_dma128<true, 3, 64>(p, s, "conv_dma128 (BK 64, 3 stages)");
         }
         ConvGemmParams p1 = p;
         p1.split_k = 1;
         if (!imd_gemm_dma_supported(p1)) return imd_set_error("gemm_dma128: needs a plain linear layer with K %% 64 == 0 (got K=%d taps=%d)", p.K, p.taps);
-        return stages == 12 ? launch_dma128<false, 2, 64>(p, s, "gemm_dma128 (BK 64)") : launch_dma128<false, 3, 64>(p, s, "gemm_dma128 (BK 64, 3 stages)");
+        return stages == 2 ? launch_dma128<false, 2, 64>(p, s, "gemm_dma128 (BK 64)") : launch_dma128<false, 3, 64>(p, s, "gemm_dma128 (BK 64, 3 stages)");
     }
-    if (stages != 3 && stages != 4) return imd_set_error("gemm_dma128: %d ring stages (3 | 4)", stages);
     if (p.taps == 9) {
         if (!imd_conv_dma_supported(p)) return imd_set_error("conv_dma: needs a 3x3 convolution with Cin %% 32 == 0 (got Cin=%d stride=%d)", p.Cin, p.stride);
         return stages == 3 ? launch_dma128<true, 3>(p, s, "conv_dma128") : launch_dma128<true, 4>(p, s, "conv_dma128 (4 stages)");

@@ -439,9 +439,7 @@ int launch_dma256(const ConvGemmParams& p, bool persistent, hipStream_t s, const
 // tile configs 30 (256 x 128 x 64, three stages, persistent), 31 (the same, one item per workgroup) and 32 (192 x 128 x 64, persistent: round 6, for
 // tile counts that strand CUs at 256 rows); K slices go to fp32 slabs and finish with the tiled kernels' second launch.  (A 256 x 256 x 64 two-stage form behind the same template -- tile config 32 of the first draft -- was slower on every
 // feed-forward shape, 88-107 us against 55-97, profiles/r5b_gemm256_bench.jsonl: one stage of lead is not enough; it is not built.)
-int imd_launch_gemm_dma256(const ConvGemmParams& p_in, int form, hipStream_t s) {
-    ConvGemmParams p = p_in;
-    p.splitk_counters = nullptr;
+int imd_launch_gemm_dma256(const ConvGemmParams& p, int form, hipStream_t s) {
     ConvGemmParams p1 = p;
     p1.split_k = 1;
     if (!imd_gemm_dma_supported(p1)) return imd_set_error("gemm_dma256: needs a plain linear layer with K %% 64 == 0 (got K=%d taps=%d)", p.K, p.taps);

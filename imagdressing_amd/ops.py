@@ -256,57 +256,45 @@ def _gemm_table() -> dict:
     return _GEMM_TABLE
 
 
-def conv_gemm(
-    x: torch.Tensor, w: torch.Tensor, *, M: int, N: int, Cin: int, taps: int = 1,
-    Hin: int = 1, Win: int = 1, Hout: int = 1, Wout: int = 1, stride: int = 1, ups: bool = False,
-    x_pix_stride: Optional[int] = None, out: Optional[torch.Tensor] = None, out_ld: Optional[int] = None,
-    bias: Optional[torch.Tensor] = None, rowvec: Optional[torch.Tensor] = None, rowvec_stride: int = 0,
-    rowvec_off: int = 0, res: Optional[torch.Tensor] = None, res_ld: Optional[int] = None, out_scale: float = 1.0,
-    act: int = ACT_NONE, out_f32: bool = False,
-    heads: Optional[dict] = None, cfg: int = -1, split_k: int = 0,
-    gn: Optional[tuple] = None, pad_br_only: bool = False, ln_eps: Optional[float] = None, gn_stats_groups: int = 0,
-    gn_out: Optional[tuple] = None, gn_in: Optional[tuple] = None,
-) -> Optional[torch.Tensor]:
-    """out[M, N] = epilogue(A(M, K) @ w[N, K]^T); see include/imagdressing_hip.h::imd_conv_gemm.
+# ---- tile configs on the dispatcher's side (what a config number IS -- tile, launcher, K-slice finish, statistics epilogue -- is the library's table,
+# csrc/conv_gemm.hip::TILE_CONFIGS): how a tabulated entry is re-validated, and which configs the fusions below may use -------------------------------
+def _conv_dma_ok(bk: int):      # Python copy of gemm_dma.hip::imd_conv_dma_supported (not exported): 3x3 convs gathered per tile, ``bk`` channels at a time
+    return lambda p: p.taps == 9 and p.Cin % bk == 0 and p.stride in (1, 2) and not p.gn_a
 
-    ``heads`` = dict(C=, H=, D=, dests=[(tensor|None, kind, DP, L, scale), ...]) selects the head-split
-    epilogue (no ``out``).  Returns the output tensor (allocated when ``out`` is None).
-    ``gn`` = (coef_a [B, Cin] fp32, coef_b [B, Cin] fp32, silu) from :func:`group_norm_coeffs` fuses GroupNorm(+SiLU)
-    of the input into the 3x3 halo-patch kernel (tile config 5).
-    ``ln_eps``: LayerNorm WITHOUT affine over the K channels of every row of ``x`` is applied on the fly (row-resident kernel,
-    K = 320 and N <= 320 only; fold gamma / beta into ``w`` / ``bias`` with :func:`fold_layernorm_affine`).
-    ``gn_stats_groups`` = G: when the launch lands on the halo-patch kernel without K slices, or is K-sliced with a separate finish launch,
-    ``gn_in`` = (gamma, beta, eps, silu, groups): GroupNorm (+ SiLU) of the INPUT ``x`` [B, HW, K] of a plain linear layer.  Where the layer runs on a
-    row-resident projection kernel (tile configs 12 / 13 / 14) and ``x`` carries its producer's statistics (``_imd_gn_stats``) the normalisation happens inside
-    that launch (``imd_conv_gemm_params.gn_in_*``: bit-identical, no normalised tensor in memory); everywhere else :func:`group_norm` runs first.
-    ``gn_out`` = (gamma, beta, eps, silu, groups): where the problem is K-sliced with a separate finish launch and that launch can own whole
-    (image, group) slabs (``imd_conv_gemm_gn_out_supported``: the 16x16 / 8x8 levels), the finish launch applies GroupNorm (+ SiLU) to its output
-    itself; the returned tensor then carries ``_imd_gn_applied = True`` and holds the NORMALISED values.  Ignored (raw output) everywhere else.
-    the epilogue / the finish launch also writes the GroupNorm(G) statistics of the OUTPUT (per-tile / per-pixel-part fp32 partials); they ride on the returned tensor (``_imd_gn_stats``) and the next
-    :func:`group_norm` of that tensor skips its statistics pass.  Silently not produced on every other path (FUSED_GN_STATS = False: never).
-    """
-    ensure_device(x.device)
-    K = taps * Cin
+
+ROW_RESIDENT_CFGS = (12, 13, 14)            # the row-resident projections (K = 320 / 640 / 1280): the ones with a gn_in prologue
+# tile config -> the library query (or predicate over the parameter block) a tabulated entry must pass: the table is keyed by (M, N, K, taps, stride, ups)
+# only, and another geometry with the same key (W % 16 != 0, pad_br_only, strided pixels ...) may not qualify; the register-staged tiles take anything
+TILE_SUPPORT = {5: "imd_conv_patch_supported", 21: "imd_conv_patch2_supported", 22: "imd_conv_patch3_supported", 23: "imd_conv_patch4_supported",
+                24: "imd_conv_img_supported", **{c: "imd_row_linear_supported" for c in ROW_RESIDENT_CFGS + (15,)},
+                **{c: "imd_gemm_dma_supported" for c in (16, 17, 19, 25, 27, 30, 31, 32)},
+                18: _conv_dma_ok(32), 20: _conv_dma_ok(32), 26: _conv_dma_ok(64), 28: _conv_dma_ok(64)}
+SLICES_ONLY_CFGS = frozenset({24})          # whole-map kernel of the 8-wide levels: K-sliced only, so its query is asked with the tabulated K slices in the block
+PATCH_CFG = 5                               # the halo-patch kernel: the road of untabulated 3x3 stride-1 convs on wide maps, and the one with the ``gn`` prologue
+PERIODIC_RES_CFGS = frozenset({12})         # read a periodic residual in place (res_rows)
+STATS_EPILOGUE_CFGS = frozenset({5, 22, 23, 29})            # halo-patch kernels: un-split epilogues that write the GroupNorm statistics of their output
+TILE_STATS_CFGS = frozenset({-1, 0, 1, 2, 3, 4, 7})         # register-staged tiles that do (GENERIC_GN_STATS); -1: the library heuristic picks among them
+
+
+def _marshal(x, w, M, N, K, Cin, taps, Hin, Win, Hout, Wout, stride, ups, x_pix_stride, out, out_ld, bias, rowvec, rowvec_stride, rowvec_off, res, res_ld,
+             out_scale, act, out_f32, heads, pad_br_only):
+    """-> (the parameter block of the problem, tile choice and fusions still open; the output tensor; rows of a periodic residual or 0)."""
     p = L.ConvGemmParams()
     p.flags = _gemm_call_flags()
     dt = x.dtype
-    p.dtype = _code(x, "x")
-    p.x = _dev(x, dt, "x")
-    p.w = _dev(w, dt, "w")
+    p.dtype, p.x, p.w = _code(x, "x"), _dev(x, dt, "x"), _dev(w, dt, "w")
     if w.numel() != N * K:
         raise L.ImdError(f"conv_gemm: weight has {w.numel()} elements, expected N*K = {N}*{K}")
     p.M, p.N, p.K = M, N, K
     p.Cin, p.taps, p.Hin, p.Win, p.Hout, p.Wout, p.stride, p.ups = Cin, taps, Hin, Win, Hout, Wout, stride, int(ups)
     p.x_pix_stride = Cin if x_pix_stride is None else x_pix_stride
-    p.bias = _opt(bias, torch.float32, "bias")
-    p.rowvec = _opt(rowvec, torch.float32, "rowvec")
+    p.bias = None if bias is None else _dev(bias, torch.float32, "bias")
+    p.rowvec = None if rowvec is None else _dev(rowvec, torch.float32, "rowvec")
     if rowvec is not None and rowvec_off:
         if rowvec_off % 4:
             raise L.ImdError("conv_gemm: rowvec_off must be a multiple of 4")
         p.rowvec = p.rowvec + 4 * rowvec_off
-    p.rowvec_stride = rowvec_stride
-    p.res = _opt(res, dt, "res")
-    p.res_ld = (N if res_ld is None else res_ld)
+    p.rowvec_stride, p.res, p.res_ld = rowvec_stride, None if res is None else _dev(res, dt, "res"), N if res_ld is None else res_ld
     # a residual with FEWER rows than the output is periodic (row m adds res[m % rows]): one copy of a tensor that is the same for both halves of a
     # CFG batch.  The K = 320 row-resident projection reads it in place (res_rows); everywhere else it is repeated into a full-size tensor first.
     res_rows = 0
@@ -314,18 +302,14 @@ def conv_gemm(
         res_rows = res.numel() // N
         if res_rows <= 0 or res_rows * N != res.numel() or M % res_rows:
             raise L.ImdError(f"conv_gemm: the residual has {res.numel()} elements: neither M x N = {M} x {N} nor a whole divisor of it")
-    p.out_scale = out_scale
-    p.pad_br_only = int(pad_br_only)
-    p.act = act
-    p.out_f32 = int(out_f32)
+    p.out_scale, p.pad_br_only, p.act, p.out_f32 = out_scale, int(pad_br_only), act, int(out_f32)
     if heads is not None:
         p.mode = 1
         p.hC, p.hH, p.hD = heads["C"], heads["H"], heads["D"]
         for i, (t, kind, DP, Ltok, scale) in enumerate(heads["dests"]):
             p.hd[i].ptr = None if t is None else _dev(t, dt, f"heads[{i}]")
             p.hd[i].kind, p.hd[i].DP, p.hd[i].L, p.hd[i].scale = kind, DP, Ltok, scale
-        p.out = None
-        p.out_ld = 0
+        p.out, p.out_ld = None, 0
     else:
         p.mode = 0
         n_out = N // 2 if act == ACT_GEGLU else N
@@ -333,26 +317,132 @@ def conv_gemm(
             out = torch.empty((M, n_out), dtype=torch.float32 if out_f32 else dt, device=x.device)
         p.out = _dev(out, torch.float32 if out_f32 else dt, "out")
         p.out_ld = n_out if out_ld is None else out_ld
+    return p, out, res_rows
+
+
+def _choose_tile(p, lib, cfg: int, split_k: int, splittable: bool) -> Tuple[int, int]:
+    """(tile config, K slices) where the caller left them open (-1 / 0): the tuning table, re-validated through TILE_SUPPORT, else the halo-patch kernel or
+    the library heuristic (-1); the library's K-slice count.  Reads the parameter block and the table only, no tensors: conv_gemm remembers the answer."""
+    if cfg == -1 and split_k == 0:
+        # 3x3 convs are keyed WITH their output map as well: the same (M, N, K) occurs for different maps (2 images of 20x16 and 8 of 10x8 are both 640 rows)
+        key = f"{p.M},{p.N},{p.K},{p.taps},{p.stride},{p.ups}"
+        ent = (_gemm_table().get(f"{key}|{p.Hout}x{p.Wout}") if p.taps == 9 else None) or _gemm_table().get(key)
+        if ent is not None:
+            cfg, split_k = (ent["cfg"], ent["split"]) if splittable else (ent["cfg_nosplit"], 1)
+            ok = TILE_SUPPORT.get(cfg)
+            if cfg in SLICES_ONLY_CFGS:
+                p.split_k = split_k
+            if ok is not None and not (getattr(lib, ok)(C.byref(p)) if isinstance(ok, str) else ok(p)):
+                cfg, split_k = -1, 0        # back to the library heuristic
+    # off the measured table 3x3 stride-1 convs on wide maps go to the halo-patch kernel (always ahead of the gather kernel there: profiles/r1k_patch_conv_ab.jsonl)
+    if PATCH_CONV and cfg == -1 and p.taps == 9 and p.stride == 1 and p.Wout >= PATCH_MIN_W and p.N >= 64 and lib.imd_conv_patch_supported(C.byref(p)):
+        cfg = PATCH_CFG
+    if split_k == 0:        # auto: K slices only where the tile grid cannot fill the chip
+        split_k = 1 if not splittable else lib.imd_conv_gemm_auto_split(p.M, p.N, p.K, cfg)
+    return cfg, split_k
+
+
+def _periodic_residual(p, res, res_rows: int, in_place: bool):       # -> the residual the launch reads (the caller keeps it alive)
+    if in_place and res_rows % 128 == 0 and PERIODIC_RES:
+        p.res_rows = res_rows
+        return res
+    res = repeat_batch(res.reshape(res_rows, p.N), p.M // res_rows)
+    p.res = _dev(res, res.dtype, "res")
+    return res
+
+
+def _fuse_gn_in(p, lib, x, gn_in, cfg: int, M: int, HW: int):
+    """``gn_in`` = (gamma, beta, eps, silu, groups), Transformer2DModel.norm -> proj_in: where the layer runs on a row-resident projection kernel and ``x`` carries
+    its producer's statistics (``_imd_gn_stats``) the normalisation happens inside that launch (``imd_conv_gemm_params.gn_in_*``: bit-identical, no normalised
+    tensor in memory); everywhere else :func:`group_norm` runs first.  -> the normalised tensor ``p.x`` then points to (the caller keeps it alive), or None."""
+    gamma, beta, eps, silu, groups = gn_in
+    st = getattr(x, "_imd_gn_stats", None)
+    if FUSED_GN_PROJ and cfg in FUSED_GN_PROJ_CFGS and st is not None and st[2] == groups and FUSED_GN_STATS and st[0].shape[0] * HW == M:
+        p.gn_in_partial, p.gn_in_nparts, p.gn_in_groups = st[0].data_ptr(), st[1], int(groups)
+        p.gn_in_gamma, p.gn_in_beta = _dev(gamma, torch.float32, "gn_in gamma"), _dev(beta, torch.float32, "gn_in beta")
+        p.gn_in_eps, p.gn_in_silu = float(eps), int(bool(silu))
+        if lib.imd_row_linear_gn_in_supported(C.byref(p), cfg):
+            return None
+        p.gn_in_partial, p.gn_in_nparts, p.gn_in_groups = None, 0, 0
+    xv = x.view(M // HW, HW, p.Cin)
+    if st is not None:
+        xv._imd_gn_stats = st
+    xn = group_norm(xv, gamma, beta, groups=groups, eps=eps, silu=silu)
+    p.x = _dev(xn, x.dtype, "x")
+    return xn
+
+
+def _fuse_gn_out(p, lib, gn_out, out_scale: float) -> bool:
+    """``gn_out`` = (gamma, beta, eps, silu, groups), ResnetBlock2D: conv1 -> norm2 -> SiLU: where the problem is K-sliced with a separate finish launch that can own whole
+    (image, group) slabs (``imd_conv_gemm_gn_out_supported``: the 16x16 / 8x8 levels) it normalises its output itself: gn_out_* filled in and True.  Else the block as it was, False."""
+    gamma, beta, eps, silu, groups = gn_out
+    if not (p.split_k > 1 and p.mode == 0 and not p.out_f32 and p.act == ACT_NONE and not p.res and out_scale == 1.0):
+        return False
+    p.gn_out_gamma, p.gn_out_beta = _dev(gamma, torch.float32, "gn_out gamma"), _dev(beta, torch.float32, "gn_out beta")
+    p.gn_out_eps, p.gn_out_silu, p.gn_out_groups = float(eps), int(bool(silu)), int(groups)
+    if lib.imd_conv_gemm_gn_out_supported(C.byref(p)):
+        p.splitk_counters = None
+        return True
+    p.gn_out_gamma, p.gn_out_beta, p.gn_out_groups = None, None, 0
+    return False
+
+
+def _attach_stats(p, lib, cfg: int, split_k: int, groups: int, images: int, device):
+    """GroupNorm(``groups``) statistics of the OUTPUT as per-tile / per-pixel-part fp32 partials: from the epilogue (halo-patch kernels un-split; with
+    GENERIC_GN_STATS the register-staged tiles -- conv_in, the stride-2 downsampler of the 64x64 level -- wherever a tile's rows lie in one image) or from
+    the finish launch of the K slices (row-major 16-bit outputs).  gn_stats_* filled in -> (partials [images, nparts, groups, 2], nparts, groups), or None where this launch cannot."""
+    if not (cfg in STATS_EPILOGUE_CFGS or split_k > 1 or (GENERIC_GN_STATS and cfg in TILE_STATS_CFGS)):
+        return None
+    p.gn_stats_groups = groups
+    nparts = lib.imd_conv_gemm_stats_parts(C.byref(p), cfg)
+    if nparts <= 0:
+        p.gn_stats_groups = 0
+        return None
+    part = torch.empty((images, nparts, groups, 2), dtype=torch.float32, device=device)
+    p.gn_stats_out = part.data_ptr()
+    return part, nparts, groups
+
+
+def conv_gemm(
+    x: torch.Tensor, w: torch.Tensor, *, M: int, N: int, Cin: int, taps: int = 1,
+    Hin: int = 1, Win: int = 1, Hout: int = 1, Wout: int = 1, stride: int = 1, ups: bool = False,
+    x_pix_stride: Optional[int] = None, out: Optional[torch.Tensor] = None, out_ld: Optional[int] = None,
+    bias: Optional[torch.Tensor] = None, rowvec: Optional[torch.Tensor] = None, rowvec_stride: int = 0,
+    rowvec_off: int = 0, res: Optional[torch.Tensor] = None, res_ld: Optional[int] = None, out_scale: float = 1.0,
+    act: int = ACT_NONE, out_f32: bool = False, heads: Optional[dict] = None, cfg: int = -1, split_k: int = 0,
+    gn: Optional[tuple] = None, pad_br_only: bool = False, ln_eps: Optional[float] = None, gn_stats_groups: int = 0,
+    gn_out: Optional[tuple] = None, gn_in: Optional[tuple] = None,
+) -> Optional[torch.Tensor]:
+    """out[M, N] = epilogue(A(M, K) @ w[N, K]^T); see include/imagdressing_hip.h::imd_conv_gemm.
+
+    ``heads`` = dict(C=, H=, D=, dests=[(tensor|None, kind, DP, L, scale), ...]) selects the head-split epilogue (no ``out``).  Returns the output tensor (allocated when ``out`` is None).
+    ``gn`` = (coef_a [B, Cin] fp32, coef_b [B, Cin] fp32, silu) from :func:`group_norm_coeffs` fuses GroupNorm(+SiLU) of the input into the 3x3 halo-patch kernel (tile config 5).
+    ``ln_eps``: LayerNorm WITHOUT affine over the K channels of every row of ``x`` is applied on the fly (row-resident kernel, K = 320 and N <= 320 only; fold gamma / beta into ``w`` / ``bias`` with :func:`fold_layernorm_affine`).
+    ``gn_in``: GroupNorm (+ SiLU) of the INPUT ``x`` [B, HW, K] of a plain linear layer, inside the launch where it can be (:func:`_fuse_gn_in`).
+    ``gn_out``: GroupNorm (+ SiLU) of the OUTPUT inside the finish launch of the K slices where that exists (:func:`_fuse_gn_out`); the returned tensor then
+    carries ``_imd_gn_applied = True`` and holds the NORMALISED values.  Ignored (raw output) everywhere else.
+    ``gn_stats_groups`` = G: where the launch can (:func:`_attach_stats`) it also writes the GroupNorm(G) statistics of the OUTPUT; they ride on the returned tensor
+    (``_imd_gn_stats``) and the next :func:`group_norm` of that tensor skips its statistics pass.  Silently not produced on every other path (FUSED_GN_STATS = False: never).
+    """
+    ensure_device(x.device)
+    K = taps * Cin
+    p, out, res_rows = _marshal(x, w, M, N, K, Cin, taps, Hin, Win, Hout, Wout, stride, ups, x_pix_stride, out, out_ld, bias, rowvec, rowvec_stride, rowvec_off,
+                                res, res_ld, out_scale, act, out_f32, heads, pad_br_only)
     _count("gemm_conv", 2.0 * M * N * K)
     lib = L.load()
     if gn is not None:
         p.gn_a, p.gn_b, p.gn_silu = _dev(gn[0], torch.float32, "gn_a"), _dev(gn[1], torch.float32, "gn_b"), int(gn[2])
         if cfg == -1:
-            cfg = 5
+            cfg = PATCH_CFG
     if ln_eps is not None:
         if res_rows:
-            if K == 320 and res_rows % 128 == 0 and PERIODIC_RES:
-                p.res_rows = res_rows
-            else:
-                res = repeat_batch(res.reshape(res_rows, N), M // res_rows)
-                p.res = _dev(res, dt, "res")
+            res = _periodic_residual(p, res, res_rows, K == 320)
         p.split_k = 1
         L.check(lib.imd_row_linear(C.byref(p), 1, float(ln_eps), _stream()))
         return out
     splittable = heads is None and act != ACT_GEGLU
     if GEMM_TRACE is not None:
-        GEMM_TRACE.append(dict(M=M, N=N, K=K, Cin=Cin, taps=taps, Hin=Hin, Win=Win, Hout=Hout, Wout=Wout, stride=stride,
-                               ups=int(ups), splittable=splittable, dtype=str(dt),
+        GEMM_TRACE.append(dict(M=M, N=N, K=K, Cin=Cin, taps=taps, Hin=Hin, Win=Win, Hout=Hout, Wout=Wout, stride=stride, ups=int(ups), splittable=splittable, dtype=str(x.dtype),
                                # the epilogue, so that a traced problem can be replayed standalone (tests/test_dispatch_sweep_gpu.py)
                                bias=bias is not None, rowvec=rowvec is not None, rowvec_stride=rowvec_stride, res=res is not None, res_rows=res_rows, act=act, out_f32=bool(out_f32),
                                heads=None if heads is None else dict(C=heads["C"], H=heads["H"], D=heads["D"],
@@ -362,111 +452,30 @@ def conv_gemm(
     # (round 6) the (tile config, K slices) decision of a call site is a pure function of the problem description: remembered per description, so
     # that a repeated layer pays neither the table key formatting nor the library's *_supported queries again (~5 of the ~75 us a processor call
     # costs on the host at the small levels).  Dropped with the tuning table (IMD_GEMM_TUNING / _GEMM_TABLE reset) and by clear_workspaces().
-    dkey = None
+    dkey = hit = None
     if cfg == -1 and split_k == 0 and GEMM_TRACE is None:
         hk = None if heads is None else (heads["C"], heads["H"], heads["D"], tuple((t is None, kind, DP, Ltok) for t, kind, DP, Ltok, _ in heads["dests"]))
         dkey = (M, N, K, Cin, taps, stride, int(ups), Hin, Win, Hout, Wout, p.x_pix_stride, p.res_ld, p.out_ld, act, int(out_f32), int(pad_br_only), p.dtype,
                 rowvec is None, res is None, bias is None, hk, PATCH_CONV, id(_GEMM_TABLE))
         hit = _CFG_DECISIONS.get(dkey)
-        if hit is not None:
-            cfg, split_k = hit
-    if cfg == -1 and split_k == 0:
-        # 3x3 convs are keyed WITH their output map as well (round 3): the same (M, N, K) occurs for different maps -- 2 images of
-        # 20x16 and 8 images of 10x8 are both 640 rows -- and the halo-patch kernel only takes maps at least 16 wide
-        key = f"{M},{N},{K},{taps},{stride},{int(ups)}"
-        ent = (_gemm_table().get(f"{key}|{Hout}x{Wout}") if taps == 9 else None) or _gemm_table().get(key)
-        if ent is not None:
-            if splittable:
-                cfg, split_k = ent["cfg"], ent["split"]
-            else:
-                cfg, split_k = ent["cfg_nosplit"], 1
-            # the table is keyed by (M, N, K, taps, stride, ups) only: another geometry with the same key (W % 16 != 0,
-            # pad_br_only, strided pixels ...) may not qualify for the halo-patch kernel -> back to the library heuristic
-            if cfg == 5 and not lib.imd_conv_patch_supported(C.byref(p)):
-                cfg, split_k = -1, 0
-            if cfg in (12, 13, 14, 15) and not lib.imd_row_linear_supported(C.byref(p)):
-                cfg, split_k = -1, 0
-            if cfg in (16, 17, 19, 25, 27, 30, 31, 32) and not lib.imd_gemm_dma_supported(C.byref(p)):
-                cfg, split_k = -1, 0
-            if (cfg in (18, 20) and (taps != 9 or Cin % 32 or stride not in (1, 2) or gn is not None)) or \
-                    (cfg in (26, 28) and (taps != 9 or Cin % 64 or stride not in (1, 2) or gn is not None)):
-                cfg, split_k = -1, 0
-            if cfg == 21 and not lib.imd_conv_patch2_supported(C.byref(p)):
-                cfg, split_k = -1, 0
-            if cfg == 22 and not lib.imd_conv_patch3_supported(C.byref(p)):
-                cfg, split_k = -1, 0
-            if cfg == 23 and not lib.imd_conv_patch4_supported(C.byref(p)):
-                cfg, split_k = -1, 0
-            if cfg == 24:                       # whole-map kernel of the 8-wide levels: K-sliced only
-                p.split_k = split_k
-                if not lib.imd_conv_img_supported(C.byref(p)):
-                    cfg, split_k = -1, 0
-    # shapes outside the measured table: 3x3 stride-1 convs on wide maps go to the halo-patch kernel (always ahead of the
-    # gather kernel there: profiles/r1k_patch_conv_ab.jsonl)
-    if PATCH_CONV and cfg == -1 and taps == 9 and stride == 1 and Wout >= PATCH_MIN_W and N >= 64 \
-            and lib.imd_conv_patch_supported(C.byref(p)):
-        cfg = 5
-    if split_k == 0:        # auto: K slices only where the tile grid cannot fill the chip
-        split_k = 1 if not splittable else lib.imd_conv_gemm_auto_split(M, N, K, cfg)
-    if dkey is not None and len(_CFG_DECISIONS) < 4096:
+    cfg, split_k = hit or _choose_tile(p, lib, cfg, split_k, splittable)
+    if hit is None and dkey is not None and len(_CFG_DECISIONS) < 4096:
         _CFG_DECISIONS[dkey] = (cfg, split_k)
     if res_rows:
-        if cfg == 12 and res_rows % 128 == 0 and PERIODIC_RES:
-            p.res_rows = res_rows
-        else:
-            res = repeat_batch(res.reshape(res_rows, N), M // res_rows)
-            p.res = _dev(res, dt, "res")
+        res = _periodic_residual(p, res, res_rows, cfg in PERIODIC_RES_CFGS)
     p.split_k = split_k
-    if gn_in is not None:
-        # Transformer2DModel.norm -> proj_in: inside the projection launch where that launch is a row-resident kernel and x came with its statistics
-        gi_gamma, gi_beta, gi_eps, gi_silu, gi_groups = gn_in
-        st = getattr(x, "_imd_gn_stats", None)
-        fused = False
-        if FUSED_GN_PROJ and cfg in FUSED_GN_PROJ_CFGS and st is not None and st[2] == gi_groups and FUSED_GN_STATS and st[0].shape[0] * Hout * Wout == M:
-            p.gn_in_partial, p.gn_in_nparts, p.gn_in_groups = st[0].data_ptr(), st[1], int(gi_groups)
-            p.gn_in_gamma, p.gn_in_beta = _dev(gi_gamma, torch.float32, "gn_in gamma"), _dev(gi_beta, torch.float32, "gn_in beta")
-            p.gn_in_eps, p.gn_in_silu = float(gi_eps), int(bool(gi_silu))
-            fused = bool(lib.imd_row_linear_gn_in_supported(C.byref(p), cfg))
-            if not fused:
-                p.gn_in_partial = None
-                p.gn_in_nparts = p.gn_in_groups = 0
-        if not fused:
-            xv = x.view(M // (Hout * Wout), Hout * Wout, Cin)
-            if st is not None:
-                xv._imd_gn_stats = st
-            xn = group_norm(xv, gi_gamma, gi_beta, groups=gi_groups, eps=gi_eps, silu=gi_silu)
-            p.x = _dev(xn, dt, "x")
+    xn = None if gn_in is None else _fuse_gn_in(p, lib, x, gn_in, cfg, M, Hout * Wout)      # noqa: F841  (kept alive until the launch is issued)
     if split_k > 1:
         p.splitk_ws = splitk_workspace(split_k * M * N, x.device).data_ptr()
         if SPLITK_IN_KERNEL:
             p.splitk_counters = splitk_counters(x.device).data_ptr()
-    if gn_out is not None and FUSED_GN_FINISH and split_k > 1 and heads is None and not out_f32 and act == ACT_NONE and res is None and out_scale == 1.0:
-        # GroupNorm (+ SiLU) of the OUTPUT inside the finish launch of the K slices (ResnetBlock2D: conv1 -> norm2 -> SiLU): the caller finds
-        # `_imd_gn_applied` on the returned tensor and skips its own group_norm
-        g_gamma, g_beta, g_eps, g_silu, g_groups = gn_out
-        p.gn_out_gamma, p.gn_out_beta = _dev(g_gamma, torch.float32, "gn_out gamma"), _dev(g_beta, torch.float32, "gn_out beta")
-        p.gn_out_eps, p.gn_out_silu, p.gn_out_groups = float(g_eps), int(bool(g_silu)), int(g_groups)
-        if lib.imd_conv_gemm_gn_out_supported(C.byref(p)):
-            p.splitk_counters = None
-            gn_stats_groups = 0
-            L.check(lib.imd_conv_gemm(C.byref(p), cfg, _stream()))
-            out._imd_gn_applied = True
-            return out
-        p.gn_out_gamma = p.gn_out_beta = None
-        p.gn_out_groups = 0
+    if gn_out is not None and FUSED_GN_FINISH and _fuse_gn_out(p, lib, gn_out, out_scale):
+        L.check(lib.imd_conv_gemm(C.byref(p), cfg, _stream()))
+        out._imd_gn_applied = True          # the caller skips its own group_norm
+        return out
     stats = None
-    # (round 6: the register-staged tiles 0..4 / 7 write them too -- conv_in, the stride-2 downsampler of the 64x64 level -- wherever a tile's rows lie in one image;
-    #  GENERIC_GN_STATS is the A/B switch of that addition)
-    if gn_stats_groups and FUSED_GN_STATS and heads is None and not out_f32 and act != ACT_GEGLU and \
-            (cfg in (5, 22, 23, 29) or split_k > 1 or (GENERIC_GN_STATS and cfg in (-1, 0, 1, 2, 3, 4, 7))):
-        p.gn_stats_groups = gn_stats_groups
-        nparts = lib.imd_conv_gemm_stats_parts(C.byref(p), cfg)       # halo-patch epilogue (un-split) or the finish launch of the K slices
-        if nparts > 0:
-            Bimg = M // (Hout * Wout)
-            stats = (torch.empty((Bimg, nparts, gn_stats_groups, 2), dtype=torch.float32, device=x.device), nparts, gn_stats_groups)
-            p.gn_stats_out = stats[0].data_ptr()
-        else:
-            p.gn_stats_groups = 0
+    if gn_stats_groups and FUSED_GN_STATS and heads is None and not out_f32 and act != ACT_GEGLU:
+        stats = _attach_stats(p, lib, cfg, split_k, gn_stats_groups, M // (Hout * Wout), x.device)
     if GEMM_EVENT_HOOK is not None:
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
@@ -481,8 +490,6 @@ def conv_gemm(
 
 
 _splitk_ws: Dict[Tuple, torch.Tensor] = {}
-
-
 _splitk_cnt: Dict[Tuple, torch.Tensor] = {}
 
 

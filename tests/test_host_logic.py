@@ -560,6 +560,36 @@ def test_dispatch_sweep_reference_is_the_convolution(taps, stride, ups, B, Hin, 
     assert torch.allclose(got.double(), ref, rtol=1e-5, atol=1e-5), float((got.double() - ref).abs().max())
 
 
+def test_dispatch_decisions_equal_the_recorded_ones():
+    """What ``ops.conv_gemm`` decides -- entry point, tile config, K slices, statistics, periodic residual, gn_in / gn_out fusion, workspace and counters -- for
+    every tuning-table case in both element types, the off-table layers of every geometry case and each of them again under the opt-in switches, plus the
+    library's pure per-config answers, equals tests/golden/dispatch_decisions.json entry for entry (recorded BEFORE the tile-config tables existed:
+    tests/dispatch_recorder.py).  A second call with the decision cache kept decides the same, asks no ``*_supported`` tile query and looks nothing up."""
+    import json
+    from imagdressing_amd import _lib, ops
+    from tests import dispatch_cases as DC, dispatch_recorder as R
+    if not os.path.isfile(_lib.LIB_PATH):
+        import __graft_entry__ as g
+        g.build()
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "dispatch_decisions.json")) as f:
+        want = json.load(f)
+    table = DC.load_table()
+    got, bad = R.record(ops, _lib.load(), table)
+    assert (got["problems"], got["ids"]) == (want["problems"], want["ids"]), "the problem list is not the recorded one"
+    assert sorted(got["sections"]) == sorted(want["sections"])
+    for name, sec in want["sections"].items():
+        mine = got["sections"][name]
+        assert mine["ids"] == sec["ids"] and len(mine["launches"]) == len(sec["launches"]), f"{name}: not the recorded problems"
+        diff = [(i, a, b) for i, a, b in zip(R.section_ids(table, name), sec["launches"], mine["launches"]) if a != b]
+        assert not diff, f"{name}: {len(diff)} decisions differ from the record; (problem, recorded, now): {diff[:3]}"
+    assert got["pure"]["auto_cfg"] == want["pure"]["auto_cfg"]
+    for b, (a, m) in enumerate(zip(want["pure"]["per_cfg"], got["pure"]["per_cfg"])):
+        diff = [(cfg - 1, x, y) for cfg, (x, y) in enumerate(zip(a, m)) if x != y]
+        assert not diff and len(a) == len(m), f"parameter block {b}: (cfg, recorded, now) of [stats parts, auto split, gn_in ok, gn_out ok]: {diff[:3]}"
+    assert len(got["pure"]["per_cfg"]) == len(want["pure"]["per_cfg"])
+    assert not bad, f"{len(bad)} second calls (decision cache kept) launched something else or asked (tile queries, table lookups) != (0, 0): {bad[:3]}"
+
+
 def test_fold_layernorm_affine_is_exact_algebra():
     """LN_affine(x) W^T + b == LN_plain(x) W'^T + b' with (W', b') = ops.fold_layernorm_affine (the host side of the fused
     LayerNorm -> linear launches)"""
