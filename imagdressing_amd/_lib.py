@@ -57,6 +57,13 @@ class FfParams(_Sized):
                 ("ln_eps", C.c_float), ("dtype", C.c_int)]
 
 
+class XattnParams(_Sized):
+    _fields_ = [("struct_bytes", C.c_uint32), ("x", C.c_void_p), ("w", C.c_void_p), ("bq", C.c_void_p), ("bo", C.c_void_p), ("kv", C.c_void_p),
+                ("out", C.c_void_p), ("M", C.c_int), ("C", C.c_int), ("heads", C.c_int), ("L", C.c_int), ("rows_per_image", C.c_int),
+                ("kv_bdiv", C.c_int), ("text_rows", C.c_int), ("x_ld", C.c_int), ("out_ld", C.c_int), ("q_scale", C.c_float),
+                ("ln_eps", C.c_float), ("dtype", C.c_int)]
+
+
 class AttnParams(_Sized):
     _fields_ = [("struct_bytes", C.c_uint32), 
         ("q", C.c_void_p), ("k1", C.c_void_p), ("v1t", C.c_void_p), ("k2", C.c_void_p), ("v2t", C.c_void_p),
@@ -129,6 +136,8 @@ SYMBOLS = {
     "imd_row_linear": (C.c_int, [C.POINTER(ConvGemmParams), C.c_int, C.c_float, C.c_void_p]),
     "imd_row_linear_supported": (C.c_int, [C.POINTER(ConvGemmParams)]),
     "imd_ff_geglu": (C.c_int, [C.POINTER(FfParams), C.c_void_p]),
+    "imd_text_xattn320": (C.c_int, [C.POINTER(XattnParams), C.c_void_p]),
+    "imd_text_xattn320_supported": (C.c_int, [C.POINTER(XattnParams)]),
     "imd_groupnorm_workspace_floats": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "imd_layernorm": (C.c_int, [C.POINTER(LayerNormParams), C.c_void_p]),
     "imd_softmax_rows": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),

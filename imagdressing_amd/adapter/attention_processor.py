@@ -236,8 +236,16 @@ def _fused_attention(x: torch.Tensor, heads: int, *, wq_or_qkv: torch.Tensor, se
     D = Cc // heads
     dpk, dpv = ops.attn_padded_dims(D)
     dev, dt = x.device, x.dtype
-    q = ops.workspace("attn_q", (B, heads, N, dpk), dt, dev)
     qscale = D ** -0.5 * LOG2E
+    # text cross-attention of a 64x64-level block (norm2 fused, one key set of <= 96 keys, residual = the block state itself): norm2 -> to_q ->
+    # attention -> to_out + residual as ONE launch (csrc/row_xattn.hip); Q and O never exist in memory.  Everything else: the three launches below.
+    if (ops.FUSED_XATTN and not self_attn and q_ln is not None and kv1 is not None and kv2 is None and not pair_half
+            and ops.text_xattn_supported(Cc, heads, N, kv1[2]) and not ops.ATTN_FP8 and not ops.FUSED_OUT_PROJ
+            and residual is not None and residual.data_ptr() == x.data_ptr() and residual.shape == x.shape
+            and residual.dtype == dt and residual.is_contiguous()):
+        return ops.text_xattn(x, ops.pack_text_xattn(q_ln[0], q_ln[1], wo, bo), ops.pack_text_kv(kv1[0], kv1[1], kv1[2]),
+                              Lk=kv1[2], kv_bdiv=kv1_bdiv, ln_eps=q_ln[2], q_scale=qscale)
+    q = ops.workspace("attn_q", (B, heads, N, dpk), dt, dev)
     x2 = x.view(B * N, Cc)
     if self_attn:
         LP = ops.pad64(N)

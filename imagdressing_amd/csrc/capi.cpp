@@ -229,6 +229,17 @@ int imd_ff_geglu(const imd_ff_params* p, void* stream) {
     return imd_launch_ff_geglu(*p, (hipStream_t)stream);
 }
 
+int imd_text_xattn320_supported(const imd_xattn_params* p) {
+    return (p && p->struct_bytes == sizeof(*p) && imd_text_xattn320_supported_of(*p)) ? 1 : 0;
+}
+
+int imd_text_xattn320(const imd_xattn_params* p, void* stream) {
+    IMD_REQUIRE(p != nullptr, "text_xattn320: null params");
+    IMD_REQUIRE_SIZE(p, "text_xattn320");
+    IMD_REQUIRE(p->x && p->w && p->bq && p->bo && p->kv && p->out, "text_xattn320: null pointer");
+    return imd_launch_text_xattn320(*p, (hipStream_t)stream);
+}
+
 int imd_layernorm(const imd_layernorm_params* p, void* stream) {
     IMD_REQUIRE(p != nullptr, "layernorm: null params");
     IMD_REQUIRE_SIZE(p, "layernorm");

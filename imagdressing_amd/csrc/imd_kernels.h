@@ -61,6 +61,8 @@ int imd_launch_gemm_dma128(const ConvGemmParams& p, int stages, int bk, hipStrea
 int imd_launch_gemm_dma256(const ConvGemmParams& p, int form, hipStream_t s);        // gemm_dma256.hip: 0 = 256x128 persistent, 1 = 256x128 one item per workgroup (tile configs 30 / 31)
 bool imd_conv_dma_supported(const ConvGemmParams& p);                         // gemm_dma.hip: 128 x 128 x 32, 3-stage ring (tile config 17)
 int imd_launch_ff_geglu(const imd_ff_params& p, hipStream_t s);                              // ff_fused.hip
+bool imd_text_xattn320_supported_of(const imd_xattn_params& p);                              // row_xattn.hip
+int imd_launch_text_xattn320(const imd_xattn_params& p, hipStream_t s);
 int imd_launch_attention(const AttnParams& p, hipStream_t s);
 int imd_launch_attention_d40(const AttnParams& p, int variant, hipStream_t s);
 int imd_launch_attention_fp8(const AttnParams& p, int eq, int ek, int ev, hipStream_t s);                       // attention_d40_fp8.hip

@@ -577,6 +577,159 @@ def ff_geglu_fused(x2d: torch.Tensor, packed: dict, ln_eps: float = 1e-5, out: O
     return out
 
 
+# ---------------------------------------------------------------------------------------------------------------------
+# Text cross-attention of a 320-channel block as one launch (csrc/row_xattn.hip; include/imagdressing_hip.h::imd_xattn_params):
+# norm2 -> attn2.to_q -> softmax(q Kt^T) Vt over <= 96 text keys -> attn2.to_out[0] + bias + residual.  A/B switch, default on.
+# ---------------------------------------------------------------------------------------------------------------------
+FUSED_XATTN = _os.environ.get("IMD_FUSED_XATTN", "1") != "0"
+XATTN_C, XATTN_HEADS, XATTN_D, XATTN_DP, XATTN_LMAX = 320, 8, 40, 48, 96
+XATTN_CHUNK = 64 * 320                 # elements of one LDS ring slot (40960 bytes)
+XATTN_VROW = 104                       # elements of a V^T image row: 96 key columns + one 16-byte piece of padding
+XATTN_HEAD = XATTN_LMAX * XATTN_DP + XATTN_DP * XATTN_VROW       # 9600 elements: K image, then V^T image
+XATTN_PAD_KEY = -30000.0               # K column 40 of a pad key (exact in fp16): exp2(score - max) is 0 in fp32
+_XATTN_W: Dict[Tuple, tuple] = {}
+_XATTN_KV: Dict[int, tuple] = {}
+_clear_hooks.append(_XATTN_W.clear)
+_clear_hooks.append(_XATTN_KV.clear)
+
+
+def xattn_q_rows(device=None):
+    """(source row of W_q' [384], valid [384]) of the packed to_q rows: packed row 64 c + r belongs to wave half r // 32, whose row
+    R = 32 c + r % 32 is dim R % 48 of head 4 (r // 32) + R // 48 (dims 40..47: zero rows)."""
+    i = torch.arange(6 * 64, device=device)
+    r = i % 64
+    R = 32 * (i // 64) + r % 32
+    head, dim = 4 * (r // 32) + R // 48, R % 48
+    return head * XATTN_D + dim.clamp(max=XATTN_D - 1), dim < XATTN_D
+
+
+def xattn_o_cols(device=None):
+    """Source column of W_o [320] at packed input position 16 s + 8 hi + e: channel group 2 s + e // 4 of the list (head h, group j) ->
+    5 h + j, dim 8 j + 4 hi + e % 4 -- the order in which a lane's O registers leave the P.V accumulators."""
+    k = torch.arange(XATTN_C, device=device)
+    s, hi, e = k // 16, (k % 16) // 8, k % 8
+    G = 2 * s + e // 4
+    return (G // 5) * XATTN_D + 8 * (G % 5) + 4 * hi + e % 4
+
+
+def xattn_swizzle_rows(w2d: torch.Tensor) -> torch.Tensor:
+    """[R, 320] -> the same rows as they sit in an LDS ring slot: the 16-byte piece at position q of chunk row r is source piece
+    q ^ ((r >> 1) & 7) (r = row % 64).  An involution."""
+    R = w2d.shape[0]
+    r = torch.arange(R, device=w2d.device) % 64
+    pos = torch.arange(40, device=w2d.device)[None, :] ^ ((r >> 1) & 7)[:, None]
+    return w2d.reshape(R, 40, 8).gather(1, pos[:, :, None].expand(R, 40, 8)).reshape(R, XATTN_C).contiguous()
+
+
+def xattn_key_cols(device=None):
+    """Key held by column c of a V^T image: inside every 16-key step the keys sit in the register order of an S^T accumulator
+    (0-3, 8-11, 4-7, 12-15), so that packed P registers are the B operand of O^T += V^T P^T."""
+    c = torch.arange(XATTN_LMAX, device=device)
+    c16 = c % 16
+    return (c // 16) * 16 + (c16 & 3) + 8 * ((c16 >> 2) & 1) + 4 * (c16 >> 3)
+
+
+def xattn_k_pieces(device=None):
+    """[96, 6]: source 16-byte piece at position q of K image row r (rows 8..15 mod 16 are stored rotated by three pieces)."""
+    r = torch.arange(XATTN_LMAX, device=device)
+    return (torch.arange(6, device=device)[None, :] - 3 * ((r >> 3) & 1)[:, None]) % 6
+
+
+def _pack_text_xattn(wq, bq, wo, bo):
+    dev, dt = wq.device, wq.dtype
+    src, valid = xattn_q_rows(dev)
+    wq_p = torch.where(valid[:, None], wq[src], torch.zeros((), dtype=dt, device=dev))
+    bq_p = torch.where(valid, bq.float()[src], torch.zeros((), dtype=torch.float32, device=dev)).contiguous()
+    wo_p = wo[:, xattn_o_cols(dev)]
+    w = torch.cat([xattn_swizzle_rows(wq_p), xattn_swizzle_rows(wo_p)], 0).contiguous()
+    bo_p = torch.zeros(XATTN_C, dtype=torch.float32, device=dev) if bo is None else bo.float().contiguous()
+    return dict(w=w, bq=bq_p, bo=bo_p)
+
+
+def pack_text_xattn(wq: torch.Tensor, bq: torch.Tensor, wo: torch.Tensor, bo: Optional[torch.Tensor]):
+    """Weights of :func:`text_xattn` from ``wq`` [320, 320] / ``bq`` [320] fp32 (LayerNorm affine folded in:
+    :func:`fold_layernorm_affine`) and ``wo`` [320, 320] / ``bo`` [320] fp32 | None.  Layout: include/imagdressing_hip.h::imd_xattn_params.
+    Host-side, once per layer: cached against the storage and version of the four tensors (which the cache keeps alive)."""
+    if tuple(wq.shape) != (XATTN_C, XATTN_C) or tuple(wo.shape) != (XATTN_C, XATTN_C) or wq.dtype != wo.dtype:
+        raise L.ImdError(f"pack_text_xattn: expected two [320, 320] matrices of one dtype, got {tuple(wq.shape)} {wq.dtype}, {tuple(wo.shape)} {wo.dtype}")
+    srcs = (wq, bq, wo, bo)
+    key = tuple(None if t is None else (t.data_ptr(), t._version, t.dtype, str(t.device)) for t in srcs)
+    ent = _XATTN_W.get(key)
+    if ent is None:
+        if len(_XATTN_W) > 64:
+            _XATTN_W.clear()
+        ent = _XATTN_W[key] = (srcs, _pack_text_xattn(wq, bq, wo, bo))
+    return ent[1]
+
+
+def _pack_text_kv(k, vt, Lk):
+    Bt, dev, dt = k.shape[0], k.device, k.dtype
+    H, D, DP, LM = XATTN_HEADS, XATTN_D, XATTN_DP, XATTN_LMAX
+    kf = torch.zeros(Bt, H, LM, DP, dtype=dt, device=dev)
+    kf[:, :, :Lk, :D] = k[:, :, :Lk, :D]
+    kf[:, :, Lk:, D] = XATTN_PAD_KEY
+    kimg = kf.view(Bt, H, LM, 6, 8).gather(3, xattn_k_pieces(dev)[None, None, :, :, None].expand(Bt, H, LM, 6, 8))
+    vf = torch.zeros(Bt, H, DP, LM, dtype=dt, device=dev)
+    vf[:, :, :D, :Lk] = vt[:, :, :D, :Lk]
+    vf[:, :, D, :] = 1.0
+    vimg = torch.zeros(Bt, H, DP, XATTN_VROW, dtype=dt, device=dev)
+    vimg[..., :LM] = vf[..., xattn_key_cols(dev)]
+    head = torch.cat([kimg.reshape(Bt, H, LM * DP), vimg.reshape(Bt, H, DP * XATTN_VROW)], -1)
+    img = torch.zeros(Bt, 4, XATTN_CHUNK, dtype=dt, device=dev)
+    img[:, :, :XATTN_HEAD] = head[:, :4]
+    img[:, :, XATTN_HEAD:2 * XATTN_HEAD] = head[:, 4:]
+    return img
+
+
+def pack_text_kv(k: torch.Tensor, vt: torch.Tensor, Lk: int) -> torch.Tensor:
+    """K / V^T images of :func:`text_xattn` [Bt, 4, 20480] from the projected text keys ``k`` [Bt, 8, Lk, 48] and values
+    ``vt`` [Bt, 8, 64, LP] (the operands of :func:`attention`): chunk c = heads c and c + 4 exactly as they sit in an LDS ring slot --
+    K [96 keys][48 dims] with column 40 = 0 (key) / XATTN_PAD_KEY (pad key), V^T [48][104] with an all-ones row 40 and the key
+    columns in accumulator order.  Step-invariant: built once per projected K (cached against its identity, which the cache keeps
+    alive) and dropped by :func:`clear_workspaces`."""
+    if k.dim() != 4 or k.shape[1] != XATTN_HEADS or k.shape[3] != XATTN_DP or not (1 <= Lk <= XATTN_LMAX) or k.shape[2] < Lk \
+            or vt.shape[:2] != k.shape[:2] or vt.shape[2] < XATTN_D or vt.shape[3] < Lk:
+        raise L.ImdError(f"pack_text_kv: expected K [Bt, 8, L, 48] / V^T [Bt, 8, >= 40, >= L] with L <= 96, got {tuple(k.shape)} / {tuple(vt.shape)}, L = {Lk}")
+    hit = _XATTN_KV.get(id(k))
+    if hit is not None and hit[0] is k and hit[1] is vt and hit[2] == Lk:
+        return hit[3]
+    if len(_XATTN_KV) > 64:
+        _XATTN_KV.clear()
+    img = _pack_text_kv(k, vt, Lk)
+    _XATTN_KV[id(k)] = (k, vt, Lk, img)
+    return img
+
+
+def text_xattn_supported(C_: int, heads: int, N: int, Lk: int) -> bool:
+    return C_ == XATTN_C and heads == XATTN_HEADS and N % 128 == 0 and 1 <= Lk <= XATTN_LMAX
+
+
+def text_xattn(x: torch.Tensor, packed: dict, kv_img: torch.Tensor, *, Lk: int, kv_bdiv: int = 1, ln_eps: float = 1e-5,
+               q_scale: Optional[float] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out = x + bo + Wo attention(LN(x) Wq'^T + bq', text K / V) for ``x`` [B, N, 320] in one launch
+    (include/imagdressing_hip.h::imd_text_xattn320).  ``packed`` = :func:`pack_text_xattn`, ``kv_img`` = :func:`pack_text_kv` of the
+    B / kv_bdiv conditioning rows.  No allocation besides ``out``, no synchronisation."""
+    ensure_device(x.device)
+    B, N, C_ = x.shape
+    dt = x.dtype
+    if out is None:
+        out = torch.empty((B, N, C_), dtype=dt, device=x.device)
+    if kv_img.dim() != 3 or tuple(kv_img.shape[1:]) != (4, XATTN_CHUNK):
+        raise L.ImdError(f"text_xattn: kv_img must be [Bt, 4, {XATTN_CHUNK}], got {tuple(kv_img.shape)}")
+    p = L.XattnParams()
+    p.x, p.w, p.out = _dev(x, dt, "x"), _dev(packed["w"], dt, "w"), _dev(out, dt, "out")
+    p.bq, p.bo, p.kv = _dev(packed["bq"], torch.float32, "bq"), _dev(packed["bo"], torch.float32, "bo"), _dev(kv_img, dt, "kv_img")
+    p.M, p.C, p.heads, p.L = B * N, C_, XATTN_HEADS, int(Lk)
+    p.rows_per_image, p.kv_bdiv, p.text_rows = N, int(kv_bdiv), kv_img.shape[0]
+    p.x_ld = p.out_ld = C_
+    p.q_scale = float(XATTN_D ** -0.5 * 1.4426950408889634 if q_scale is None else q_scale)
+    p.ln_eps, p.dtype = float(ln_eps), _code(x, "x")
+    _count("gemm_conv", 2 * 2.0 * B * N * C_ * C_)
+    _count("attention", 4.0 * XATTN_HEADS * N * XATTN_D * B * Lk)
+    L.check(L.load().imd_text_xattn320(C.byref(p), _stream()))
+    return out
+
+
 def conv2d_nhwc(x: torch.Tensor, w: torch.Tensor, bias=None, *, taps=9, stride=1, ups=False, rowvec=None,
                 rowvec_stride=0, rowvec_off=0, res=None, out_scale=1.0, act=ACT_NONE, out_f32=False, cfg=-1, split_k=0, gn=None,
                 pad_br_only=False, gn_stats_groups=0, gn_out=None, gn_in=None) -> torch.Tensor:

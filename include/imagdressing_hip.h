@@ -208,6 +208,32 @@ typedef struct imd_ff_params {
     int dtype;
 } imd_ff_params;
 
+/* Text cross-attention of a transformer block on the 64x64 level as one launch (row_xattn.hip), C = 320, 8 heads of 40, L <= 96 keys:
+ *   out = x + bo + Wo . concat_h( softmax(q_h Kt_h^T) Vt_h ),   q = (LN(x) . Wq'^T + bq') * q_scale
+ *   (norm2 -> attn2.to_q -> attention over the text keys -> attn2.to_out[0] + bias + block residual; softmax in base 2: q_scale carries log2 e)
+ * Operands are PACKED by the host (imagdressing_amd/ops.py::pack_text_xattn / pack_text_kv; layouts documented there and in row_xattn.hip):
+ *   w  [11 chunks][64 rows][320]: chunks 0..5 = Wq' (LayerNorm gamma folded in) with every head padded to 48 rows (row 32 c + r of half
+ *      r / 32 = head 4 (r / 32) + (32 c + r % 32) / 48, dim (32 c + r % 32) % 48; dims >= 40 are zero rows), chunks 6..10 = Wo with its input
+ *      channels in the order of the kernel's O registers; the 16-byte pieces of chunk row r sit at position piece ^ ((r >> 1) & 7);
+ *   bq [6][64] fp32 in the row order of chunks 0..5 (LayerNorm beta folded in), bo [320] fp32;
+ *   kv [text_rows][4 chunks][40960 bytes]: chunk c = the K / V^T images of heads c and c + 4 (19200 bytes each) of one conditioning row. */
+typedef struct imd_xattn_params {
+    uint32_t struct_bytes; /* sizeof(imd_xattn_params) in the caller's view; checked on entry */
+    const uint16_t* x;   /* [M, x_ld] the block's UN-normalised state -- also the residual */
+    const uint16_t* w;
+    const float* bq;
+    const float* bo;
+    const uint16_t* kv;
+    uint16_t* out;       /* [M, out_ld] */
+    int M, C, heads, L;  /* L: text keys per conditioning row (the images mask keys >= L) */
+    int rows_per_image;  /* tokens per batch entry, a multiple of 128; image b = row / rows_per_image reads conditioning row b / kv_bdiv */
+    int kv_bdiv, text_rows;
+    int x_ld, out_ld;
+    float q_scale;       /* head_dim^-1/2 * log2(e) */
+    float ln_eps;
+    int dtype;
+} imd_xattn_params;
+
 typedef struct imd_groupnorm_params {
     uint32_t struct_bytes; /* sizeof(imd_groupnorm_params) in the caller's view (ABI v8); checked on entry */
     const uint16_t* x; uint16_t* y; const float* gamma; const float* beta;
@@ -368,6 +394,12 @@ int imd_row_linear_supported(const imd_conv_gemm_params* p);
 
 /* BasicTransformerBlock.norm3 + ff (GEGLU feed-forward) + residual as one launch; see imd_ff_params. */
 int imd_ff_geglu(const imd_ff_params* p, void* stream);
+
+/* BasicTransformerBlock.norm2 + attn2 (text cross-attention, to_q .. to_out[0]) + residual as one launch; see imd_xattn_params.
+ * imd_text_xattn320_supported: 1 iff the geometry in *p (M, C, heads, L, rows_per_image, kv_bdiv, text_rows, x_ld, out_ld, dtype) is one the
+ * kernel takes; pointers are not looked at. */
+int imd_text_xattn320(const imd_xattn_params* p, void* stream);
+int imd_text_xattn320_supported(const imd_xattn_params* p);
 
 /* LayerNorm over the last dim: BasicTransformerBlock.norm1/2/3; adapter/resampler.py:16,43-44,199. */
 int imd_layernorm(const imd_layernorm_params* p, void* stream);
