@@ -138,6 +138,8 @@ SYMBOLS = {
     "imd_ff_geglu": (C.c_int, [C.POINTER(FfParams), C.c_void_p]),
     "imd_text_xattn320": (C.c_int, [C.POINTER(XattnParams), C.c_void_p]),
     "imd_text_xattn320_supported": (C.c_int, [C.POINTER(XattnParams)]),
+    "imd_conv_ups_phase": (C.c_int, [C.POINTER(ConvGemmParams), C.c_void_p]),
+    "imd_conv_ups_phase_supported": (C.c_int, [C.POINTER(ConvGemmParams)]),
     "imd_groupnorm_workspace_floats": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "imd_layernorm": (C.c_int, [C.POINTER(LayerNormParams), C.c_void_p]),
     "imd_softmax_rows": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),

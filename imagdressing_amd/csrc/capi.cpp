@@ -240,6 +240,15 @@ int imd_text_xattn320(const imd_xattn_params* p, void* stream) {
     return imd_launch_text_xattn320(*p, (hipStream_t)stream);
 }
 
+int imd_conv_ups_phase_supported(const imd_conv_gemm_params* p) { return (sized(p) && imd_conv_ups_phase_supported_of(*p)) ? 1 : 0; }
+
+int imd_conv_ups_phase(const imd_conv_gemm_params* p, void* stream) {
+    IMD_REQUIRE(p != nullptr, "conv_ups_phase: null params");
+    IMD_REQUIRE_SIZE(p, "conv_ups_phase");
+    IMD_REQUIRE(p->x && p->w && p->out, "conv_ups_phase: null input / weight / output pointer");
+    return imd_launch_conv_ups_phase(*p, (hipStream_t)stream);
+}
+
 int imd_layernorm(const imd_layernorm_params* p, void* stream) {
     IMD_REQUIRE(p != nullptr, "layernorm: null params");
     IMD_REQUIRE_SIZE(p, "layernorm");

@@ -751,6 +751,124 @@ def conv2d_nhwc(x: torch.Tensor, w: torch.Tensor, bias=None, *, taps=9, stride=1
     return r
 
 
+# ---------------------------------------------------------------------------------------------------------------------
+# Upsample2D (nearest-2x interpolate -> 3x3 conv) as four 2x2 phase convolutions (csrc/conv_patch.hip::conv_ups_phase_kernel;
+# include/imagdressing_hip.h::imd_conv_ups_phase): after the upsample the four pixels of a 2x2 output block see the same 2x2 source
+# pixels, so the 3x3 taps that fall on one source pixel are summed once per layer and four taps run instead of nine.  A/B switch,
+# default on; IMD_UPS_PHASE=0 restores conv2d_nhwc(ups=True), whose dispatch is untouched.
+# ---------------------------------------------------------------------------------------------------------------------
+UPS_PHASE = _os.environ.get("IMD_UPS_PHASE", "1") != "0"
+UPS_PHASE_TAPS = (((0,), (1, 2)), ((0, 1), (2,)))      # [phase p][tap d] -> the 3x3 taps k that read source pixel y + p - 1 + d (the same in x)
+UPS_PHASE_CFG = "ups_phase"                            # what the event hook records in place of a tile config
+_UPS_W: Dict[Tuple, tuple] = {}
+_UPS_OK: Dict[Tuple, bool] = {}
+_clear_hooks.append(_UPS_W.clear)
+_clear_hooks.append(_UPS_OK.clear)
+
+
+def _pack_upsample_phase(w: torch.Tensor, dtype=None) -> torch.Tensor:
+    N, Cp = w.shape[0], w.shape[1] // 9
+    acc_dt = torch.float32 if w.dtype in DTYPE_CODE else w.dtype       # 16-bit weights: sum in fp32, round once
+    w9 = w.to(acc_dt).view(N, 3, 3, Cp)
+    out = torch.zeros(4, N, 4, Cp, dtype=acc_dt, device=w.device)
+    for py in range(2):
+        for px in range(2):
+            for dy in range(2):
+                for dx in range(2):
+                    for ky in UPS_PHASE_TAPS[py][dy]:
+                        for kx in UPS_PHASE_TAPS[px][dx]:
+                            out[2 * py + px, :, 2 * dy + dx] += w9[:, ky, kx]
+    return out.to(w.dtype if dtype is None else dtype).contiguous()
+
+
+def pack_upsample_phase(w: torch.Tensor, dtype=None) -> torch.Tensor:
+    """Phase weights of :func:`conv_ups_phase` [4 phases py*2+px][Cout][4 taps dy*2+dx][Cin_p] from the packed 3x3 weight ``w``
+    [Cout, 9 * Cin_p] (tap-major: ky, kx, channel), in ``dtype`` (default: ``w``'s): summed in fp32, rounded once.  Packed from a 16-bit ``w`` the
+    sums carry a second rounding; a caller that still holds the layer's fp32 weight can hand that in with ``dtype`` = the activation type.
+    16/9 of the layer's weight bytes.
+    Host-side, once per layer: cached against the storage and version of ``w`` (which the cache keeps alive) -- the first call
+    must lie outside any HIP-graph capture (the pipelines run one step eagerly before they capture)."""
+    if w.dim() != 2 or w.shape[1] % 9:
+        raise L.ImdError(f"pack_upsample_phase: expected a packed 3x3 weight [Cout, 9 * Cin], got {tuple(w.shape)}")
+    key = (w.data_ptr(), w._version, w.dtype, str(w.device), tuple(w.shape), dtype)
+    ent = _UPS_W.get(key)
+    if ent is None:
+        if len(_UPS_W) > 64:
+            _UPS_W.clear()
+        ent = _UPS_W[key] = (w, _pack_upsample_phase(w, dtype))
+    return ent[1]
+
+
+def _ups_phase_block(shape, N: int, dtype):
+    """The parameter block of the 9-tap problem conv3x3(nearest2x(x [B, H, W, Cin])) -> N channels (geometry only, no pointers)."""
+    B, H, W, Cin = shape
+    p = L.ConvGemmParams()
+    p.flags = _gemm_call_flags()
+    p.dtype, p.M, p.N, p.K, p.Cin, p.taps = DTYPE_CODE[dtype], 4 * B * H * W, N, 9 * Cin, Cin, 9
+    p.Hin, p.Win, p.Hout, p.Wout, p.stride, p.ups = H, W, 2 * H, 2 * W, 1, 1
+    p.x_pix_stride, p.out_ld, p.res_ld, p.out_scale, p.split_k = Cin, N, N, 1.0, 1
+    return p
+
+
+def conv_ups_phase_supported(x: torch.Tensor, w: torch.Tensor, bias=None) -> bool:
+    """Should ``conv3x3(nearest2x(x)) + bias`` of ``x`` [B, H, W, Cin] with the packed 3x3 weight ``w`` [Cout, 9 * Cin] run as four phase convolutions
+    (``imd_conv_ups_phase_supported``: Cin % 32 == 0, operands < 2 GiB, clearly fewer tile-padded multiplies than the 9-tap form, and a grid of at
+    least 160 workgroups -- the smallest at which a gain over the K-sliced 9-tap launch has been measured)?
+    A pure function of the geometry: remembered per geometry."""
+    if x.dim() != 4 or w.dim() != 2 or w.shape[1] != 9 * x.shape[3] or x.dtype not in DTYPE_CODE or w.dtype != x.dtype or not x.is_contiguous():
+        return False
+    key = (tuple(x.shape), w.shape[0], x.dtype)
+    ok = _UPS_OK.get(key)
+    if ok is None:
+        ok = bool(L.load().imd_conv_ups_phase_supported(C.byref(_ups_phase_block(x.shape, w.shape[0], x.dtype))))
+        if len(_UPS_OK) < 4096:
+            _UPS_OK[key] = ok
+    return ok
+
+
+def conv_ups_phase(x: torch.Tensor, w: torch.Tensor, bias=None, *, out: Optional[torch.Tensor] = None,
+                   phase_weights: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """x [B, H, W, Cin] 16-bit -> conv3x3(nearest2x(x), padding 1) + bias [B, 2H, 2W, Cout] in one launch of four taps per output pixel
+    (include/imagdressing_hip.h::imd_conv_ups_phase).  ``w`` is the layer's packed 3x3 weight [Cout, 9 * Cin]; its phase form comes from
+    :func:`pack_upsample_phase` (cached) unless the caller hands in ``phase_weights`` [4, Cout, 4, Cin] it packed itself.  Runs whatever the kernel
+    computes correctly (Cin % 32 == 0, contiguous operands < 2 GiB) and raises otherwise -- there is no fallback in here; whether the launch PAYS
+    is :func:`conv_ups_phase_supported`, which the call sites ask first.
+    Counted and traced as the 9-tap convolution it computes (2 M N K with K = 9 Cin)."""
+    ensure_device(x.device)
+    B, H, W, Cin = x.shape
+    N = w.shape[0]
+    M, K = 4 * B * H * W, 9 * Cin
+    dt = x.dtype
+    if w.dim() != 2 or tuple(w.shape) != (N, K) or w.dtype != dt:
+        raise L.ImdError(f"conv_ups_phase: expected a packed 3x3 weight [{N}, {K}] of {dt}, got {tuple(w.shape)} {w.dtype}")
+    wp = pack_upsample_phase(w) if phase_weights is None else phase_weights
+    if tuple(wp.shape) != (4, N, 4, Cin):
+        raise L.ImdError(f"conv_ups_phase: phase weights must be [4, {N}, 4, {Cin}], got {tuple(wp.shape)}")
+    if out is None:
+        out = torch.empty((B, 2 * H, 2 * W, N), dtype=dt, device=x.device)
+    elif out.numel() != M * N:
+        raise L.ImdError(f"conv_ups_phase: out has {out.numel()} elements, expected {M * N}")
+    p = _ups_phase_block(x.shape, N, dt)
+    p.x, p.w, p.out = _dev(x, dt, "x"), _dev(wp, dt, "phase weights"), _dev(out, dt, "out")
+    p.bias = None if bias is None else _dev(bias, torch.float32, "bias")
+    _count("gemm_conv", 2.0 * M * N * K)
+    if GEMM_TRACE is not None:
+        GEMM_TRACE.append(dict(M=M, N=N, K=K, Cin=Cin, taps=9, Hin=H, Win=W, Hout=2 * H, Wout=2 * W, stride=1, ups=1, splittable=True, dtype=str(x.dtype),
+                               bias=bias is not None, rowvec=False, rowvec_stride=0, res=False, res_rows=0, act=ACT_NONE, out_f32=False, heads=None,
+                               gn_stats_groups=0, x_pix_stride=Cin, out_scale=1.0, pad_br_only=False, out_ld=N, res_ld=N, gn=False, gn_in=False, gn_out=False,
+                               ups_phase=True))
+    lib = L.load()
+    if GEMM_EVENT_HOOK is not None:
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        L.check(lib.imd_conv_ups_phase(C.byref(p), _stream()))
+        e1.record()
+        GEMM_EVENT_HOOK.setdefault((f"{M},{N},{K},9,1,1|{2 * H}x{2 * W}", UPS_PHASE_CFG, 1), []).append((e0, e1))
+    else:
+        L.check(lib.imd_conv_ups_phase(C.byref(p), _stream()))
+    return out.view(B, 2 * H, 2 * W, N)
+
+
 # bench.py installs {"match": fn(**shape) -> bool, "events": []} to bracket matching launches with HIP
 # events on the launch stream (roofline measurement inside the timed region); None = no overhead.
 ATTN_EVENT_HOOK = None

@@ -203,6 +203,10 @@ class ConvOp:
         assert cout_p == cout, "output channels must be a multiple of 4"
 
     def __call__(self, x, **kw):
+        # Upsample2D (interpolate nearest-2x -> conv): four 2x2 phase convolutions where the library's query says the launch pays (ops.conv_ups_phase:
+        # four taps instead of nine; phase weights packed at the first call); ops.UPS_PHASE = False restores the fused-gather 9-tap launch below
+        if ops.UPS_PHASE and self.taps == 9 and kw == {"ups": True} and ops.conv_ups_phase_supported(x, self.weight, self.bias):
+            return ops.conv_ups_phase(x, self.weight, self.bias)
         return ops.conv2d_nhwc(x, self.weight, self.bias, taps=self.taps, **kw)
 
 

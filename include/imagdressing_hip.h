@@ -401,6 +401,22 @@ int imd_ff_geglu(const imd_ff_params* p, void* stream);
 int imd_text_xattn320(const imd_xattn_params* p, void* stream);
 int imd_text_xattn320_supported(const imd_xattn_params* p);
 
+/* Upsample2D (nearest-2x interpolate -> 3x3 conv) as four 2x2 PHASE convolutions (conv_patch.hip): out[2y + py, 2x + px] = bias +
+ * sum over dy, dx in {0, 1} of W'[py, px][dy, dx] . src[y + py - 1 + dy, x + px - 1 + dx] (out-of-image src = 0) -- 4 taps instead of 9.
+ * *p describes the 9-tap problem exactly as imd_conv_gemm takes it (taps = 9, K = 9 Cin, stride = 1, ups = 1, Hout = 2 Hin, Wout = 2 Win),
+ * except that p->w holds the PHASE weights [4 phases py * 2 + px][N][4 taps dy * 2 + dx][Cin] in the activation type, the 3x3 taps that
+ * fall on one source pixel summed in fp32 and rounded once (rows: py = 0: {ky 0}, {ky 1, 2}; py = 1: {ky 0, 1}, {ky 2}; the same in x;
+ * imagdressing_amd/ops.py::pack_upsample_phase, once per layer).
+ * imd_conv_ups_phase runs any problem with Cin % 32 == 0, contiguous 16-bit input and output (x_pix_stride = Cin, out_ld = N) below 2 GiB like
+ * the phase weights, and the bias as its whole epilogue (no residual, row vector, GroupNorm prologue, statistics, activation, scale, K slices,
+ * fp32 or head-split output).  imd_conv_ups_phase_supported: 1 iff it runs *p AND the launch pays against the 9-tap form, whose results it does
+ * not reproduce bit for bit: 6/5 of the tile-padded multiply count of the phase form (16 per 8 x 16 tile of the source map) is below that of the
+ * 9-tap form (9 per 8 x 16 tile of the output map) -- an 8 x 8 source is refused -- and the grid (images x source tiles x 4 phases x 128-channel
+ * tiles) has at least 160 workgroups, the smallest at which a gain over the K-sliced 9-tap launch has been measured (the kernel takes no K slices).
+ * Pointers are not looked at. */
+int imd_conv_ups_phase(const imd_conv_gemm_params* p, void* stream);
+int imd_conv_ups_phase_supported(const imd_conv_gemm_params* p);
+
 /* LayerNorm over the last dim: BasicTransformerBlock.norm1/2/3; adapter/resampler.py:16,43-44,199. */
 int imd_layernorm(const imd_layernorm_params* p, void* stream);
 /* Row softmax, fp32 in -> 16-bit out: p[r][c] = softmax_c(s[r][:cols]) (the upcast softmax of the single-head, d = 512
