@@ -17,12 +17,14 @@ imported, which the scripts do before they import ``transformers``' models.
 """
 import os as _os
 
-from imagdressing_amd.scheduler import DDIMScheduler, UniPCMultistepScheduler  # noqa: F401
+from imagdressing_amd.scheduler import (DDIMScheduler, DPMSolverMultistepScheduler, EulerAncestralDiscreteScheduler,  # noqa: F401
+                                        EulerDiscreteScheduler, PNDMScheduler, UniPCMultistepScheduler)
 from imagdressing_amd.unet import ControlNetModel, UNet2DConditionModel  # noqa: F401
 from imagdressing_amd.vae import AutoencoderKL  # noqa: F401
 
 __version__ = "0.24.0+imagdressing_amd"
-__all__ = ["UNet2DConditionModel", "ControlNetModel", "AutoencoderKL", "DDIMScheduler", "UniPCMultistepScheduler"]
+__all__ = ["UNet2DConditionModel", "ControlNetModel", "AutoencoderKL", "DDIMScheduler", "UniPCMultistepScheduler",
+           "DPMSolverMultistepScheduler", "EulerDiscreteScheduler", "EulerAncestralDiscreteScheduler", "PNDMScheduler"]
 
 
 def _use_native_clip():

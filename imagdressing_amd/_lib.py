@@ -105,6 +105,20 @@ class DdimParams(_Sized):
     ]
 
 
+class SamplerParams(_Sized):
+    _fields_ = [("struct_bytes", C.c_uint32),
+        ("z", C.c_void_p), ("eps", C.c_void_p), ("x_next", C.c_void_p), ("hist", C.c_void_p),
+        ("B", C.c_int), ("HW", C.c_int), ("K", C.c_int), ("dtype", C.c_int),
+        ("guidance", C.c_float), ("guidance_rows", C.c_void_p),
+        ("m_x", C.c_float), ("m_e", C.c_float), ("z_x", C.c_float), ("z_m", C.c_float),
+        ("z_h", C.c_float * 4),
+        ("z_n", C.c_float), ("b_img", C.c_float), ("b_noise", C.c_float), ("in_scale", C.c_float),
+        ("store", C.c_int),
+        ("noise", C.c_void_p), ("mask", C.c_void_p), ("z_img", C.c_void_p), ("blend_noise", C.c_void_p),
+        ("coefs", C.c_void_p),
+    ]
+
+
 # every symbol include/imagdressing_hip.h declares: name -> (restype, argtypes)
 SYMBOLS = {
     "imd_abi_version": (C.c_int, []),
@@ -145,6 +159,7 @@ SYMBOLS = {
     "imd_softmax_rows": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "imd_ddim_cfg_step": (C.c_int, [C.POINTER(DdimParams), C.c_void_p]),
     "imd_ddim_cfg_step_rows": (C.c_int, [C.POINTER(DdimParams), C.c_void_p, C.c_void_p]),
+    "imd_sampler_step": (C.c_int, [C.POINTER(SamplerParams), C.c_void_p]),
     "imd_timestep_embedding": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "imd_add": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_long, C.c_int, C.c_float, C.c_int, C.c_void_p]),
     "imd_embed_tokens": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_long, C.c_int, C.c_int, C.c_void_p]),

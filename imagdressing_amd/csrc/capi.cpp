@@ -286,6 +286,13 @@ int imd_ddim_cfg_step(const imd_ddim_params* p, void* stream) {
     return imd_launch_ddim_cfg_step(*p, (hipStream_t)stream);
 }
 
+int imd_sampler_step(const imd_sampler_params* p, void* stream) {
+    IMD_REQUIRE(p != nullptr, "sampler_step: null params");
+    IMD_REQUIRE_SIZE(p, "sampler_step");
+    IMD_REQUIRE(p->z && p->eps, "sampler_step: null pointer");
+    return imd_launch_sampler_step(*p, (hipStream_t)stream);
+}
+
 int imd_ddim_cfg_step_rows(const imd_ddim_params* p, const float* guidance, void* stream) {
     IMD_REQUIRE(p != nullptr, "ddim_cfg_step_rows: null params");
     IMD_REQUIRE_SIZE(p, "ddim_cfg_step_rows");

@@ -70,6 +70,81 @@ __global__ __launch_bounds__(256) void ddim_cfg_step_kernel(const DdimParams p, 
     }
 }
 
+// sampler_step: the same fused launch for every sampler whose update is affine in the latent, the guided epsilon, a short history
+// and noise (DPM-Solver++ 1 / 2M, Euler, Euler-ancestral, PNDM/PLMS -- imd_sampler_params):
+//   m  = m_x z + m_e eps;   z' = z_x z + z_m m + sum_k z_h[k] H[k] + z_n noise;   blend;   H[store] = m;   x_next = 16-bit(in_scale z')
+// The coefficients come from the parameter block or from 13 floats of device memory (a captured step replays with other
+// coefficients AND another history slot written, nothing in the graph changes).  History slot k is the float4 array
+// p.hist + k * B * HW; a slot with coefficient 0 is not read (the start-up steps of a multistep sampler cost no extra traffic), and
+// the slot being overwritten is read by the same thread first.
+// Algorithmic traffic per latent element: 3 fp32 reads + 1 fp32 write + 2 x 4 B of next-input writes, + 1 read per history term,
+// + 1 write with a store, + 1 read with noise, + 3 reads with the blend.
+template <bool F16>
+__global__ __launch_bounds__(256) void sampler_step_kernel(const SamplerParams p) {
+    const long total = (long)p.B * p.HW;                   // one thread per pixel (4 channels = 16 B)
+    float m_x = p.m_x, m_e = p.m_e, z_x = p.z_x, z_m = p.z_m, z_n = p.z_n, b_img = p.b_img, b_noise = p.b_noise, in_scale = p.in_scale;
+    float zh[4] = {p.z_h[0], p.z_h[1], p.z_h[2], p.z_h[3]};
+    int store = p.store;
+    if (p.coefs) {
+        m_x = p.coefs[0]; m_e = p.coefs[1]; z_x = p.coefs[2]; z_m = p.coefs[3];
+        zh[0] = p.coefs[4]; zh[1] = p.coefs[5]; zh[2] = p.coefs[6]; zh[3] = p.coefs[7];
+        z_n = p.coefs[8]; b_img = p.coefs[9]; b_noise = p.coefs[10]; in_scale = p.coefs[11];
+        store = (int)p.coefs[12];
+    }
+    if (store >= p.K) store = -1;                          // (device coefficients are not seen by the launcher: never past the buffer)
+    for (long i = blockIdx.x * 256L + threadIdx.x; i < total; i += (long)gridDim.x * 256L) {
+        const float4 z = reinterpret_cast<const float4*>(p.z)[i];
+        const float4 ec = reinterpret_cast<const float4*>(p.eps)[i];
+        const float4 eu = reinterpret_cast<const float4*>(p.eps)[i + total];
+        float zz[4] = {z.x, z.y, z.z, z.w};
+        const float g = p.guidance_rows ? p.guidance_rows[i / p.HW] : p.guidance;     // the latent row of this pixel
+        const float c[4] = {ec.x, ec.y, ec.z, ec.w};
+        const float u[4] = {eu.x, eu.y, eu.z, eu.w};
+        float hs[4][4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            float4 h = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (k < p.K && zh[k] != 0.f) h = reinterpret_cast<const float4*>(p.hist)[(long)k * total + i];
+            hs[k][0] = h.x; hs[k][1] = h.y; hs[k][2] = h.z; hs[k][3] = h.w;
+        }
+        float mk = 1.f;
+        float zi[4] = {0, 0, 0, 0}, nz[4] = {0, 0, 0, 0}, vn[4] = {0, 0, 0, 0};
+        if (p.noise) {
+            const float4 n = reinterpret_cast<const float4*>(p.noise)[i];
+            vn[0] = z_n * n.x; vn[1] = z_n * n.y; vn[2] = z_n * n.z; vn[3] = z_n * n.w;
+        }
+        if (p.mask) {
+            mk = p.mask[i];
+            const float4 a = reinterpret_cast<const float4*>(p.z_img)[i];
+            const float4 n = reinterpret_cast<const float4*>(p.blend_noise)[i];
+            zi[0] = a.x; zi[1] = a.y; zi[2] = a.z; zi[3] = a.w;
+            nz[0] = n.x; nz[1] = n.y; nz[2] = n.z; nz[3] = n.w;
+        }
+        float mm[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const float eps = u[e] + g * (c[e] - u[e]);
+            mm[e] = m_x * zz[e] + m_e * eps;
+            float zn = z_x * zz[e] + z_m * mm[e];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) zn += zh[k] * hs[k][e];
+            zn += vn[e];
+            if (p.mask) {
+                const float proper = b_img * zi[e] + b_noise * nz[e];
+                zn = (1.f - mk) * proper + mk * zn;
+            }
+            zz[e] = zn;
+        }
+        reinterpret_cast<float4*>(p.z)[i] = make_float4(zz[0], zz[1], zz[2], zz[3]);
+        if (store >= 0) reinterpret_cast<float4*>(p.hist)[(long)store * total + i] = make_float4(mm[0], mm[1], mm[2], mm[3]);
+        if (p.x_next) {
+            const uint4 o = make_uint4(El<F16>::pack2(in_scale * zz[0], in_scale * zz[1]), El<F16>::pack2(in_scale * zz[2], in_scale * zz[3]), 0u, 0u);
+            reinterpret_cast<uint4*>(p.x_next)[i] = o;
+            reinterpret_cast<uint4*>(p.x_next)[i + total] = o;
+        }
+    }
+}
+
 // diffusers Timesteps(dim, flip_sin_to_cos=True, downscale_freq_shift=0): [cos | sin]
 __global__ void timestep_embedding_kernel(const float* t, float* out, int B, int dim) {
     const int half = dim / 2;
@@ -229,6 +304,24 @@ int imd_launch_ddim_cfg_step(const DdimParams& p, hipStream_t s) { return launch
 int imd_launch_ddim_cfg_step_rows(const DdimParams& p, const float* guidance, hipStream_t s) {
     if (!guidance) return imd_set_error("ddim_cfg_step_rows: null guidance array");
     return launch_ddim_cfg_step(p, s, "ddim_cfg_step_rows", guidance);
+}
+
+int imd_launch_sampler_step(const SamplerParams& p, hipStream_t s) {
+    auto misaligned = [](const void* q, uintptr_t a) { return (reinterpret_cast<uintptr_t>(q) & (a - 1)) != 0; };
+    if (p.B <= 0 || p.HW <= 0) return imd_set_error("sampler_step: empty latent");
+    if (p.K < 0 || p.K > IMD_SAMPLER_MAX_HISTORY) return imd_set_error("sampler_step: K (%d) must be 0..%d history slots", p.K, IMD_SAMPLER_MAX_HISTORY);
+    if (p.K > 0 && !p.hist) return imd_set_error("sampler_step: K = %d history slots without a history buffer", p.K);
+    if (!p.coefs && (p.store < -1 || p.store >= p.K)) return imd_set_error("sampler_step: store slot %d outside -1..%d", p.store, p.K - 1);
+    if (p.mask && (!p.z_img || !p.blend_noise)) return imd_set_error("sampler_step: inpaint mask given without image latents / blend noise");
+    if (misaligned(p.z, 16) || misaligned(p.eps, 16) || misaligned(p.x_next, 16) || misaligned(p.hist, 16) || misaligned(p.noise, 16) ||
+        misaligned(p.z_img, 16) || misaligned(p.blend_noise, 16))
+        return imd_set_error("sampler_step: z, eps, x_next, hist, noise, z_img and blend_noise must be 16-byte aligned");
+    if (misaligned(p.mask, 4) || misaligned(p.guidance_rows, 4) || misaligned(p.coefs, 4))
+        return imd_set_error("sampler_step: mask, guidance_rows and coefs must be 4-byte aligned");
+    if (p.dtype == IMD_DTYPE_F16) hipLaunchKernelGGL(sampler_step_kernel<true>, dim3(grid_for((long)p.B * p.HW)), dim3(256), 0, s, p);
+    else if (p.dtype == IMD_DTYPE_BF16) hipLaunchKernelGGL(sampler_step_kernel<false>, dim3(grid_for((long)p.B * p.HW)), dim3(256), 0, s, p);
+    else return imd_set_error("sampler_step: unknown dtype %d", p.dtype);
+    return imd_check_launch("sampler_step");
 }
 
 int imd_launch_timestep_embedding(const float* t, float* out, int B, int dim, hipStream_t s) {

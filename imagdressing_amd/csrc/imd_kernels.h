@@ -13,6 +13,7 @@ typedef imd_attn_params AttnParams;
 typedef imd_groupnorm_params GroupNormParams;
 typedef imd_layernorm_params LayerNormParams;
 typedef imd_ddim_params DdimParams;
+typedef imd_sampler_params SamplerParams;
 
 enum { ACT_NONE = IMD_ACT_NONE, ACT_SILU = IMD_ACT_SILU, ACT_GEGLU = IMD_ACT_GEGLU, ACT_GELU = IMD_ACT_GELU, ACT_QUICK_GELU = IMD_ACT_QUICK_GELU };
 enum { OUT_ROWMAJOR = IMD_OUT_ROWMAJOR, OUT_HEADS = IMD_OUT_HEADS };
@@ -87,6 +88,7 @@ int imd_launch_layernorm(const LayerNormParams& p, hipStream_t s);
 int imd_launch_softmax_rows(const float* s_in, int s_ld, bf16_t* p_out, int p_ld, int rows, int cols, int dtype, hipStream_t s);
 int imd_launch_ddim_cfg_step(const DdimParams& p, hipStream_t s);
 int imd_launch_ddim_cfg_step_rows(const DdimParams& p, const float* guidance, hipStream_t s);
+int imd_launch_sampler_step(const SamplerParams& p, hipStream_t s);
 int imd_launch_timestep_embedding(const float* t, float* out, int B, int dim, hipStream_t s);
 int imd_launch_add(const bf16_t* a, int a_ld, const bf16_t* b, int b_ld, bf16_t* out, int out_ld, long rows, int C, float b_scale, int dtype, hipStream_t s);
 int imd_launch_embed_tokens(const bf16_t* table, int vocab, const bf16_t* pos, int T, const int64_t* ids, bf16_t* out, long rows, int C, int dtype, hipStream_t s);

@@ -50,6 +50,7 @@ class IMAGDressing_v1(PipelineBase):
             R, prompt, negative_prompt, prompt_embeds, negative_prompt_embeds, device, clip_skip)      # :395-405
         ref_lat, cloth_tokens, G = self._request_garments(R, null_prompt, ref_image, ref_image_latents, ref_clip_image,
                                                           ref_clip_hidden_states, device)              # :409-427, :454-458
+        self.scheduler.set_timesteps(num_inference_steps, device=device)      # (init_noise_sigma may depend on the schedule; IMAGDressing_v1_pipeline.py:386)
         lat = self.prepare_latents(R * num_images_per_prompt, 4, width, height, torch.float32, device, generator, latents)
         lat = self._shard(lat, shard_over_ranks)
         sa = self._sa_states(ref_lat, cloth_tokens, shard_over_ranks, G)                             # :465-480

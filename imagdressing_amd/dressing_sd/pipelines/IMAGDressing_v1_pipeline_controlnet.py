@@ -69,6 +69,7 @@ class IMAGDressing_v1(PipelineBase):
                                 size=(height, width))
         if control is not None:
             height, width = control["image"].shape[-2:]                     # :501
+        self.scheduler.set_timesteps(num_inference_steps, device=device)      # (init_noise_sigma may depend on the schedule; IMAGDressing_v1_pipeline.py:386)
         lat = self._shard(self.prepare_latents(R * num_images_per_prompt, 4, width, height, torch.float32, device, generator, latents),
                           shard_over_ranks)
         sa = self._sa_states(ref_lat, cloth_tokens, shard_over_ranks, G)

@@ -87,11 +87,11 @@ class IMAGDressing_v1(PipelineBase):
         if init_steps < 1:
             raise ValueError(f"After adjusting the num_inference_steps by strength parameter: {strength}, the number of pipeline "
                              f"steps is {init_steps} which is < 1 and not appropriate for this pipeline.")
+        self.scheduler.set_timesteps(num_inference_steps, device=device)
         if latents is not None or float(strength) == 1.0:
             lat = (noise if latents is None else latents).to(device=device, dtype=torch.float32) * self.scheduler.init_noise_sigma
         else:
-            self.scheduler.set_timesteps(num_inference_steps, device=device)
-            t0 = int(self.scheduler.timesteps[t_start * getattr(self.scheduler, "order", 1)])
+            t0 = self.scheduler.timesteps[t_start * getattr(self.scheduler, "order", 1)]          # (unrounded: Euler's may be fractional)
             il = image_latents.to(device=device, dtype=torch.float32)
             if il.shape[0] != B:                                              # one person image shared, or one per request (request-major rows)
                 il = il.expand(B, -1, -1, -1) if il.shape[0] == 1 else RequestLayout(R, num_images_per_prompt).expand(il, "image / image_latents")

@@ -145,6 +145,7 @@ class IMAGDressing_v1(PipelineBase):
             negative_prompt_embeds = torch.cat([negative_prompt_embeds.to(device), neg.to(negative_prompt_embeds.dtype)], dim=1)
         ref_lat, cloth_tokens, G = self._request_garments(R, null_prompt, ref_image, ref_image_latents, ref_clip_image,
                                                           ref_clip_hidden_states, device)
+        self.scheduler.set_timesteps(num_inference_steps, device=device)      # (init_noise_sigma may depend on the schedule; IMAGDressing_v1_pipeline.py:386)
         lat = self._shard(self.prepare_latents(R * num_images_per_prompt, 4, width, height, torch.float32, device, generator, latents),
                           shard_over_ranks)
         sa = self._sa_states(ref_lat, cloth_tokens, shard_over_ranks, G)

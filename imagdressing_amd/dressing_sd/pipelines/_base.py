@@ -102,9 +102,10 @@ class PipelineBase:
         return self
 
     def enable_step_graph(self, flag: bool = True):
-        """Opt in to HIP-graph replay of the DDIM denoising step (see ``denoise``): same kernels, same arithmetic, one graph launch
-        per step instead of ~500 kernel launches.  Worth it where the loop is host-bound (small batches); ignored for UniPC, step
-        callbacks, traces and per-step ControlNet gating."""
+        """Opt in to HIP-graph replay of the denoising step (see ``denoise``) -- DDIM and the deterministic samplers of the fused
+        sampler step (DPM-Solver++, Euler, PNDM): same kernels, same arithmetic, one graph launch per step instead of ~500 kernel
+        launches.  Worth it where the loop is host-bound (small batches); ignored for UniPC, Euler-ancestral, step callbacks, traces
+        and per-step ControlNet gating."""
         self._step_graph = bool(flag)
         if not flag:
             self.release_step_graph()
@@ -223,6 +224,9 @@ class PipelineBase:
         (carried in the ``sa_batch_mask`` rows; the processors' own ``scale`` is then expected to be 1).  ``control["image"]`` and
         the ``inpaint`` tensors hold 1, R or B rows.
 
+        The scheduler decides the step: DDIM (``imd_ddim_cfg_step``), a scheduler with a ``plan`` method -- DPM-Solver++, Euler,
+        Euler-ancestral, PNDM (scheduler.py) -- one ``imd_sampler_step`` per step with the same guidance / blend / graph-replay
+        features (Euler-ancestral draws its per-step noise like ``eta`` > 0 below and runs eagerly), or UniPC (``step_guided``).
         ``eta`` > 0 (DDIM only; other schedulers ignore it, like ``prepare_extra_step_kwargs``, IMAGDressing_v1_pipeline.py:102-119):
         the stochastic step, noise per step = ``variance_noise[i]`` [B, 4, h, w] or a draw of that shape in the UNet's element type
         from ``generator`` (what ``DDIMScheduler.step`` does with the reference's ``noise_pred``).
@@ -241,6 +245,7 @@ class PipelineBase:
             raise ValueError(f"{B} latent rows cannot be split into {requests} requests")
         gs = per_request_floats("guidance_scale", guidance_scale, lay.requests)
         multistep = hasattr(self.scheduler, "step_guided")        # UniPC: latent updates are host-computed linear combinations
+        fused = not multistep and hasattr(self.scheduler, "plan")  # DPM-Solver++ / Euler / Euler-ancestral / PNDM: one imd_sampler_step per step
         if len(set(gs)) > 1 and multistep:
             raise ValueError("guidance_scale differs between the requests: the per-request guidance step is the fused DDIM step; "
                              "UniPC takes one guidance scale per call")
@@ -249,13 +254,18 @@ class PipelineBase:
         g_arg = gs[0] if len(set(gs)) == 1 else lay.per_row(gs).to(dev)
         sch = self.scheduler
         sch.set_timesteps(num_inference_steps, device=dev)
-        timesteps = [int(t) for t in sch.timesteps][int(t_start) * getattr(sch, "order", 1):]
+        if fused:          # fractional timesteps (Euler, "linspace" spacing or Karras sigmas) reach the time embedding unrounded
+            timesteps = [t.item() for t in sch.timesteps][int(t_start):]
+        else:
+            timesteps = [int(t) for t in sch.timesteps][int(t_start) * getattr(sch, "order", 1):]
         if not timesteps:
             raise ValueError(f"no denoising steps left (num_inference_steps={num_inference_steps}, t_start={t_start})")
         z = latents.to(device=dev, dtype=torch.float32).permute(0, 2, 3, 1).reshape(B, HW, Cl).contiguous()
         dt = self.unet.dtype
         x_in = torch.zeros(2 * B, h, w, 8, dtype=dt, device=dev)
         x_in[..., :Cl] = torch.cat([z, z]).view(2 * B, h, w, Cl)
+        if fused and sch.input_scale(int(t_start)) != 1.0:          # scale_model_input of the first step; later inputs come scaled out of the step
+            x_in[..., :Cl] = (torch.cat([z, z]) * sch.input_scale(int(t_start))).view(2 * B, h, w, Cl)
         # rows [0,B): prompt (+garment), rows [B,2B): negative prompt, no garment -> ehs rows shared per half (R > 1: [R prompts; R negatives],
         # the processors' kv bdiv = n then maps cond row b to prompt b // n and uncond row B + j to negative j // n -- RequestLayout.ehs_row)
         ehs = lay.text_context(prompt_embeds, negative_prompt_embeds).to(device=dev, dtype=dt).contiguous()
@@ -281,12 +291,41 @@ class PipelineBase:
             inp = dict(mask=nhwc(inpaint["mask"], 1).view(B, HW).contiguous(), z_img=nhwc(inpaint["image_latents"], Cl),
                        noise=nhwc(inpaint["noise"], Cl))
         if multistep and inp is not None:
-            raise NotImplementedError("the inpainting blend is defined on the DDIM step (…inpainting.py:487-500)")
-        keeps = None if control is None else [control.get("keep", [1.0] * len(timesteps))[i] for i in range(len(timesteps))]
-        stochastic = float(eta) > 0.0 and not multistep
+            raise NotImplementedError("the inpainting blend is defined on the DDIM step (…inpainting.py:487-500)")       # (and on imd_sampler_step)
+        keep_in = None if control is None else control.get("keep", [1.0] * len(timesteps))
+        # (PNDM calls the UNet once more than it has steps: the extra call keeps the last gate)
+        keeps = None if control is None else [keep_in[min(i, len(keep_in) - 1) if fused else i] for i in range(len(timesteps))]
+        noisy = fused and sch.stochastic                          # Euler-ancestral: noise every step, whatever eta
+        stochastic = (float(eta) > 0.0 and not multistep and not fused) or noisy
         if variance_noise is not None and stochastic and len(variance_noise) < len(timesteps):
             raise ValueError(f"variance_noise has {len(variance_noise)} entries for {len(timesteps)} steps")
         ctrl_scale = 0.0 if control is None else float(control.get("scale", 1.0))
+
+        def step_noise(i):
+            vn = variance_noise[i] if variance_noise is not None else randn_tensor((B, Cl, h, w), generator=generator, device=dev, dtype=dt)
+            return vn.to(device=dev, dtype=torch.float32).permute(0, 2, 3, 1).reshape(B, HW, Cl).contiguous()
+
+        if fused:
+            # the history buffer [K][B HW 4] lives for the whole call at one address; which slot a step reads and writes is part of its
+            # coefficient row (scheduler.SamplerHistory), so the rows of the whole run are known before the first launch
+            from ...scheduler import SamplerHistory
+            hist = torch.zeros(sch.history, B, HW, Cl, dtype=torch.float32, device=dev) if sch.history else None
+            ring = SamplerHistory(sch.history)
+            sampler_rows = [ring.coefs(sch.plan(i, int(t_start), blend=inp is not None)) for i in range(len(timesteps))]
+
+        def sampler_step(t, i=None, coefs=None):
+            """ControlNet + UNet + ONE imd_sampler_step (CFG / update / history / noise / blend / next UNet input); ``t``, ``coefs`` as
+            for ``ddim_step`` (graph replay: the coefficient row, history slot included, is read from device memory)."""
+            down = mid = None
+            if control is not None:
+                down, mid = self.controlnet.forward_nhwc(x_in, t, ctrl_ehs, ctrl_img, ctrl_scale * (keeps[0] if i is None else keeps[i]))
+            eps = self.unet.forward_nhwc(x_in, t, ehs, cak, down, mid, cfg_pair=True)
+            kw = {}
+            if inp is not None:
+                kw = dict(mask=inp["mask"], z_img=inp["z_img"], blend_noise=inp["noise"])
+            if noisy:
+                kw["noise"] = step_noise(i)
+            ops.sampler_step(z, eps, x_in.view(2 * B, HW, 8), guidance=g_arg, coefs=sampler_rows[i] if coefs is None else coefs, hist=hist, **kw)
 
         def ddim_step(t, i=None, coefs=None):
             """ControlNet + UNet + CFG / DDIM / blend / next UNet input for one timestep; ``t`` a Python int (eager) or a device
@@ -304,8 +343,7 @@ class PipelineBase:
                 if inp is not None:
                     kw["a_next"] = sch.alpha(timesteps[i + 1]) if i < len(timesteps) - 1 else None
                 if stochastic:
-                    vn = variance_noise[i] if variance_noise is not None else randn_tensor((B, Cl, h, w), generator=generator, device=dev, dtype=dt)
-                    kw["var_noise"] = vn.to(device=dev, dtype=torch.float32).permute(0, 2, 3, 1).reshape(B, HW, Cl).contiguous()
+                    kw["var_noise"] = step_noise(i)
                     kw["sigma"] = sch.sigma(timesteps[i], eta)
                 ops.ddim_cfg_step(z, eps, x_in.view(2 * B, HW, 8), guidance=g_arg, a_t=sch.alpha(timesteps[i]),
                                   a_prev=sch.alpha_prev(timesteps[i]), **kw)
@@ -316,6 +354,8 @@ class PipelineBase:
         tables = [e.precompute_time_embeddings(timesteps, dev) for e in encs] if ops.TEMB_TABLE else []
         if not tables:
             encs = []
+
+        one_step = sampler_step if fused else ddim_step
 
         def run_steps():
             nonlocal z
@@ -328,13 +368,14 @@ class PipelineBase:
                 # replayed for steps 1 .. S-1: ~500 kernel launches per step become one hipGraphLaunch (the loop is host-bound at batch 1).
                 steps_n = len(timesteps)
                 t_table = torch.tensor(timesteps, dtype=torch.float32).to(dev)
-                rows = []
-                for i, t in enumerate(timesteps):
-                    a_next = (sch.alpha(timesteps[i + 1]) if i < steps_n - 1 else None) if inp is not None else None
-                    rows.append(ops.ddim_coefs(sch.alpha(t), sch.alpha_prev(t), a_next))
+                rows = sampler_rows if fused else []          # (fused samplers: 13 values per step, history slots included)
+                if not fused:
+                    for i, t in enumerate(timesteps):
+                        a_next = (sch.alpha(timesteps[i + 1]) if i < steps_n - 1 else None) if inp is not None else None
+                        rows.append(ops.ddim_coefs(sch.alpha(t), sch.alpha_prev(t), a_next))
                 coef_table = torch.tensor(rows, dtype=torch.float32).to(dev)
                 t_dev = torch.zeros(1, dtype=torch.float32, device=dev)
-                coef_dev = torch.zeros(6, dtype=torch.float32, device=dev)
+                coef_dev = torch.zeros(coef_table.shape[1], dtype=torch.float32, device=dev)
                 side = self.__dict__.get("_graph_stream")
                 if side is None:
                     side = self._graph_stream = torch.cuda.Stream(device=dev)
@@ -346,11 +387,11 @@ class PipelineBase:
                     for e, buf, tab in zip(encs, temb_bufs, tables):
                         buf.copy_(tab[0:1])
                         e.use_time_embedding(buf)
-                    ddim_step(t_dev, coefs=coef_dev)
+                    one_step(t_dev, coefs=coef_dev)
                     g = torch.cuda.CUDAGraph()
                     g.capture_begin()
                     try:
-                        ddim_step(t_dev, coefs=coef_dev)
+                        one_step(t_dev, coefs=coef_dev)
                     finally:
                         g.capture_end()
                     for i in range(1, steps_n):
@@ -372,7 +413,7 @@ class PipelineBase:
                     ops.ddim_cfg_step(z, ops.workspace("zero_eps", (2 * B, HW, Cl), torch.float32, dev), x_in.view(2 * B, HW, 8),
                                       guidance=1.0, a_t=1.0, a_prev=1.0)
                 else:
-                    ddim_step(t, i)
+                    one_step(t, i)
                 if trace is not None:
                     trace.append(z.clone())
                 if callback is not None and i % callback_steps == 0:

@@ -276,6 +276,40 @@ typedef struct imd_ddim_params {
     float sigma;          /* eta * sqrt((1 - a_prev) / (1 - a_t) * (1 - a_t / a_prev)); read only with var_noise */
 } imd_ddim_params;
 
+/* One step of an affine sampler (imd_sampler_step) over the [B, HW, 4] latent, per element in fp32:
+ *   e  = eps_u + g (eps_c - eps_u)                         g = guidance, or guidance_rows[row]
+ *   m  = m_x z + m_e e                                     the quantity the sampler keeps a history of (x0 prediction, or e itself)
+ *   z' = z_x z + z_m m + sum_{k < K} z_h[k] hist[k] + z_n noise
+ *   z' = (1 - mask) (b_img z_img + b_noise blend_noise) + mask z'            (with mask)
+ *   z <- z';  hist[store] <- m (store >= 0);  x_next[both CFG halves] <- 16-bit(in_scale z'), channels 4..7 = 0
+ * DPM-Solver++ (1 / 2M), Euler, Euler-ancestral and PNDM/PLMS differ in the host-computed coefficients only
+ * (imagdressing_amd/scheduler.py). */
+#define IMD_SAMPLER_MAX_HISTORY 4
+#define IMD_SAMPLER_COEFS 13     /* floats of the device coefficient block: m_x, m_e, z_x, z_m, z_h[4], z_n, b_img, b_noise, in_scale, store */
+typedef struct imd_sampler_params {
+    uint32_t struct_bytes; /* sizeof(imd_sampler_params) in the caller's view; checked on entry */
+    float* z;             /* [B, HW, 4] fp32 latent state, updated in place */
+    const float* eps;     /* [2B, HW, 4] fp32: rows [0,B) cond pass, [B,2B) uncond pass */
+    uint16_t* x_next;     /* [2B, HW, 8] 16-bit next UNet input (channels 4..7 = 0) or NULL */
+    float* hist;          /* [K][B HW 4] fp32, ONE contiguous buffer owned by the caller (NULL iff K == 0).  A slot may be read and
+                           * overwritten by the same launch: every thread reads its element of each slot before it stores */
+    int B, HW, K;         /* K: history slots, 0..IMD_SAMPLER_MAX_HISTORY */
+    int dtype;            /* element type of x_next */
+    float guidance;
+    const float* guidance_rows; /* NULL, or DEVICE [B] fp32: the guidance scale of each latent row, read instead of `guidance` */
+    float m_x, m_e, z_x, z_m;
+    float z_h[4];         /* by PHYSICAL slot; a slot whose coefficient is 0 is not read */
+    float z_n, b_img, b_noise, in_scale;
+    int store;            /* physical slot that receives m, -1: none */
+    const float* noise;   /* NULL, or [B, HW, 4] fp32 standard-normal noise of a stochastic step (scaled by z_n, added before the blend) */
+    const float* mask;    /* NULL, or [B, HW] inpaint mask; then z_img and blend_noise [B, HW, 4] are required */
+    const float* z_img;
+    const float* blend_noise;
+    const float* coefs;   /* NULL, or DEVICE pointer to IMD_SAMPLER_COEFS fp32 read by the kernel INSTEAD of m_x .. store above (store as
+                           * a float holding the integer; a value outside -1..K-1 stores nothing): a captured HIP graph of a step then
+                           * holds no pointer or scalar that changes between replays -- the host refreshes 52 bytes per step */
+} imd_sampler_params;
+
 /* library / device */
 int imd_abi_version(void);
 const char* imd_last_error(void);
@@ -432,6 +466,13 @@ int imd_ddim_cfg_step(const imd_ddim_params* p, void* stream);
  * as imd_ddim_cfg_step.  One call then serves a batch of requests with different guidance scales (the pipelines'
  * request-batched call).  With every entry equal to g it is bit-identical to imd_ddim_cfg_step with guidance = g. */
 int imd_ddim_cfg_step_rows(const imd_ddim_params* p, const float* guidance, void* stream);
+/* CFG combine + one step of an affine sampler (+ history update, noise, inpaint blend) + next UNet input as ONE launch; see
+ * imd_sampler_params.  Replaces `scheduler.step` of diffusers' DPMSolverMultistepScheduler / EulerDiscreteScheduler /
+ * EulerAncestralDiscreteScheduler / PNDMScheduler at the call site IMAGDressing_v1_pipeline.py:530-532 (the pipelines take any
+ * KarrasDiffusionSchedulers member, ..._pipeline_controlnet.py:36-41).  Errors without launching: K outside 0..4, store outside
+ * -1..K-1 (host coefficients), a mask without z_img / blend_noise, K > 0 without hist, misaligned pointers (16 bytes for the
+ * float4 / uint4 tensors, 4 for mask, guidance_rows and coefs). */
+int imd_sampler_step(const imd_sampler_params* p, void* stream);
 
 /* diffusers Timesteps(dim, flip_sin_to_cos=True, freq_shift=0): out[B, dim] fp32 = [cos | sin]. */
 int imd_timestep_embedding(const float* t, float* out, int B, int dim, void* stream);

@@ -138,6 +138,35 @@ def check_schedulers(diffusers, results):
             z = orcu.step(eps, t, z)
             zl = libu.step(eps, libu.timesteps[i], zl).prev_sample
         report(f"UniPCMultistepScheduler {n}-step trajectory", z, zl, 1e-6, results)
+    # the samplers on the fused step: tests/sampler_oracle.py (library-form restatements, what imagdressing_amd/scheduler.py is tested against).
+    # The DPM-Solver++ restatement ends at sigma = 0, the 0.24 library at the sigma of training timestep 0: its last step is expected to differ.
+    from tests import sampler_oracle as SO
+    for cls, orc_cls, lib_kw, orc_kw in (
+            ("DPMSolverMultistepScheduler", SO.DPMSolverOracle, {}, {}),
+            ("DPMSolverMultistepScheduler", SO.DPMSolverOracle, dict(use_karras_sigmas=True), dict(use_karras_sigmas=True)),
+            ("EulerDiscreteScheduler", SO.EulerOracle, {}, {}),
+            ("EulerDiscreteScheduler", SO.EulerOracle, dict(timestep_spacing="leading", steps_offset=1), dict(timestep_spacing="leading", steps_offset=1)),
+            ("EulerAncestralDiscreteScheduler", SO.EulerAncestralOracle, {}, {}),
+            ("PNDMScheduler", SO.PNDMOracle, dict(skip_prk_steps=True, steps_offset=1), {})):
+        libs = getattr(diffusers, cls)(**kw, **lib_kw)
+        orcs = orc_cls(**orc_kw)
+        tag = cls + (f" {lib_kw}" if lib_kw else "")
+        for n in (10, 25):
+            libs.set_timesteps(n)
+            ts = orcs.set_timesteps(n)
+            report(f"{tag}.timesteps ({n} steps)", ts.double(), libs.timesteps.double().cpu(), 1e-3, results)
+            if hasattr(orcs, "sigmas") and hasattr(libs, "sigmas"):
+                report(f"{tag}.sigmas ({n} steps, without the final one)", torch.as_tensor(orcs.sigmas[:-1]).double(), libs.sigmas[:-1].double().cpu(), 1e-6, results)
+            if cls == "EulerAncestralDiscreteScheduler":
+                continue          # the library draws the per-step noise itself: schedule and sigmas only (the step shares EulerOracle's arithmetic)
+            z = rnd(9, 1, 4, 8, 8).double() * orcs.init_noise_sigma
+            zl = z.clone()
+            last = len(ts) - (1 if cls == "DPMSolverMultistepScheduler" else 0)
+            for i, t in enumerate(ts[:last]):
+                eps = rnd(300 + i, 1, 4, 8, 8).double()
+                z = orcs.step(eps, t, z)
+                zl = libs.step(eps, libs.timesteps[i], zl).prev_sample
+            report(f"{tag} {n}-step trajectory" + (" (all but the last step)" if last < len(ts) else ""), z, zl, 1e-6, results)
 
 
 def main():
@@ -146,7 +175,7 @@ def main():
     a = ap.parse_args()
     diffusers, ver = find_diffusers()
     if diffusers is None:
-        print(f"diffusers absent ({ver}) -- oracle/sd15.py, oracle/vae.py, oracle/ddim.py, oracle/unipc.py stay UNPINNED "
+        print(f"diffusers absent ({ver}) -- oracle/sd15.py, oracle/vae.py, oracle/ddim.py, oracle/unipc.py and tests/sampler_oracle.py stay UNPINNED "
               "(anchored on parameter counts, key names and schedule values only).  Install diffusers==0.24.0 to run this check.")
         return 0
     print(f"diffusers {ver} found at {os.path.dirname(diffusers.__file__)}")
