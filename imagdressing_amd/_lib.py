@@ -119,6 +119,23 @@ class SamplerParams(_Sized):
     ]
 
 
+class ImageResampleParams(_Sized):
+    _fields_ = [("struct_bytes", C.c_uint32),
+        ("src", C.c_void_p), ("src_row_stride", C.c_int64), ("src_img_stride", C.c_int64), ("out", C.c_void_p), ("tmp", C.c_void_p),
+        ("B", C.c_int), ("Hin", C.c_int), ("Win", C.c_int), ("C", C.c_int), ("Hres", C.c_int), ("Wres", C.c_int),
+        ("h_xmin", C.c_void_p), ("h_count", C.c_void_p), ("h_k", C.c_void_p), ("h_kmax", C.c_int), ("h_taps", C.c_int),
+        ("v_xmin", C.c_void_p), ("v_count", C.c_void_p), ("v_k", C.c_void_p), ("v_kmax", C.c_int), ("v_taps", C.c_int),
+        ("v_tile_rows", C.c_int), ("top", C.c_int), ("left", C.c_int), ("crop_h", C.c_int), ("crop_w", C.c_int),
+        ("kind", C.c_int), ("dtype", C.c_int), ("binarize", C.c_int), ("flags", C.c_int),
+        ("a", C.c_float * 3), ("b", C.c_float * 3),
+    ]
+
+
+class ImagePackParams(_Sized):
+    _fields_ = [("struct_bytes", C.c_uint32), ("src", C.c_void_p), ("out", C.c_void_p),
+                ("B", C.c_int), ("H", C.c_int), ("W", C.c_int), ("ld", C.c_int), ("dtype", C.c_int)]
+
+
 # every symbol include/imagdressing_hip.h declares: name -> (restype, argtypes)
 SYMBOLS = {
     "imd_abi_version": (C.c_int, []),
@@ -160,6 +177,9 @@ SYMBOLS = {
     "imd_ddim_cfg_step": (C.c_int, [C.POINTER(DdimParams), C.c_void_p]),
     "imd_ddim_cfg_step_rows": (C.c_int, [C.POINTER(DdimParams), C.c_void_p, C.c_void_p]),
     "imd_sampler_step": (C.c_int, [C.POINTER(SamplerParams), C.c_void_p]),
+    "imd_image_resample": (C.c_int, [C.POINTER(ImageResampleParams), C.c_void_p]),
+    "imd_image_resample_form": (C.c_int, [C.POINTER(ImageResampleParams)]),
+    "imd_image_pack_u8": (C.c_int, [C.POINTER(ImagePackParams), C.c_void_p]),
     "imd_timestep_embedding": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "imd_add": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_long, C.c_int, C.c_float, C.c_int, C.c_void_p]),
     "imd_embed_tokens": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_long, C.c_int, C.c_int, C.c_void_p]),

@@ -293,6 +293,23 @@ int imd_sampler_step(const imd_sampler_params* p, void* stream) {
     return imd_launch_sampler_step(*p, (hipStream_t)stream);
 }
 
+int imd_image_resample(const imd_image_resample_params* p, void* stream) {
+    IMD_REQUIRE(p != nullptr, "image_resample: null params");
+    IMD_REQUIRE_SIZE(p, "image_resample");
+    return imd_launch_image_resample(*p, (hipStream_t)stream);
+}
+
+int imd_image_resample_form(const imd_image_resample_params* p) {
+    if (!p || p->struct_bytes != sizeof(*p)) return 0;
+    return imd_image_resample_form_of(*p);
+}
+
+int imd_image_pack_u8(const imd_image_pack_params* p, void* stream) {
+    IMD_REQUIRE(p != nullptr, "image_pack_u8: null params");
+    IMD_REQUIRE_SIZE(p, "image_pack_u8");
+    return imd_launch_image_pack_u8(*p, (hipStream_t)stream);
+}
+
 int imd_ddim_cfg_step_rows(const imd_ddim_params* p, const float* guidance, void* stream) {
     IMD_REQUIRE(p != nullptr, "ddim_cfg_step_rows: null params");
     IMD_REQUIRE_SIZE(p, "ddim_cfg_step_rows");

@@ -6,8 +6,7 @@ from typing import Any, Callable, Dict, List, Optional, Union
 
 import torch
 
-from ._base import (PipelineBase, RefSAttnProcessor2_0, as_batch, controlnet_keep, first, min_guidance, per_call_value, set_scale_by_type,
-                    to_image_tensor)
+from ._base import (PipelineBase, RefSAttnProcessor2_0, as_batch, controlnet_keep, first, min_guidance, per_call_value, set_scale_by_type)
 
 
 class IMAGDressing_v1(PipelineBase):
@@ -27,8 +26,8 @@ class IMAGDressing_v1(PipelineBase):
         (``prompt_embeds_control``, ..._ipa_controlnet.py:550)."""
         if pose_image is None:
             return None
-        return dict(image=to_image_tensor(pose_image, device, normalize=False, size=size, multiple=self.vae_scale_factor),
-                    prompt_embeds=prompt_embeds,
+        image, hw = self._image_tensor(pose_image, device, normalize=False, size=size, multiple=self.vae_scale_factor, layout="nhwc8")
+        return dict(image=image, hw=hw, prompt_embeds=prompt_embeds,
                     negative_prompt_embeds=negative_prompt_embeds, scale=float(first(scale)),
                     keep=controlnet_keep(num_inference_steps, float(first(start)), float(first(end))))
 
@@ -68,7 +67,7 @@ class IMAGDressing_v1(PipelineBase):
                                 controlnet_conditioning_scale, control_guidance_start, control_guidance_end, device,
                                 size=(height, width))
         if control is not None:
-            height, width = control["image"].shape[-2:]                     # :501
+            height, width = control["hw"]                                   # :501
         self.scheduler.set_timesteps(num_inference_steps, device=device)      # (init_noise_sigma may depend on the schedule; IMAGDressing_v1_pipeline.py:386)
         lat = self._shard(self.prepare_latents(R * num_images_per_prompt, 4, width, height, torch.float32, device, generator, latents),
                           shard_over_ranks)

@@ -7,7 +7,7 @@ from typing import Any, Callable, Dict, List, Optional, Union
 import torch
 
 from ._base import (PipelineBase, RefSAttnProcessor2_0, RequestLayout, as_batch, controlnet_keep, first, min_guidance, per_call_value,
-                    randn_tensor, set_scale_by_type, to_image_tensor)
+                    randn_tensor, set_scale_by_type)
 
 
 class IMAGDressing_v1(PipelineBase):
@@ -25,7 +25,7 @@ class IMAGDressing_v1(PipelineBase):
     def _image_latents(self, image, device, generator, size=None):
         """VAE-encode the person image (inherited ``prepare_latents(..., return_image_latents=True)``, :330-346)."""
         p = next(self.vae.parameters())
-        x = to_image_tensor(image, p.device, normalize=True, size=size, multiple=self.vae_scale_factor).to(p.dtype)
+        x = self._image_tensor(image, p.device, normalize=True, size=size, multiple=self.vae_scale_factor)[0].to(p.dtype)
         return self.vae.encode(x).latent_dist.sample(generator) * self.vae.config.scaling_factor
 
     @torch.no_grad()
@@ -68,8 +68,8 @@ class IMAGDressing_v1(PipelineBase):
         ref_lat, cloth_tokens, G = self._request_garments(R, null_prompt, ref_image, ref_image_latents, ref_clip_image,
                                                           ref_clip_hidden_states, device)
         steps_run = min(int(num_inference_steps * float(strength)), num_inference_steps)          # the gate is over the timesteps actually run (:376-381)
-        control = dict(image=to_image_tensor(as_batch(control_image, "control_image"), device, normalize=False, size=(height, width),
-                                             multiple=self.vae_scale_factor),
+        control = dict(image=self._image_tensor(as_batch(control_image, "control_image"), device, normalize=False, size=(height, width),
+                                                multiple=self.vae_scale_factor, layout="nhwc8")[0],
                        prompt_embeds=prompt_embeds,
                        negative_prompt_embeds=negative_prompt_embeds, scale=float(first(controlnet_conditioning_scale)),
                        keep=controlnet_keep(max(steps_run, 1), float(first(control_guidance_start)), float(first(control_guidance_end))))
@@ -97,7 +97,7 @@ class IMAGDressing_v1(PipelineBase):
                 il = il.expand(B, -1, -1, -1) if il.shape[0] == 1 else RequestLayout(R, num_images_per_prompt).expand(il, "image / image_latents")
             lat = self.scheduler.add_noise(il, noise.to(device=device, dtype=torch.float32), t0)
         if mask_latents is None:                                              # prepare_mask_latents: nearest resize to h x w
-            m = to_image_tensor(as_batch(mask_image, "mask_image"), device, normalize=False)[:, :1]
+            m = self._image_tensor(as_batch(mask_image, "mask_image"), device, normalize=False, binarize=True)[0][:, :1]
             m = (m >= 0.5).float()
             mask_latents = torch.nn.functional.interpolate(m, size=(h, w))
         lat, noise_s = self._shard(lat, shard_over_ranks), self._shard(noise.to(device), shard_over_ranks)

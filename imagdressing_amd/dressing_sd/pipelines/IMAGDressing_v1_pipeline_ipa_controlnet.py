@@ -9,7 +9,7 @@ import torch
 
 from ...adapter.resampler import ProjPlusModel
 from ._base import (IPAttnProcessor2_0, LoRAIPAttnProcessor2_0, LoraRefSAttnProcessor2_0, PipelineBase, as_batch, controlnet_keep, first,
-                    min_guidance, per_call_value, request_rows, set_scale_by_type, to_image_tensor)
+                    min_guidance, per_call_value, request_rows, set_scale_by_type)
 
 
 def _faces(name, value):
@@ -130,13 +130,12 @@ class IMAGDressing_v1(PipelineBase):
             R, prompt, negative_prompt, prompt_embeds, negative_prompt_embeds, device, clip_skip)
         control = None
         if pose_image is not None:                                            # ControlNet sees the 77 text tokens only (:550)
-            control = dict(image=to_image_tensor(as_batch(pose_image, "pose_image"), device, normalize=False, size=(height, width),
-                                                 multiple=self.vae_scale_factor),
-                           prompt_embeds=prompt_embeds,
+            image, (height, width) = self._image_tensor(as_batch(pose_image, "pose_image"), device, normalize=False, size=(height, width),
+                                                        multiple=self.vae_scale_factor, layout="nhwc8")
+            control = dict(image=image, prompt_embeds=prompt_embeds,
                            negative_prompt_embeds=negative_prompt_embeds, scale=float(first(controlnet_conditioning_scale)),
                            keep=controlnet_keep(num_inference_steps, float(first(control_guidance_start)),
                                                 float(first(control_guidance_end))))
-            height, width = control["image"].shape[-2:]
         if has_face:                                                          # :513-521, :555-557
             pos, neg = self.get_image_embeds(face_clip_image, faceid_embeds, face_clip_hidden_states, face_uncond_clip_hidden_states)
             if R > 1:                                                         # one face per request (or one shared by all)

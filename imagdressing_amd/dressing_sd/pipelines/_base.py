@@ -127,6 +127,48 @@ class PipelineBase:
         except Exception:        # noqa: BLE001  (interpreter shutdown)
             pass
 
+    def enable_device_image_io(self, flag: bool = True):
+        """Opt in to image input and output on the GPU (``imagdressing_amd.image.DeviceImageProcessor``): PIL / uint8 pose, control,
+        inpainting and mask images are resized (Pillow's Lanczos filter, bit for bit), scaled and laid out by ``imd_image_resample``
+        instead of on one host thread, and ``output_type="pil" | "np"`` packs the decoder's NHWC output to uint8 on the device and copies
+        one byte per channel value back instead of four.  No pixel changes; float tensor inputs and ``"pt"`` / ``"latent"`` outputs keep
+        the host route.  Off by default."""
+        self._device_image_io = bool(flag)
+        return self
+
+    def disable_device_image_io(self):
+        return self.enable_device_image_io(False)
+
+    def _image_processor(self):
+        from ...image import DeviceImageProcessor
+        proc = self.__dict__.get("_image_proc")
+        if proc is None or proc.device != self.device or proc.dtype != self.unet.dtype:
+            proc = self._image_proc = DeviceImageProcessor(self.device, self.unet.dtype)
+        return proc
+
+    def _image_tensor(self, image, device, normalize: bool, size=None, multiple: int = 8, layout: str = "nchw", binarize: bool = False):
+        """-> (tensor, (height, width)).  ``to_image_tensor`` (fp32 NCHW) -- or, with device image I/O enabled and PIL / uint8 images
+        that need no nearest-neighbour resize, the same values from the GPU: ``layout="nchw"`` fp32 [B, 3 | 1, H, W]; ``"nhwc8"``: the
+        engines' [B, H, W, 8] (what ``nchw_to_nhwc8`` makes of it).  The size is returned beside the tensor because the two layouts
+        keep it in different places.  ``binarize`` (masks) thresholds at 0.5 on the device; the host route leaves that to the caller."""
+        if getattr(self, "_device_image_io", False) and torch.device(device).type == "cuda":
+            ims = list(image) if isinstance(image, (list, tuple)) else [image]
+            hw = None if size is None else (int(size[0]) // multiple * multiple, int(size[1]) // multiple * multiple)
+
+            def on_device(im):
+                if hasattr(im, "convert") and hasattr(im, "resize"):
+                    return True                # PIL: Lanczos to ``hw``, as the host route
+                # uint8 [H, W, 3] arrays: the host route resizes those with F.interpolate (nearest) -- only unresized ones come here
+                return (not isinstance(im, torch.Tensor) and getattr(im, "dtype", None) == "uint8" and getattr(im, "ndim", 0) == 3
+                        and im.shape[-1] == 3 and (hw is None or tuple(im.shape[:2]) == hw))
+            if ims and all(on_device(im) for im in ims):
+                gray = binarize and all(getattr(im, "mode", None) in ("1", "L") for im in ims)     # (their RGB conversion repeats the one channel)
+                t = self._image_processor().preprocess(ims, size=size, resample="lanczos", out=layout, normalize=normalize,
+                                                       binarize=binarize, multiple=multiple, mode="L" if gray else "RGB")
+                return t, (tuple(t.shape[1:3]) if layout == "nhwc8" else tuple(t.shape[-2:]))
+        t = to_image_tensor(image, device, normalize, size=size, multiple=multiple)
+        return t, tuple(t.shape[-2:])
+
     def enable_vae_slicing(self):
         self.vae.enable_slicing()
 
@@ -478,6 +520,15 @@ class PipelineBase:
         if output_type == "latent":
             return StableDiffusionPipelineOutput(images=latents, nsfw_content_detected=None)
         p = next(self.vae.parameters())
+        if getattr(self, "_device_image_io", False) and output_type in ("np", "pil"):
+            if not hasattr(self.vae, "decode_nhwc"):
+                raise TypeError("enable_device_image_io() needs the engine VAE (imagdressing_amd.vae.AutoencoderKL.decode_nhwc), got "
+                                f"{type(self.vae).__module__}.{type(self.vae).__name__}")
+            z = (latents / self.vae.config.scaling_factor).to(p.dtype)
+            ops.ensure_device(z.device)
+            slices = z.split(1) if getattr(self.vae, "use_slicing", False) and z.shape[0] > 1 else (z,)
+            ys = [self.vae.decode_nhwc(nchw_to_nhwc8(zb.float(), self.vae.dtype)) for zb in slices]       # (AutoencoderKL.decode, without its NCHW copy)
+            return StableDiffusionPipelineOutput(images=self._image_processor().postprocess(ys, output_type), nsfw_content_detected=None)
         image = self.vae.decode((latents / self.vae.config.scaling_factor).to(p.dtype), return_dict=False)[0]
         image = (image.float() / 2 + 0.5).clamp(0, 1)
         if output_type == "pt":

@@ -1,0 +1,288 @@
+"""Image pre- and post-processing on the device, bit-exact with Pillow.
+
+Pillow's 8-bit resampler (libImaging/Resample.c) is integer arithmetic once its coefficient table exists: per axis
+``out = clip8((2^21 + sum_j in[xmin + j] * k[j]) >> 22)``, horizontal pass first, the vertical pass over the uint8 result of the
+horizontal one.  ``resample_tables`` builds the table in float64 exactly as Pillow does; ``imd_image_resample`` (csrc/image.hip)
+applies it on the GPU and fuses what follows the resize on the host today -- crop, /255, normalisation, the NCHW / NHWC8 layout.
+``resample_reference`` is the same integer formula in numpy (tests, tools/make_image_goldens.py).
+
+``DeviceImageProcessor`` is what the pipelines use after ``enable_device_image_io()``: the only host work left per image is
+``convert("RGB" | "L")``, one copy of the uint8 pixels into pinned memory and their upload; the decoder's output comes back as ONE uint8 copy instead of fp32 NCHW.
+"""
+from __future__ import annotations
+
+import collections
+import functools
+import math
+from typing import List, Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+
+from . import ops
+
+PRECISION_BITS = 22                      # 32 - 8 - 2: Pillow's fixed-point fraction of an 8-bit channel
+FILTER_SUPPORT = {"bilinear": 1.0, "bicubic": 2.0, "lanczos": 3.0}
+CLIP_MEAN = (0.48145466, 0.4578275, 0.40821073)
+CLIP_STD = (0.26862954, 0.26130258, 0.27577711)
+
+
+def _bilinear(x: float) -> float:
+    x = abs(x)
+    return 1.0 - x if x < 1.0 else 0.0
+
+
+def _bicubic(x: float) -> float:           # Keys' cubic, a = -0.5
+    a = -0.5
+    x = abs(x)
+    if x < 1.0:
+        return ((a + 2.0) * x - (a + 3.0)) * x * x + 1
+    if x < 2.0:
+        return (((x - 5) * x + 8) * x - 4) * a
+    return 0.0
+
+
+def _sinc(x: float) -> float:
+    if x == 0.0:
+        return 1.0
+    x = x * math.pi
+    return math.sin(x) / x
+
+
+def _lanczos(x: float) -> float:           # sinc(x) sinc(x / 3) on [-3, 3)
+    return _sinc(x) * _sinc(x / 3) if -3.0 <= x < 3.0 else 0.0
+
+
+_FILTERS = {"bilinear": _bilinear, "bicubic": _bicubic, "lanczos": _lanczos}
+
+
+@functools.lru_cache(maxsize=256)
+def _tables(n_in: int, n_out: int, filter: str):
+    f, S = _FILTERS[filter], FILTER_SUPPORT[filter]
+    scale = n_in / n_out
+    fs = max(scale, 1.0)
+    support = S * fs
+    kmax = int(math.ceil(support)) * 2 + 1
+    inv = 1.0 / fs
+    xmin = np.zeros(n_out, np.int32)
+    count = np.zeros(n_out, np.int32)
+    k = np.zeros((n_out, kmax), np.int32)
+    for i in range(n_out):
+        c = (i + 0.5) * scale
+        lo = max(0, int(c - support + 0.5))
+        hi = min(n_in, int(c + support + 0.5))
+        w = [f((j + lo - c + 0.5) * inv) for j in range(hi - lo)]
+        ww = 0.0
+        for v in w:                          # (summed in tap order, as the C loop does)
+            ww += v
+        if ww != 0.0:
+            w = [v / ww for v in w]
+        xmin[i], count[i] = lo, hi - lo
+        for j, v in enumerate(w):
+            k[i, j] = int(v * (1 << PRECISION_BITS) + 0.5) if v >= 0 else int(v * (1 << PRECISION_BITS) - 0.5)
+    for a in (xmin, count, k):
+        a.setflags(write=False)
+    return xmin, count, k
+
+
+def resample_tables(n_in: int, n_out: int, filter: str = "lanczos") -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """(xmin[n_out], count[n_out], k[n_out][kmax]) int32: the window of source samples each output reads and their fixed-point weights
+    (22 fraction bits, rows zero-padded to kmax = 2 ceil(support) + 1), computed in float64 as Pillow's precompute_coeffs /
+    normalize_coeffs_8bpc do.  sum |k| * 255 < 2^31 for the three filters, so an int32 accumulator holds the pass.  Cached."""
+    if filter not in _FILTERS:
+        raise ValueError(f"resample filter must be one of {sorted(_FILTERS)}, got {filter!r}")
+    if n_in < 1 or n_out < 1:
+        raise ValueError(f"resample_tables: sizes must be positive, got {n_in} -> {n_out}")
+    return _tables(int(n_in), int(n_out), filter)
+
+
+def _pass(a: np.ndarray, table, axis: int) -> np.ndarray:
+    xmin, count, k = table
+    a = np.moveaxis(a.astype(np.int32), axis, 0)
+    out = np.empty((len(xmin),) + a.shape[1:], np.uint8)
+    for i in range(len(xmin)):
+        n = int(count[i])
+        acc = np.tensordot(k[i, :n], a[xmin[i]:xmin[i] + n], axes=(0, 0)).astype(np.int32) + (1 << (PRECISION_BITS - 1))
+        out[i] = np.clip(acc >> PRECISION_BITS, 0, 255)
+    return np.moveaxis(out, 0, axis)
+
+
+def resample_reference(arr: np.ndarray, size: Tuple[int, int], filter: str = "lanczos") -> np.ndarray:
+    """``Image.resize`` of uint8 [..., H, W, C] to ``size`` = (height, width) by the integer formula, in numpy: horizontal pass, then the
+    vertical pass over its uint8 result; an axis whose size does not change is skipped."""
+    arr = np.asarray(arr)
+    if arr.dtype != np.uint8 or arr.ndim < 3:
+        raise ValueError("resample_reference: uint8 [..., H, W, C] expected")
+    H, W = arr.shape[-3], arr.shape[-2]
+    if W != size[1]:
+        arr = _pass(arr, resample_tables(W, size[1], filter), arr.ndim - 2)
+    if H != size[0]:
+        arr = _pass(arr, resample_tables(H, size[0], filter), arr.ndim - 3)
+    return arr
+
+
+def tile_rows(table, top: int, rows: int, tile_h: int = ops.IMAGE_TILE_H) -> int:
+    """Most source rows that one tile of ``tile_h`` output rows reads, over the tiles of output rows [top, top + rows)"""
+    xmin, count, _ = table
+    lo = xmin[top:top + rows].astype(np.int64)
+    hi = lo + count[top:top + rows]
+    starts = range(0, rows, tile_h)
+    return int(max(hi[s:s + tile_h].max() - lo[s:s + tile_h].min() for s in starts))
+
+
+_dev_tables = collections.OrderedDict()     # least recently used first
+DEVICE_TABLES_MAX = 64                      # entries kept (a table is n_out * (kmax + 2) int32): bounded like the host cache
+
+
+def device_tables(n_in: int, n_out: int, filter: str, device) -> dict:
+    """The table of one axis on ``device`` (uploaded once per (n_in, n_out, filter, device)) with its host copy"""
+    device = torch.device(device)
+    key = (n_in, n_out, filter, device.type, device.index)
+    t = _dev_tables.get(key)
+    if t is None:
+        xmin, count, k = resample_tables(n_in, n_out, filter)
+        t = dict(host=(xmin, count, k), xmin=torch.from_numpy(xmin.copy()).to(device), count=torch.from_numpy(count.copy()).to(device),
+                 k=torch.from_numpy(k.copy()).to(device), kmax=int(k.shape[1]), taps=int(count.max()), n_in=n_in, n_out=n_out)
+        _dev_tables[key] = t
+        while len(_dev_tables) > DEVICE_TABLES_MAX:
+            _dev_tables.popitem(last=False)
+    else:
+        _dev_tables.move_to_end(key)
+    return t
+
+
+ops._clear_hooks.append(_dev_tables.clear)
+
+
+def resize_to(src: torch.Tensor, size: Tuple[int, int], filter: str = "lanczos", **stage) -> torch.Tensor:
+    """uint8 [B, Hin, Win, C] on the device -> resized to ``size`` = (height, width) and through the output stage of
+    ``ops.image_resample`` (kind, a, b, crop, binarize, dtype, out, ...)."""
+    Hin, Win = int(src.shape[1]), int(src.shape[2])
+    th = device_tables(Win, int(size[1]), filter, src.device) if Win != size[1] else None
+    tv = device_tables(Hin, int(size[0]), filter, src.device) if Hin != size[0] else None
+    return ops.image_resample(src, (int(size[0]), int(size[1])), th, tv, **stage)
+
+
+def _is_pil(im) -> bool:
+    return hasattr(im, "convert") and hasattr(im, "resize")
+
+
+class DeviceImageProcessor:
+    """Image input and output of the pipelines on the GPU.  ``dtype`` is the 16-bit type of the engines (``out="nhwc8"``,
+    ``clip_preprocess``)."""
+
+    def __init__(self, device, dtype=torch.float16):
+        if dtype not in ops.DTYPE_CODE and dtype != torch.float32:          # (fp32: clip_preprocess and out="nchw" only)
+            raise ValueError(f"dtype must be torch.bfloat16, torch.float16 or torch.float32, got {dtype}")
+        self.device, self.dtype = torch.device(device), dtype
+
+    # ---- input ----
+    def _upload(self, im, mode: str) -> torch.Tensor:
+        """one image -> uint8 [1, H, W, C] on the device (PIL / arrays: convert, one copy into pinned memory, one upload)"""
+        if isinstance(im, torch.Tensor):
+            t = im
+        else:
+            if _is_pil(im):
+                im = im.convert(mode)
+            a = np.asarray(im)                 # (a PIL image exports its pixels here; the view is read-only)
+            if a.dtype != np.uint8:
+                raise TypeError(f"DeviceImageProcessor takes PIL images or uint8 arrays / tensors, got {a.dtype}")
+            t = torch.empty(a.shape, dtype=torch.uint8, pin_memory=self.device.type == "cuda")
+            np.copyto(t.numpy(), a)            # the one host copy: straight into pinned memory
+        if t.dtype != torch.uint8:
+            raise TypeError(f"DeviceImageProcessor takes PIL images or uint8 arrays / tensors, got {t.dtype}")
+        if t.dim() == 2:
+            t = t.unsqueeze(-1)
+        if t.dim() == 3:
+            t = t.unsqueeze(0)
+        want = 3 if mode == "RGB" else 1
+        if t.dim() != 4 or t.shape[-1] != want:
+            raise ValueError(f"expected uint8 [B, H, W, {want}] (mode {mode}), got {tuple(t.shape)}")
+        if not t.is_cuda:
+            t = t.contiguous()
+            t = (t if t.is_pinned() or self.device.type != "cuda" else t.pin_memory()).to(self.device, non_blocking=True)
+        return t.contiguous()
+
+    @staticmethod
+    def _as_list(images) -> list:
+        if isinstance(images, (list, tuple)):
+            return list(images)
+        return [images]
+
+    def preprocess(self, images, size: Optional[Tuple[int, int]] = None, resample: str = "lanczos", out: str = "nhwc8",
+                   normalize: bool = True, binarize: bool = False, multiple: int = 8, mode: str = "RGB",
+                   _force_two_pass: bool = False) -> torch.Tensor:
+        """PIL image(s) or uint8 [B, H, W, C] array(s) / tensor(s) -> ``out="nchw"``: fp32 [B, C, H, W], ``out="nhwc8"``: ``dtype``
+        [B, H, W, 8] (channels C..7 zero) -- the values of ``to_image_tensor`` (then ``nchw_to_nhwc8``) bit for bit: resized to
+        ``size`` = (height, width) rounded down to a multiple of ``multiple`` with Pillow's ``resample`` filter, /255, and mapped to
+        [-1, 1] when ``normalize``.  ``size=None`` keeps each image's size (then they must agree).  ``binarize``: pixels >= 0.5 -> 1, else 0."""
+        if out not in ("nhwc8", "nchw"):
+            raise ValueError(f"out must be 'nhwc8' or 'nchw', got {out!r}")
+        if mode not in ("RGB", "L"):
+            raise ValueError(f"mode must be 'RGB' or 'L', got {mode!r}")
+        srcs = [self._upload(im, mode) for im in self._as_list(images)]
+        if size is not None:
+            hw = (int(size[0]) // multiple * multiple, int(size[1]) // multiple * multiple)
+        else:
+            hw = (int(srcs[0].shape[1]), int(srcs[0].shape[2]))
+            if any(tuple(s.shape[1:3]) != hw for s in srcs):
+                raise ValueError("preprocess(size=None): the images differ in size")
+        C_ = 3 if mode == "RGB" else 1
+        B = sum(int(s.shape[0]) for s in srcs)
+        if out == "nchw":
+            dst = torch.empty(B, C_, hw[0], hw[1], dtype=torch.float32, device=self.device)
+            kind = ops.IMAGE_F32_NCHW
+        else:
+            if self.dtype not in ops.DTYPE_CODE:
+                raise ValueError(f"out='nhwc8' needs a 16-bit processor dtype, got {self.dtype}")
+            dst = torch.empty(B, hw[0], hw[1], 8, dtype=self.dtype, device=self.device)
+            kind = ops.IMAGE_16_NHWC8
+        a, b = ((2.0, -1.0) if normalize else (1.0, 0.0))
+        i = 0
+        for s in srcs:
+            n = int(s.shape[0])
+            resize_to(s, hw, resample, kind=kind, a=(a,) * 3, b=(b,) * 3, binarize=binarize, out=dst[i:i + n],
+                      _force_two_pass=_force_two_pass)
+            i += n
+        return dst
+
+    def clip_preprocess(self, images, size: int = 224, mean: Sequence[float] = CLIP_MEAN, std: Sequence[float] = CLIP_STD) -> torch.Tensor:
+        """``CLIPImageProcessor()(images).pixel_values`` on the device: bicubic resize of the short edge to ``size`` (long edge
+        int(size * long / short)), centre crop, (x / 255 - mean) / std as x / 255 * (1 / std) - mean / std -> [B, 3, size, size] ``dtype``."""
+        a = tuple(1.0 / float(s) for s in std)
+        b = tuple(-float(m) / float(s) for m, s in zip(mean, std))
+        srcs = [self._upload(im, "RGB") for im in self._as_list(images)]
+        B = sum(int(s.shape[0]) for s in srcs)
+        dst = torch.empty(B, 3, size, size, dtype=torch.float32, device=self.device)
+        i = 0
+        for s in srcs:
+            n, h, w = int(s.shape[0]), int(s.shape[1]), int(s.shape[2])
+            short, long_ = (w, h) if w <= h else (h, w)
+            new_long = int(size * long_ / short)
+            nh, nw = (new_long, size) if w <= h else (size, new_long)
+            if nh < size or nw < size:
+                raise ValueError(f"clip_preprocess: a {h} x {w} image resizes to {nh} x {nw}, below the {size} x {size} crop")
+            resize_to(s, (nh, nw), "bicubic", kind=ops.IMAGE_F32_NCHW, a=a, b=b, crop=((nh - size) // 2, (nw - size) // 2, size, size),
+                      out=dst[i:i + n])
+            i += n
+        return dst if self.dtype == torch.float32 else dst.to(self.dtype)
+
+    # ---- output ----
+    def pack(self, nhwc16: torch.Tensor) -> torch.Tensor:
+        """decoder output [B, H, W, 4 | 8] 16-bit -> uint8 [B, H, W, 3] on the device"""
+        return ops.image_pack_u8(nhwc16)
+
+    def postprocess(self, nhwc16, output_type: str = "pil"):
+        """``AutoencoderKL.decode_nhwc`` output (a tensor, or a list of them: VAE slicing) -> ``"np"``: uint8 [B, H, W, 3],
+        ``"pil"``: list of images -- the values of the pipelines' host path, through ONE uint8 device-to-host copy."""
+        if output_type not in ("np", "pil"):
+            raise ValueError(f"postprocess handles output_type 'np' and 'pil', got {output_type!r}")
+        parts = [self.pack(y) for y in (nhwc16 if isinstance(nhwc16, (list, tuple)) else [nhwc16])]
+        arr = (parts[0] if len(parts) == 1 else torch.cat(parts)).cpu().numpy()
+        if output_type == "np":
+            return arr
+        from PIL import Image
+        return [Image.fromarray(a) for a in arr]
+
+
+__all__ = ["resample_tables", "resample_reference", "tile_rows", "device_tables", "resize_to", "DeviceImageProcessor", "CLIP_MEAN", "CLIP_STD"]

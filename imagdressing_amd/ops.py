@@ -1260,6 +1260,93 @@ def sampler_step(z, eps, x_next, *, guidance, coefs, hist=None, noise=None, mask
     return z
 
 
+# ---------------------------------------------------------------------------------------------
+# image input / output (csrc/image.hip; imagdressing_amd/image.py builds the coefficient tables)
+# ---------------------------------------------------------------------------------------------
+IMAGE_U8, IMAGE_F32_NCHW, IMAGE_16_NHWC8 = 0, 1, 2          # IMD_IMG_*
+IMAGE_FORCE_TWO_PASS = 1                                    # IMD_IMG_FORCE_TWO_PASS
+IMAGE_TILE_W, IMAGE_TILE_H, IMAGE_LDS_BYTES = 32, 8, 32768  # IMD_IMG_TILE_W / _TILE_H / _LDS_BYTES
+IMAGE_IO_COUNTER = {"resample": 0, "resample_single": 0, "resample_two_pass": 0, "pack_u8": 0}      # calls made (tests, tools/image_io_bench.py)
+
+
+def image_resample(src: torch.Tensor, size: Tuple[int, int], table_h: Optional[dict], table_v: Optional[dict], *, kind: int = IMAGE_U8,
+                   a=(1.0, 1.0, 1.0), b=(0.0, 0.0, 0.0), crop: Optional[Tuple[int, int, int, int]] = None, binarize: bool = False,
+                   dtype=None, out: Optional[torch.Tensor] = None, _force_two_pass: bool = False) -> torch.Tensor:
+    """uint8 ``src`` [B, Hin, Win, C] (C = 1 | 3; rows may be strided) -> resized to ``size`` = (Hres, Wres) as Pillow does, then the
+    output stage over ``crop`` = (top, left, h, w) of the resized image: IMAGE_U8 uint8 [B, h, w, C], IMAGE_F32_NCHW fp32 [B, C, h, w]
+    = v / 255 * a[c] + b[c], IMAGE_16_NHWC8 the same in 16 bits as [B, h, w, 8].  ``table_h`` / ``table_v``: ``image.device_tables`` of
+    the axis, None for an axis whose size does not change.  One launch, or two through a uint8 intermediate when the rows a tile needs
+    exceed its LDS (``_force_two_pass``: take that road regardless -- tests)."""
+    if not isinstance(src, torch.Tensor) or not src.is_cuda:
+        raise L.ImdError(f"src: tensor is on {getattr(src, 'device', type(src))}; imagdressing_amd runs on MI355X only (no CPU path)")
+    if src.dtype != torch.uint8 or src.dim() != 4 or src.stride(3) != 1 or src.stride(2) != src.shape[3]:
+        raise L.ImdError(f"src: expected uint8 [B, H, W, C] with contiguous rows, got {src.dtype} {tuple(src.shape)} strides {src.stride()}")
+    ensure_device(src.device)
+    B, Hin, Win, Cc = (int(v) for v in src.shape)
+    Hres, Wres = int(size[0]), int(size[1])
+    top, left, ch, cw = (0, 0, Hres, Wres) if crop is None else (int(v) for v in crop)
+    shape = {IMAGE_U8: (B, ch, cw, Cc), IMAGE_F32_NCHW: (B, Cc, ch, cw), IMAGE_16_NHWC8: (B, ch, cw, 8)}.get(kind)
+    if shape is None:
+        raise L.ImdError(f"image_resample: unknown output kind {kind}")
+    odt = {IMAGE_U8: torch.uint8, IMAGE_F32_NCHW: torch.float32}.get(kind, dtype if out is None else out.dtype)
+    if kind == IMAGE_16_NHWC8 and odt not in DTYPE_CODE:
+        raise L.ImdError(f"image_resample: an NHWC8 output is bfloat16 or float16 (dtype= or out=), got {odt}")
+    if out is None:
+        out = torch.empty(shape, dtype=odt, device=src.device)
+    elif tuple(out.shape) != shape:
+        raise L.ImdError(f"out: expected shape {shape}, got {tuple(out.shape)}")
+    p = L.ImageResampleParams()
+    p.src, p.src_row_stride, p.src_img_stride = src.data_ptr(), src.stride(1), src.stride(0)
+    p.out = _dev(out, odt, "out")
+    p.B, p.Hin, p.Win, p.C, p.Hres, p.Wres = B, Hin, Win, Cc, Hres, Wres
+    for axis, t, n_in, n_out in (("h", table_h, Win, Wres), ("v", table_v, Hin, Hres)):
+        if t is None:
+            continue
+        if (t["n_in"], t["n_out"]) != (n_in, n_out):
+            raise L.ImdError(f"image_resample: the {axis} table maps {t['n_in']} -> {t['n_out']}, the image needs {n_in} -> {n_out}")
+        setattr(p, axis + "_xmin", _dev(t["xmin"], torch.int32, axis + "_xmin"))
+        setattr(p, axis + "_count", _dev(t["count"], torch.int32, axis + "_count"))
+        setattr(p, axis + "_k", _dev(t["k"], torch.int32, axis + "_k"))
+        setattr(p, axis + "_kmax", t["kmax"])
+        setattr(p, axis + "_taps", t["taps"])
+    p.top, p.left, p.crop_h, p.crop_w = top, left, ch, cw
+    p.kind, p.binarize, p.flags = kind, int(bool(binarize)), IMAGE_FORCE_TWO_PASS if _force_two_pass else 0
+    p.dtype = _code(out, "out") if kind == IMAGE_16_NHWC8 else 0
+    for c in range(3):
+        p.a[c], p.b[c] = float(a[c]), float(b[c])
+    lib = L.load()
+    tmp = None
+    if table_h is not None and table_v is not None:
+        if 0 <= top and ch > 0 and top + ch <= Hres:
+            from .image import tile_rows
+            p.v_tile_rows = tile_rows(table_v["host"], top, ch, IMAGE_TILE_H)
+        if _force_two_pass or p.v_tile_rows * IMAGE_TILE_W * Cc > IMAGE_LDS_BYTES:
+            tmp = torch.empty(B, Hin, max(cw, 1), Cc, dtype=torch.uint8, device=src.device)
+            p.tmp = tmp.data_ptr()
+    form = lib.imd_image_resample_form(C.byref(p))
+    L.check(lib.imd_image_resample(C.byref(p), _stream()))
+    IMAGE_IO_COUNTER["resample"] += 1
+    if table_h is not None and table_v is not None:
+        IMAGE_IO_COUNTER["resample_single" if form == 1 else "resample_two_pass"] += 1
+    return out
+
+
+def image_pack_u8(x: torch.Tensor) -> torch.Tensor:
+    """16-bit [B, H, W, 4 | 8] (``AutoencoderKL.decode_nhwc``) -> uint8 [B, H, W, 3] = rint(clamp(x / 2 + 0.5, 0, 1) * 255) in fp32"""
+    if not isinstance(x, torch.Tensor) or x.dim() != 4 or x.shape[-1] not in (4, 8):
+        raise L.ImdError(f"image_pack_u8: expected a 16-bit [B, H, W, 4 | 8] tensor, got {tuple(getattr(x, 'shape', ()))}")
+    p = L.ImagePackParams()
+    p.src = _dev(x, x.dtype, "x")
+    p.dtype = _code(x, "x")
+    ensure_device(x.device)
+    out = torch.empty(x.shape[0], x.shape[1], x.shape[2], 3, dtype=torch.uint8, device=x.device)
+    p.out = out.data_ptr()
+    p.B, p.H, p.W, p.ld = (int(v) for v in x.shape)
+    L.check(L.load().imd_image_pack_u8(C.byref(p), _stream()))
+    IMAGE_IO_COUNTER["pack_u8"] += 1
+    return out
+
+
 def timestep_embedding(t: torch.Tensor, dim: int) -> torch.Tensor:
     ensure_device(t.device)
     out = torch.empty((t.shape[0], dim), dtype=torch.float32, device=t.device)

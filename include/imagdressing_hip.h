@@ -310,6 +310,65 @@ typedef struct imd_sampler_params {
                            * holds no pointer or scalar that changes between replays -- the host refreshes 52 bytes per step */
 } imd_sampler_params;
 
+/* Device-side image input (imd_image_resample): separable antialiased resampling of uint8 images, bit-exact with Pillow's 8-bit
+ * resampler (libImaging/Resample.c), with a fused output stage -- the work diffusers' VaeImageProcessor / transformers'
+ * CLIPImageProcessor do on the host in front of IMAGDressing_v1_pipeline*.py.  Per axis whose size changes the caller passes a
+ * coefficient table for `n` outputs: xmin[n], count[n] (int32) and k[n][kmax] (int32 fixed point, 22 fraction bits, zero padded):
+ *   h[y][x][c]   = clip8((2^21 + sum_{j < count[x]} src[y][xmin[x] + j][c] * k[x][j]) >> 22)          horizontal, int32 accumulator
+ *   res[y][x][c] = clip8((2^21 + sum_{j < count[y]} h[ymin[y] + j][x][c] * k[y][j]) >> 22)            vertical, over the uint8 h
+ * An axis whose table pointers are NULL is skipped (then Wres == Win / Hres == Hin is required).  Output stage over the crop window
+ * (top, left, crop_h, crop_w) of the resized image, v = res[top + y][left + x][c] (binarize != 0: v = v / 255.0f >= 0.5f ? 255 : 0):
+ *   IMD_IMG_U8        uint8 [B, crop_h, crop_w, C]                                       v
+ *   IMD_IMG_F32_NCHW  fp32  [B, C, crop_h, crop_w]                                       (float(v) / 255.0f) * a[c] + b[c]
+ *   IMD_IMG_16_NHWC8  fp16 / bf16 [B, crop_h, crop_w, 8], channels C..7 zero             the same, rounded to nearest even
+ * (IEEE division, then one rounded multiply and one rounded add: no FMA contraction.)
+ * Both axes resampled: ONE launch when the horizontally resampled rows that an output tile of IMD_IMG_TILE_H rows needs fit the LDS
+ * tile (v_tile_rows * IMD_IMG_TILE_W * C <= IMD_IMG_LDS_BYTES) and IMD_IMG_FORCE_TWO_PASS is not set; otherwise two launches through
+ * `tmp`, uint8 [B, Hin, crop_w, C].  imd_image_resample_form answers which, without launching: 1 | 2 launches, 0 = refused. */
+enum { IMD_IMG_U8 = 0, IMD_IMG_F32_NCHW = 1, IMD_IMG_16_NHWC8 = 2 };
+#define IMD_IMG_FORCE_TWO_PASS 1
+#define IMD_IMG_TILE_W 32
+#define IMD_IMG_TILE_H 8
+#define IMD_IMG_LDS_BYTES 32768
+typedef struct imd_image_resample_params {
+    uint32_t struct_bytes; /* sizeof(imd_image_resample_params) in the caller's view; checked on entry */
+    const uint8_t* src;    /* uint8 [B, Hin, Win, C] */
+    int64_t src_row_stride, src_img_stride;   /* bytes from row to row and from image to image */
+    void* out;
+    uint8_t* tmp;          /* [B, Hin, crop_w, C] uint8: required when both axes are resampled in two launches */
+    int B, Hin, Win, C;    /* C: 1 | 3 */
+    int Hres, Wres;        /* size of the resized image */
+    const int32_t* h_xmin; /* horizontal table (DEVICE pointers, Wres entries), all NULL: the axis is skipped */
+    const int32_t* h_count;
+    const int32_t* h_k;
+    int h_kmax, h_taps;    /* row length of h_k; the largest entry of h_count (refused when above h_kmax) */
+    const int32_t* v_xmin; /* vertical table (Hres entries), all NULL: the axis is skipped */
+    const int32_t* v_count;
+    const int32_t* v_k;
+    int v_kmax, v_taps;
+    int v_tile_rows;       /* max over tiles t of rows of h that output rows [top + t TILE_H, top + (t + 1) TILE_H) read (both axes resampled) */
+                           /* TRUSTED: the library cannot read the device tables.  A value below the true one keeps the single launch where
+                            * the rows do not fit: reads are clamped (memory-safe) but pixels are wrong, with no error. */
+    int top, left, crop_h, crop_w;
+    int kind;              /* IMD_IMG_* */
+    int dtype;             /* IMD_DTYPE_* of an IMD_IMG_16_NHWC8 output */
+    int binarize;
+    int flags;             /* IMD_IMG_FORCE_TWO_PASS */
+    float a[3], b[3];
+} imd_image_resample_params;
+
+/* Device-side image output (imd_image_pack_u8): 16-bit [B, H, W, ld] (ld = 4 | 8; AutoencoderKL.decode_nhwc) -> uint8 [B, H, W, 3],
+ * u = rint(clamp(x / 2 + 0.5, 0, 1) * 255) per value in fp32, rint to nearest even (numpy.round) -- the operations of
+ * `(image / 2 + 0.5).clamp(0, 1)` ... `(x * 255).round().astype("uint8")` (IMAGDressing_v1_pipeline.py:544-547 through diffusers'
+ * VaeImageProcessor.postprocess), identical for every finite 16-bit input. */
+typedef struct imd_image_pack_params {
+    uint32_t struct_bytes; /* sizeof(imd_image_pack_params) in the caller's view; checked on entry */
+    const uint16_t* src;
+    uint8_t* out;
+    int B, H, W, ld;
+    int dtype;             /* IMD_DTYPE_* of src */
+} imd_image_pack_params;
+
 /* library / device */
 int imd_abi_version(void);
 const char* imd_last_error(void);
@@ -473,6 +532,15 @@ int imd_ddim_cfg_step_rows(const imd_ddim_params* p, const float* guidance, void
  * -1..K-1 (host coefficients), a mask without z_img / blend_noise, K > 0 without hist, misaligned pointers (16 bytes for the
  * float4 / uint4 tensors, 4 for mask, guidance_rows and coefs). */
 int imd_sampler_step(const imd_sampler_params* p, void* stream);
+
+/* Pillow-exact resize (+ crop, normalise, layout) of uint8 images on the device; see imd_image_resample_params.  Errors without
+ * launching: a foreign struct size, null src / out, C outside {1, 3}, an incomplete table or a skipped axis whose size changes, a
+ * crop outside the resized image, h_taps > h_kmax / v_taps > v_kmax, an unknown output kind or dtype, two launches without tmp.
+ * imd_image_resample_form: the number of launches imd_image_resample would make for *p (1 | 2), 0 when it would refuse. */
+int imd_image_resample(const imd_image_resample_params* p, void* stream);
+int imd_image_resample_form(const imd_image_resample_params* p);
+/* Decoder output -> uint8 RGB on the device; see imd_image_pack_params. */
+int imd_image_pack_u8(const imd_image_pack_params* p, void* stream);
 
 /* diffusers Timesteps(dim, flip_sin_to_cos=True, freq_shift=0): out[B, dim] fp32 = [cos | sin]. */
 int imd_timestep_embedding(const float* t, float* out, int B, int dim, void* stream);
