@@ -710,7 +710,7 @@ __device__ __attribute__((always_inline)) bool attn40_body(const AttnParams& p) 
         // (register staging keeps the simpler form: NU full iterations, past-the-end blocks masked to P = 0 on the exact path)
         const int NUF = DMA ? (J >> 1) : NU;
         auto iteration_sync = [&]() __attribute__((always_inline)) {
-            if (DMA) { if (NPIECE == 3) dma_wait_keep3(); else dma_wait_keep2(); }   // this wave's pieces of unit u + 1 have landed (u + 2 stays in flight) ...
+            if (DMA) { if (NPIECE == 3) dma_wait_keep_n<3>(); else dma_wait_keep_n<2>(); }   // this wave's pieces of unit u + 1 have landed (u + 2 stays in flight) ...
             if (!(VAR & 8)) __syncthreads();                        // ... and so have everybody else's
         };
         int ring = 0;                                               // u % NRING

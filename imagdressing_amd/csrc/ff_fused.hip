@@ -8,7 +8,7 @@
 // which the 84 MB GEGLU tensor written and read back, the 21 MB normalised tensor and three lock-step fill / drain phases are
 // pure overhead; here the 128 x 1280 activations of a workgroup never leave the CU.
 //
-// Structure (same row-resident scheme as row_linear.hip):
+// Structure (row-resident scheme, row_common.h; rows cut as in row_linear.hip):
 //   * a workgroup (8 waves) owns 128 token rows; wave (rb, hh) holds the 32 rows of block rb -- all 320 k -- in 80 VGPRs in
 //     MFMA B-operand layout, normalises them in place (LayerNorm affine folded into W1 / b1 by the host), and owns the
 //     accumulators of output channels [160 hh, 160 hh + 160) of those rows (80 VGPRs);
@@ -24,8 +24,7 @@
 // Arithmetic is that of the unfused path: h is rounded to the 16-bit element type before the second GEMM (as the GEGLU tensor
 // was when it went through memory), fp32 accumulation everywhere, erf-based GELU (common.h).
 #include <type_traits>
-#include "gemm_common.h"
-#include "lds_dma.h"
+#include "row_common.h"
 
 namespace {
 
@@ -58,8 +57,7 @@ __global__ __launch_bounds__(512, 1) void ff_geglu320_kernel(const imd_ff_params
     const __amdgpu_buffer_rsrc_t rs_x = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(p.x), 0, x_bytes, 0x00020000);
     const uint32_t xoff = (uint32_t)m * (uint32_t)(p.x_ld * 2) + hi * 16;
     uint4 xf[FF_STEPS];
-#pragma unroll
-    for (int s = 0; s < FF_STEPS; ++s) xf[s] = buf_load16(rs_x, m < p.M ? xoff + s * 32 : OOB);
+    load_rows(xf, rs_x, m < p.M, xoff, 32);
     float b1v[5];
 #pragma unroll
     for (int i = 0; i < 5; ++i) b1v[i] = p.b1[tid + 512 * i];
@@ -69,11 +67,7 @@ __global__ __launch_bounds__(512, 1) void ff_geglu320_kernel(const imd_ff_params
     const v4i_t ds_w1 = raw_rsrc(p.w1, (uint32_t)(2 * FF_I * FF_C * 2)), ds_w2 = raw_rsrc(p.w2, (uint32_t)(FF_C * FF_I * 2));
     uint32_t w1off[5], w2off[3];
 #pragma unroll
-    for (int j = 0; j < 5; ++j) {                   // W1 chunk: 64 rows x 40 pieces, piece p of row r at p ^ ((r >> 1) & 7)
-        const int q = (j * 8 + wave) * 64 + lane;
-        const int row = q / 40, pos = q - row * 40;
-        w1off[j] = (uint32_t)(row * (FF_C * 2) + ((pos ^ ((row >> 1) & 7)) << 4));
-    }
+    for (int j = 0; j < 5; ++j) w1off[j] = ring_offset<40, 1, 7>(j, wave, lane);      // W1 chunk: 64 rows x 40 pieces, piece p of row r at p ^ ((r >> 1) & 7)
 #pragma unroll
     for (int j = 0; j < 3; ++j) {                   // W2 chunk: 320 rows x 4 pieces, piece p of row r at p ^ ((r >> 2) & 3)
         const int id = j * 8 + wave;
@@ -96,9 +90,7 @@ __global__ __launch_bounds__(512, 1) void ff_geglu320_kernel(const imd_ff_params
         }
     };
     stage_w1(0);
-    // hipcc counts only its own loads: pin their wait here (it also covers W1 chunk 0, requested with them)
-#pragma unroll
-    for (int s = 0; s < FF_STEPS; ++s) asm volatile("" : "+v"(xf[s].x), "+v"(xf[s].y), "+v"(xf[s].z), "+v"(xf[s].w));
+    pin_rows(xf);                                   // (covers W1 chunk 0, requested with the rows)
     {
         float* b1s = reinterpret_cast<float*>(smem + FF_OFF_B1);
 #pragma unroll
@@ -106,7 +98,8 @@ __global__ __launch_bounds__(512, 1) void ff_geglu320_kernel(const imd_ff_params
         if (tid < FF_C) reinterpret_cast<float*>(smem + FF_OFF_B2)[tid] = b2v;
     }
 
-    if (p.ln) {      // LayerNorm without affine, in place (two-pass fp32; lanes l and l ^ 32 share a row)
+    if (p.ln) {      // LayerNorm without affine, in place (two-pass fp32; lanes l and l ^ 32 share a row).  Written out: behind this run-time branch
+                     // any of the three pass helpers of row_common.h changes the register allocation of the whole kernel
         float sum = 0.f;
 #pragma unroll
         for (int s = 0; s < FF_STEPS; ++s) {
@@ -119,7 +112,7 @@ __global__ __launch_bounds__(512, 1) void ff_geglu320_kernel(const imd_ff_params
         const float mean = sum * (1.0f / FF_C);
         float sq = 0.f;
 #pragma unroll
-        for (int s = 0; s < FF_STEPS; ++s) asm volatile("" : "+v"(xf[s].x), "+v"(xf[s].y), "+v"(xf[s].z), "+v"(xf[s].w));
+        for (int s = 0; s < FF_STEPS; ++s) pin_row(xf[s]);
 #pragma unroll
         for (int s = 0; s < FF_STEPS; ++s) {
             float f[8];
@@ -131,7 +124,7 @@ __global__ __launch_bounds__(512, 1) void ff_geglu320_kernel(const imd_ff_params
         const float rstd = rsqrtf(sq * (1.0f / FF_C) + p.ln_eps);
         const float shift = -mean * rstd;
 #pragma unroll
-        for (int s = 0; s < FF_STEPS; ++s) asm volatile("" : "+v"(xf[s].x), "+v"(xf[s].y), "+v"(xf[s].z), "+v"(xf[s].w));
+        for (int s = 0; s < FF_STEPS; ++s) pin_row(xf[s]);
 #pragma unroll
         for (int s = 0; s < FF_STEPS; ++s) {
             float f[8];
@@ -241,25 +234,21 @@ __global__ __launch_bounds__(512, 1) void ff_geglu320_kernel(const imd_ff_params
             const int n = hh * 160 + cb * 32 + 8 * q + 4 * hi;
             res[cb][q] = buf_load8(rs_x, m < p.M ? rbase + (uint32_t)(n * 2) : OOB);
         }
-    // (round 5) 16-byte stores: one v_permlane32_swap per packed register pair turns the accumulator layout's two 4-channel groups into 8
-    // consecutive channels per lane -- half as many store requests, 32 contiguous bytes per row (row_linear.hip: "WIDE stores")
+    // 16-byte stores of 8 consecutive channels (quads_to_wide)
 #pragma unroll
     for (int cb = 0; cb < 5; ++cb)
 #pragma unroll
         for (int t = 0; t < 2; ++t) {
-            uint32_t pk[2][2];
+            v2u pk[2];
 #pragma unroll
             for (int qq = 0; qq < 2; ++qq) {
                 const int q = 2 * t + qq, n = hh * 160 + cb * 32 + 8 * q + 4 * hi;
                 const float4 bb = *reinterpret_cast<const float4*>(b2s + n);
                 const float v0 = acc_out[cb][4 * q] + bb.x + E::lo(res[cb][q].x), v1 = acc_out[cb][4 * q + 1] + bb.y + E::hi(res[cb][q].x);
                 const float v2 = acc_out[cb][4 * q + 2] + bb.z + E::lo(res[cb][q].y), v3 = acc_out[cb][4 * q + 3] + bb.w + E::hi(res[cb][q].y);
-                pk[qq][0] = E::pack2(v0, v1); pk[qq][1] = E::pack2(v2, v3);
+                pk[qq] = v2u{E::pack2(v0, v1), E::pack2(v2, v3)};
             }
-            const auto r0 = __builtin_amdgcn_permlane32_swap(pk[0][0], pk[1][0], false, false);
-            const auto r1 = __builtin_amdgcn_permlane32_swap(pk[0][1], pk[1][1], false, false);
-            typedef __attribute__((__vector_size__(4 * sizeof(uint32_t)))) uint32_t v4u_t;
-            const v4u_t w = {r0[0], r1[0], r0[1], r1[1]};
+            const v4u w = quads_to_wide(pk[0], pk[1]);
             const int n8 = hh * 160 + cb * 32 + 16 * t + 8 * hi;
             __builtin_amdgcn_raw_buffer_store_b128(w, rs_o, (int)(m < p.M ? obase + (uint32_t)(n8 * 2) : OOB), 0, 0);
         }

@@ -1,5 +1,6 @@
 // LDS-DMA (buffer_load ... lds) helpers shared by the kernels that stream operand tiles straight from global memory into
-// LDS without a VGPR round trip (attention_d40.hip, row_linear.hip).
+// LDS without a VGPR round trip: the attention kernels (attention_d40.hip), the DMA GEMMs and convolutions (gemm_dma*.hip, conv_patch*.hip,
+// conv_img.hip) and the row-resident family (through row_common.h).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -27,12 +28,8 @@ __device__ __forceinline__ void dma16_nonop(const v4i_t& rsrc, uint32_t lds_addr
                  : "=&s"(keep) : "v"(voff), "s"(lds_addr), "s"(rsrc) : "memory");
 }
 __device__ __forceinline__ void dma_wait() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
-// all but the N youngest pieces of this wave (N a compile-time constant; the named forms below are older call sites)
+// all but the N youngest pieces of this wave (N a compile-time constant)
 template <int N> __device__ __forceinline__ void dma_wait_keep_n() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-__device__ __forceinline__ void dma_wait_keep2() { asm volatile("s_waitcnt vmcnt(2)" ::: "memory"); }   // all but the 2 youngest pieces
-__device__ __forceinline__ void dma_wait_keep3() { asm volatile("s_waitcnt vmcnt(3)" ::: "memory"); }   // all but the 3 youngest pieces
-__device__ __forceinline__ void dma_wait_keep4() { asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); }   // all but the 4 youngest pieces
-__device__ __forceinline__ void dma_wait_keep5() { asm volatile("s_waitcnt vmcnt(5)" ::: "memory"); }   // all but the 5 youngest pieces
 __device__ __forceinline__ v4i_t raw_rsrc(const void* base, uint32_t bytes) {      // stride 0, raw addressing, wave-uniform by construction
     const uint64_t a = (uint64_t)base;
     v4i_t r;

@@ -23,8 +23,7 @@
 // Reference arithmetic: diffusers==0.24.0 BasicTransformerBlock / Transformer2DModel (un-vendored; call sites
 // /root/reference/dressing_sd/pipelines/IMAGDressing_v1_pipeline.py:499,511): proj_in, attn.to_out[0] (+ residual),
 // norm2 -> attn2.to_q, proj_out (+ residual), and adapter/attention_processor.py:568 (to_q), :617 (to_out) on the 64x64 level.
-#include "gemm_common.h"
-#include "lds_dma.h"
+#include "row_common.h"
 
 namespace {
 
@@ -33,13 +32,12 @@ constexpr int RL_STEPS = RL_K / 16;              // 20 MFMA k-steps
 constexpr int RL_ROWB = RL_K * 2;                // bytes per weight row
 constexpr int RL_CH = 64;                        // output channels per weight chunk
 constexpr int RL_CHUNK = RL_CH * RL_ROWB;        // 40960 bytes
-constexpr int RL_PIECES = RL_CHUNK / (8 * 1024); // DMA pieces per wave per chunk: 5
-constexpr int RL_RING = 3;
+constexpr int RL_RING = ROW_RING;
 constexpr int RL_BM = 128;
 constexpr int RL_CLD = 320 + 4;                  // fp32 epilogue tile leading dimension
 constexpr int RL_LDS = RL_RING * RL_CHUNK;       // 122880 >= 64 * RL_CLD * 4 = 82944
 constexpr int RL_LDS_TOTAL = RL_LDS + 320 * 4;   // + the bias vector of the direct epilogue
-static_assert(RL_PIECES == 5, "dma_wait_keep5 assumes five pieces per chunk");
+static_assert(RL_CHUNK == ROW_CHUNK, "ring_stage moves 40 KB chunks");
 
 // GN (round 6): GroupNorm (+ SiLU) of the rows from the statistic partials of x (imd_conv_gemm_params.gn_in_*) -- Transformer2DModel.norm -> proj_in in one launch
 template <bool F16, int NC, bool LN, bool DIRECT, bool GN = false>
@@ -62,8 +60,7 @@ __global__ __launch_bounds__(512, 1) void row_linear_kernel(const ConvGemmParams
     const int m = m0 + rb * 32 + col;
     const uint32_t xoff = (uint32_t)m * (uint32_t)(p.x_pix_stride * 2) + hi * 16;
     uint4 xf[RL_STEPS];
-#pragma unroll
-    for (int s = 0; s < RL_STEPS; ++s) xf[s] = buf_load16(rs_x, m < p.M ? xoff + s * 32 : OOB);
+    load_rows(xf, rs_x, m < p.M, xoff, 32);
 
     // DIRECT epilogue (row-major 16-bit output or head-split Q; bias / scale / residual only): every chunk's 32 x 32 block
     // leaves straight from the accumulators while the NEXT chunk is being multiplied, so the output stream overlaps the
@@ -98,63 +95,17 @@ __global__ __launch_bounds__(512, 1) void row_linear_kernel(const ConvGemmParams
 
     // ---- weight stream: source offsets of this lane's five pieces of a chunk (piece q of the chunk lands at LDS slot q) ----
     const v4i_t ds_w = raw_rsrc(p.w, p.w_bytes);
-    uint32_t woff[RL_PIECES];
+    uint32_t woff[ROW_PIECES];
 #pragma unroll
-    for (int j = 0; j < RL_PIECES; ++j) {
-        const int q = (j * 8 + wave) * 64 + lane;
-        const int row = q / 40, pos = q - row * 40;
-        woff[j] = (uint32_t)(row * RL_ROWB + ((pos ^ ((row >> 1) & 7)) << 4));
-    }
+    for (int j = 0; j < ROW_PIECES; ++j) woff[j] = ring_offset<40, 1, 7>(j, wave, lane);
     const uint32_t lds0 = (uint32_t)(uintptr_t)smem;      // LDS aperture offset of the dynamic array
-    auto stage = [&](int c) {
-        const uint32_t base = lds0 + (uint32_t)((c % RL_RING) * RL_CHUNK) + (uint32_t)wave * 1024u;
-#pragma unroll
-        for (int j = 0; j < RL_PIECES; ++j) dma16(ds_w, base + j * 8192u, woff[j] + (uint32_t)c * RL_CHUNK);
-    };
+    auto stage = [&](int c) { ring_stage(ds_w, lds0, wave, woff, c); };
     stage(0);
     if (NC > 1) stage(1);
-    // hipcc counts only its own (activation) loads: pin their wait HERE, where it also covers chunks 0 and 1 that were
-    // requested with them, instead of in front of the last MFMA of chunk 0 where it would drain chunk 2 as well
-#pragma unroll
-    for (int s = 0; s < RL_STEPS; ++s) asm volatile("" : "+v"(xf[s].x), "+v"(xf[s].y), "+v"(xf[s].z), "+v"(xf[s].w));
+    pin_rows(xf);
     if (DIRECT && tid < NC * RL_CH) reinterpret_cast<float*>(smem + RL_LDS)[tid] = bias_v;     // published by the first barrier of the chunk loop
 
-    if constexpr (LN) {      // rows normalised in place (affine folded into W / bias by the caller)
-        float sum = 0.f;
-#pragma unroll
-        for (int s = 0; s < RL_STEPS; ++s) {
-            float f[8];
-            unpack8<F16>(xf[s], f);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) sum += f[e];
-        }
-        sum += __shfl_xor(sum, 32);
-        const float mean = sum * (1.0f / RL_K);
-        float sq = 0.f;
-        // (opaque touch: keeps hipcc from holding all 160 unpacked values of the row alive across the passes)
-#pragma unroll
-        for (int s = 0; s < RL_STEPS; ++s) asm volatile("" : "+v"(xf[s].x), "+v"(xf[s].y), "+v"(xf[s].z), "+v"(xf[s].w));
-#pragma unroll
-        for (int s = 0; s < RL_STEPS; ++s) {
-            float f[8];
-            unpack8<F16>(xf[s], f);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) { const float d = f[e] - mean; sq = fmaf(d, d, sq); }
-        }
-        sq += __shfl_xor(sq, 32);
-        const float rstd = rsqrtf(sq * (1.0f / RL_K) + ln_eps);
-        const float shift = -mean * rstd;
-#pragma unroll
-        for (int s = 0; s < RL_STEPS; ++s) asm volatile("" : "+v"(xf[s].x), "+v"(xf[s].y), "+v"(xf[s].z), "+v"(xf[s].w));
-#pragma unroll
-        for (int s = 0; s < RL_STEPS; ++s) {
-            float f[8];
-            unpack8<F16>(xf[s], f);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) f[e] = fmaf(f[e], rstd, shift);
-            xf[s] = pack8<F16>(f);
-        }
-    }
+    if constexpr (LN) ln_rows_inplace<F16, RL_K>(xf, ln_eps);      // (affine folded into W / bias by the caller)
 
     if constexpr (GN) {      // rows normalised in place with the per-channel coefficients of this workgroup's image (its 128 rows lie in ONE image)
         // scratch = ring slot 2: no DMA piece lands there before stage(2), which is issued behind the first barrier of the chunk loop
@@ -184,10 +135,7 @@ __global__ __launch_bounds__(512, 1) void row_linear_kernel(const ConvGemmParams
         if (heads) { const int bi = m / HWo, tok = m - bi * HWo; obase = (uint32_t)(((size_t)bi * p.hH * p.hd[0].L + tok) * p.hd[0].DP * 2); }
         else obase = (uint32_t)m * (uint32_t)(p.out_ld * 2);
     }
-    // WIDE stores (round 5): the accumulator layout gives a lane 4 channels of a row, so an 8-byte store instruction puts 16 contiguous bytes
-    // into each of 32 rows -- fragments the L2 takes at its REQUEST rate (measured on the GEMM epilogues: 16-byte fragments drain at 2.5 TB/s, a
-    // plain fill writes at 6.2, profiles/r5d_write_bw_probe.jsonl).  One v_permlane32_swap per packed register pair turns two 4-channel groups
-    // into 8 consecutive channels per lane: half as many store requests, 32 contiguous bytes per row.  (Tuning knob 2 bit 10 = the 8-byte form.)
+    // wide: 16-byte stores of 8 consecutive channels (quads_to_wide); tuning knob 2 bit 10 = the 8-byte form
     auto emit = [&](int c) {
         const float* bias_s = reinterpret_cast<const float*>(smem + RL_LDS);
         uint2 rres[4];                     // residual in accumulator layout: group j = channels 8 j + 4 hi .. + 3
@@ -195,17 +143,11 @@ __global__ __launch_bounds__(512, 1) void row_linear_kernel(const ConvGemmParams
 #pragma unroll
             for (int t = 0; t < 2; ++t) {
                 uint4 r = rraw[c & 1][t];
-                if (wide) {                // lane hi = 0 holds channels 16 t + 0..7, hi = 1 holds 16 t + 8..15: swap hi = 0's upper half with hi = 1's lower half
-                    const auto sx = __builtin_amdgcn_permlane32_swap(r.x, r.z, false, false);
-                    const auto sy = __builtin_amdgcn_permlane32_swap(r.y, r.w, false, false);
-                    r = make_uint4(sx[0], sy[0], sx[1], sy[1]);
-                }
+                if (wide) r = wide_to_quads(r);      // lane hi = 0 holds channels 16 t + 0..7, hi = 1 holds 16 t + 8..15
                 rres[2 * t] = make_uint2(r.x, r.y); rres[2 * t + 1] = make_uint2(r.z, r.w);
             }
         }
         const float osc = heads ? p.out_scale * p.hd[0].scale : p.out_scale;
-        typedef __attribute__((__vector_size__(2 * sizeof(uint32_t)))) uint32_t v2u;
-        typedef __attribute__((__vector_size__(4 * sizeof(uint32_t)))) uint32_t v4u_t;
         v2u pk[4];
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
@@ -219,16 +161,11 @@ __global__ __launch_bounds__(512, 1) void row_linear_kernel(const ConvGemmParams
             }
             pk[j] = v2u{E::pack2(v0, v1), E::pack2(v2, v3)};
         }
-        auto offset_of = [&](int n) -> uint32_t {
-            if (heads) { const int h = n / p.hD, dd = n - h * p.hD; return (uint32_t)((h * p.hd[0].L * p.hd[0].DP + dd) * 2); }
-            return (uint32_t)(n * 2);
-        };
+        auto offset_of = [&](int n) -> uint32_t { return heads ? heads_channel_offset(p, n) : (uint32_t)(n * 2); };
         if (wide) {
 #pragma unroll
             for (int t = 0; t < 2; ++t) {      // groups j = 2 t (channels 16 t + 4 hi ..) and 2 t + 1 (16 t + 8 + 4 hi ..) -> channels 16 t + 8 hi + 0..7
-                const auto r0 = __builtin_amdgcn_permlane32_swap(pk[2 * t][0], pk[2 * t + 1][0], false, false);
-                const auto r1 = __builtin_amdgcn_permlane32_swap(pk[2 * t][1], pk[2 * t + 1][1], false, false);
-                const v4u_t w = {r0[0], r1[0], r0[1], r1[1]};
+                const v4u w = quads_to_wide(pk[2 * t], pk[2 * t + 1]);
                 const uint32_t off = offset_of(c * 64 + chh * 32 + 16 * t + 8 * hi);
                 __builtin_amdgcn_raw_buffer_store_b128(w, rs_o, (int)(obase == OOB ? OOB : obase + off), 0, 0);
             }
@@ -247,7 +184,7 @@ __global__ __launch_bounds__(512, 1) void row_linear_kernel(const ConvGemmParams
         // this wave's pieces of chunk c have landed (chunk c + 1 may still fly).  With the direct epilogue stores are in
         // flight too, and loads and stores do not retire in order with each other: no counted wait, drain everything (the
         // youngest operations are one whole chunk old by now).
-        if (DIRECT || c + 1 >= NC) dma_wait(); else dma_wait_keep5();
+        if (DIRECT || c + 1 >= NC) dma_wait(); else dma_wait_keep_n<ROW_PIECES>();
         __syncthreads();                                          // ... and everybody else's; all waves are done with chunk c - 1
         // order matters: hipcc drains the memory counter in front of emit()'s use of the residual registers (loads and stores
         // pending together) -- at this point nothing is in flight, after stage() the fresh DMA pieces would be
@@ -306,17 +243,15 @@ int launch_rl_d(const ConvGemmParams& p, float eps, hipStream_t s) {
 
 template <bool F16, int NC, bool LN>
 int launch_rl(const ConvGemmParams& p, float eps, hipStream_t s) {
-    const bool direct = p.act == ACT_NONE && !p.out_f32 && p.rowvec == nullptr && (g_gemm_flags & 256) == 0 &&
-                        (p.mode == OUT_ROWMAJOR || (p.hd[0].kind == 0 && p.hd[0].ptr != nullptr && p.N == p.hC));
-    const size_t ob = p.mode == OUT_HEADS ? (size_t)(p.M / (p.Hout * p.Wout)) * p.hH * p.hd[0].L * p.hd[0].DP * 2 : ((size_t)(p.M - 1) * p.out_ld + p.N) * 2;
-    const size_t rb = p.res ? ((size_t)(p.M - 1) * p.res_ld + p.N) * 2 : 0;
+    // (outputs or residuals of 2 GiB and more take the staged epilogue)
+    const bool direct = row_direct_epilogue(p) && (g_gemm_flags & 256) == 0 && row_out_below_2g(p);
     if (p.gn_in_partial != nullptr) {        // (never together with LN: refused by the launcher)
         if constexpr (!LN) {
-            if (direct && ob < 0x80000000ull && rb < 0x80000000ull) return launch_rl_d<F16, NC, false, true, true>(p, eps, s);
+            if (direct) return launch_rl_d<F16, NC, false, true, true>(p, eps, s);
             return launch_rl_d<F16, NC, false, false, true>(p, eps, s);
         }
     }
-    if (direct && !(LN && p.res) && ob < 0x80000000ull && rb < 0x80000000ull) return launch_rl_d<F16, NC, LN, true>(p, eps, s);
+    if (direct && !(LN && p.res)) return launch_rl_d<F16, NC, LN, true>(p, eps, s);
     return launch_rl_d<F16, NC, LN, false>(p, eps, s);
 }
 
@@ -348,10 +283,7 @@ int imd_launch_row_linear(const ConvGemmParams& p_in, int ln, float ln_eps, hipS
     if (p.res_rows != 0 && (p.res == nullptr || p.res_rows < 0 || p.res_rows % RL_BM || p.M % p.res_rows))
         return imd_set_error("row_linear: res_rows (%d) needs a residual, a multiple of %d rows and a divisor of M = %d", p.res_rows, RL_BM, p.M);
     if (p.dtype != IMD_DTYPE_BF16 && p.dtype != IMD_DTYPE_F16) return imd_set_error("row_linear: unknown dtype %d", p.dtype);
-    const size_t xb = ((size_t)(p.M - 1) * p.x_pix_stride + p.K) * 2, wb = (size_t)p.N * p.K * 2;
-    if (xb >= 0xffffffffull) return imd_set_error("row_linear: operand larger than 4 GiB");
-    p.x_bytes = (uint32_t)xb;
-    p.w_bytes = (uint32_t)wb;
+    if (int rc = row_operand_bytes(p, "row_linear", "operand larger than 4 GiB")) return rc;
     p.split_k = 1;
     p.flags = (g_gemm_flags & 1024) ? 0 : 1024;        // bit 10 of the kernel's flags: wide (16-byte) stores of the direct epilogue
     const bool h = p.dtype == IMD_DTYPE_F16;

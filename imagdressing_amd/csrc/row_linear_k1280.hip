@@ -1,6 +1,6 @@
 // Row-resident linear layer for the 16x16-level token matrix (K = 1280, N a multiple of 160): the K = N = 1280 projections of the
 // level-2 transformer blocks (25 launches per denoising step, M = 2048 rows) and `norm2 -> attn2.to_q` as one launch.  Third
-// member of the family (row_linear.hip: K = 320, row_linear_k640.hip: K = 640); same reference arithmetic, same motivation.
+// member of the family (row_common.h; row_linear.hip: K = 320, row_linear_k640.hip: K = 640); same reference arithmetic, same motivation.
 //
 // With M = 2048 there are only 64 blocks of 32 rows, and a 32-channel chunk of 1280-wide weight rows is 80 KB -- no room for a
 // ring in LDS.  So this one runs on v_mfma_f32_16x16x32 (a weight chunk is 16 rows = 40 KB) and cuts K four ways:
@@ -15,8 +15,7 @@
 //     residual (requested up front with the activations: a chunk step is shorter than a trip to HBM) and store 4 channels per
 //     token straight from registers while the next chunk runs;
 //   * LayerNorm prologue: the four K quarters exchange (sum, squared deviations) through LDS.
-#include "gemm_common.h"
-#include "lds_dma.h"
+#include "row_common.h"
 
 namespace {
 
@@ -24,8 +23,9 @@ constexpr int R12_K = 1280, R12_KQ = 320;
 constexpr int R12_STEPS = R12_KQ / 32;            // 10 k32-steps per wave and chunk
 constexpr int R12_ROWB = R12_K * 2;               // 2560 bytes per weight row = 160 pieces
 constexpr int R12_CHUNK = 16 * R12_ROWB;          // 40960
-constexpr int R12_RING = 3;
-constexpr int R12_NG = 160;                       // channels per workgroup
+constexpr int R12_RING = ROW_RING;
+constexpr int R12_NG = ROW_NG;                    // channels per workgroup
+static_assert(R12_CHUNK == ROW_CHUNK, "ring_stage moves 40 KB chunks");
 constexpr int R12_NC = R12_NG / 16;               // 10 chunks
 constexpr int R12_OFF_RED = R12_RING * R12_CHUNK;             // 122880: partial sums, 2 buffers x [2 tb][4 kq][2 th] x 1 KB
 constexpr int R12_OFF_BIAS = R12_OFF_RED + 2 * 16 * 1024;     // 155648
@@ -73,8 +73,7 @@ __global__ __launch_bounds__(512, 1) void row_linear_k1280_kernel(const ConvGemm
     for (int th = 0; th < 2; ++th) {
         const int m = m0 + th * 16 + col;
         const uint32_t xoff = (uint32_t)m * (uint32_t)(p.x_pix_stride * 2) + (uint32_t)(kq * (R12_KQ * 2) + g * 16);
-#pragma unroll
-        for (int s = 0; s < R12_STEPS; ++s) xf[th][s] = buf_load16(rs_x, m < p.M ? xoff + s * 64 : OOB);
+        load_rows(xf[th], rs_x, m < p.M, xoff, 64);
     }
     float bias_v = 0.f;
     if (tid < R12_NG && p.bias) bias_v = p.bias[n0 + tid];
@@ -93,25 +92,15 @@ __global__ __launch_bounds__(512, 1) void row_linear_k1280_kernel(const ConvGemm
 
     // ---- weight stream ----
     const v4i_t ds_w = raw_rsrc(p.w, p.w_bytes);
-    uint32_t woff[5];
+    uint32_t woff[ROW_PIECES];
 #pragma unroll
-    for (int j = 0; j < 5; ++j) {
-        const int q = (j * 8 + wave) * 64 + lane;
-        const int row = q / 160, pos = q - row * 160;
-        woff[j] = (uint32_t)((n0 + row) * R12_ROWB + ((pos ^ (row & 15)) << 4));
-    }
+    for (int j = 0; j < ROW_PIECES; ++j) woff[j] = ring_offset<160, 0, 15>(j, wave, lane, n0);
     const uint32_t lds0 = (uint32_t)(uintptr_t)smem;
-    auto stage = [&](int c) {
-        const uint32_t base = lds0 + (uint32_t)((c % R12_RING) * R12_CHUNK) + (uint32_t)wave * 1024u;
-#pragma unroll
-        for (int j = 0; j < 5; ++j) dma16(ds_w, base + j * 8192u, woff[j] + (uint32_t)c * R12_CHUNK);
-    };
+    auto stage = [&](int c) { ring_stage(ds_w, lds0, wave, woff, c); };
     stage(0);
     stage(1);
-#pragma unroll
-    for (int th = 0; th < 2; ++th)
-#pragma unroll
-        for (int s = 0; s < R12_STEPS; ++s) asm volatile("" : "+v"(xf[th][s].x), "+v"(xf[th][s].y), "+v"(xf[th][s].z), "+v"(xf[th][s].w));
+    pin_rows(xf[0]);
+    pin_rows(xf[1]);
     if (tid < R12_NG) reinterpret_cast<float*>(smem + R12_OFF_BIAS)[tid] = bias_v;
 
     if constexpr (GN) {      // (scratch = ring slot 2: nothing lands there before stage(2), issued behind the chunk loop's first barrier; the 64 rows lie in ONE image)
@@ -134,14 +123,7 @@ __global__ __launch_bounds__(512, 1) void row_linear_k1280_kernel(const ConvGemm
         float part[2];
 #pragma unroll
         for (int th = 0; th < 2; ++th) {
-            float sum = 0.f;
-#pragma unroll
-            for (int s = 0; s < R12_STEPS; ++s) {
-                float f[8];
-                unpack8<F16>(xf[th][s], f);
-#pragma unroll
-                for (int e = 0; e < 8; ++e) sum += f[e];
-            }
+            float sum = rows_sum<F16>(xf[th]);
             sum += __shfl_xor(sum, 16);
             sum += __shfl_xor(sum, 32);
             part[th] = sum;
@@ -156,20 +138,11 @@ __global__ __launch_bounds__(512, 1) void row_linear_k1280_kernel(const ConvGemm
             mean[th] = t * (1.0f / R12_K);
         }
         __syncthreads();
-#pragma unroll
-        for (int th = 0; th < 2; ++th)
-#pragma unroll
-            for (int s = 0; s < R12_STEPS; ++s) asm volatile("" : "+v"(xf[th][s].x), "+v"(xf[th][s].y), "+v"(xf[th][s].z), "+v"(xf[th][s].w));
+        pin_rows(xf[0]);
+        pin_rows(xf[1]);
 #pragma unroll
         for (int th = 0; th < 2; ++th) {
-            float sq = 0.f;
-#pragma unroll
-            for (int s = 0; s < R12_STEPS; ++s) {
-                float f[8];
-                unpack8<F16>(xf[th][s], f);
-#pragma unroll
-                for (int e = 0; e < 8; ++e) { const float d = f[e] - mean[th]; sq = fmaf(d, d, sq); }
-            }
+            float sq = rows_sqdev<F16>(xf[th], mean[th]);
             sq += __shfl_xor(sq, 16);
             sq += __shfl_xor(sq, 32);
             lnx[(wave * 2 + th) * 64 + lane] = sq;
@@ -183,22 +156,10 @@ __global__ __launch_bounds__(512, 1) void row_linear_k1280_kernel(const ConvGemm
             rstd[th] = rsqrtf(t * (1.0f / R12_K) + ln_eps);
         }
         (void)part;
+        pin_rows(xf[0]);
+        pin_rows(xf[1]);
 #pragma unroll
-        for (int th = 0; th < 2; ++th)
-#pragma unroll
-            for (int s = 0; s < R12_STEPS; ++s) asm volatile("" : "+v"(xf[th][s].x), "+v"(xf[th][s].y), "+v"(xf[th][s].z), "+v"(xf[th][s].w));
-#pragma unroll
-        for (int th = 0; th < 2; ++th) {
-            const float shift = -mean[th] * rstd[th];
-#pragma unroll
-            for (int s = 0; s < R12_STEPS; ++s) {
-                float f[8];
-                unpack8<F16>(xf[th][s], f);
-#pragma unroll
-                for (int e = 0; e < 8; ++e) f[e] = fmaf(f[e], rstd[th], shift);
-                xf[th][s] = pack8<F16>(f);
-            }
-        }
+        for (int th = 0; th < 2; ++th) rows_scale_shift<F16>(xf[th], rstd[th], -mean[th] * rstd[th]);
     }
 
     // ---- output side: waves kq = 0 / 1 own token half 0 / 1: channels n0 + 16 c + 4 g .. + 3 of token m0 + 16 kq + col ----
@@ -231,10 +192,7 @@ __global__ __launch_bounds__(512, 1) void row_linear_k1280_kernel(const ConvGemm
             v2 += E::lo(rres[c].y); v3 += E::hi(rres[c].y);
         }
         const int n = n0 + nl;
-        uint32_t off;
-        if (heads) { const int h = n / p.hD, dd = n - h * p.hD; off = (uint32_t)((h * p.hd[0].L * p.hd[0].DP + dd) * 2); }
-        else off = (uint32_t)(n * 2);
-        typedef __attribute__((__vector_size__(2 * sizeof(uint32_t)))) uint32_t v2u;
+        const uint32_t off = heads ? heads_channel_offset(p, n) : (uint32_t)(n * 2);
         const v2u pk = {E::pack2(v0, v1), E::pack2(v2, v3)};
         __builtin_amdgcn_raw_buffer_store_b64(pk, rs_o, (int)(obase == OOB ? OOB : obase + off), 0, 0);
     };
@@ -270,44 +228,16 @@ __global__ __launch_bounds__(512, 1) void row_linear_k1280_kernel(const ConvGemm
 
 template <bool F16, bool LN, bool GN = false>
 int launch_r12(const ConvGemmParams& p, float eps, hipStream_t s) {
-    auto kern = row_linear_k1280_kernel<F16, LN, GN>;
-    if (int rc_attr = imd_lds_attr(reinterpret_cast<const void*>(kern), R12_LDS, "row_linear_k1280")) return rc_attr;
-    const unsigned grid = (unsigned)((((p.M + 63) / 64 + 7) / 8) * 8 * (p.N / R12_NG));
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(512), R12_LDS, s, p, eps);
-    return imd_check_launch("row_linear_k1280");
+    return row_wide_launch_kernel<64>(row_linear_k1280_kernel<F16, LN, GN>, R12_LDS, "row_linear_k1280", p, eps, s);
 }
+constexpr RowLaunchFn R12_KERNELS[3][2] = {{launch_r12<true, false, true>, launch_r12<false, false, true>},
+                                           {launch_r12<true, true>, launch_r12<false, true>},
+                                           {launch_r12<true, false>, launch_r12<false, false>}};
 
 }  // namespace
 
-bool imd_row_linear_k1280_supported(const ConvGemmParams& p) {
-    const bool direct = p.act == ACT_NONE && !p.out_f32 && p.rowvec == nullptr &&
-                        (p.mode == OUT_ROWMAJOR || (p.hd[0].kind == 0 && p.hd[0].ptr != nullptr && p.N == p.hC));
-    return direct && p.taps == 1 && p.K == R12_K && p.Cin == R12_K && p.stride == 1 && !p.ups && p.Hin == p.Hout && p.Win == p.Wout &&
-           p.N >= R12_NG && (p.N % R12_NG) == 0 && p.split_k <= 1 && p.gn_a == nullptr && (p.x_pix_stride % 8) == 0 &&
-           (p.mode != OUT_HEADS || (p.hD % 4) == 0);
-}
+bool imd_row_linear_k1280_supported(const ConvGemmParams& p) { return row_wide_supported<R12_K>(p); }
 
-int imd_launch_row_linear_k1280(const ConvGemmParams& p_in, int ln, float ln_eps, hipStream_t s) {
-    ConvGemmParams p = p_in;
-    if (p_in.res_rows != 0) return imd_set_error("row_linear_k1280: a periodic residual (res_rows) exists in the K = 320 row-resident projection only");
-    if (!imd_row_linear_k1280_supported(p))
-        return imd_set_error("row_linear_k1280: needs a plain linear layer with K = 1280, N a multiple of 160 and a bias / scale / residual epilogue "
-                             "(got N=%d K=%d taps=%d act=%d)", p.N, p.K, p.taps, p.act);
-    if (p.dtype != IMD_DTYPE_BF16 && p.dtype != IMD_DTYPE_F16) return imd_set_error("row_linear_k1280: unknown dtype %d", p.dtype);
-    const size_t xb = ((size_t)(p.M - 1) * p.x_pix_stride + p.K) * 2, wb = (size_t)p.N * p.K * 2;
-    const size_t ob = p.mode == OUT_HEADS ? (size_t)(p.M / (p.Hout * p.Wout)) * p.hH * p.hd[0].L * p.hd[0].DP * 2 : ((size_t)(p.M - 1) * p.out_ld + p.N) * 2;
-    const size_t rb = p.res ? ((size_t)(p.M - 1) * p.res_ld + p.N) * 2 : 0;
-    if (xb >= 0xffffffffull || ob >= 0x80000000ull || rb >= 0x80000000ull) return imd_set_error("row_linear_k1280: operand too large");
-    p.x_bytes = (uint32_t)xb;
-    p.w_bytes = (uint32_t)wb;
-    p.split_k = 1;
-    p.flags = 0;
-    const bool h = p.dtype == IMD_DTYPE_F16;
-    if (p.gn_in_partial != nullptr) {
-        if (ln || !gn_in_ok(p, R12_K, 64))
-            return imd_set_error("row_linear_k1280: gn_in_* needs K = 1280, K %% groups == 0, groups <= 64, H W %% 64 == 0 and no LayerNorm prologue (ask imd_row_linear_gn_in_supported())");
-        return h ? launch_r12<true, false, true>(p, ln_eps, s) : launch_r12<false, false, true>(p, ln_eps, s);
-    }
-    if (ln) return h ? launch_r12<true, true>(p, ln_eps, s) : launch_r12<false, true>(p, ln_eps, s);
-    return h ? launch_r12<true, false>(p, ln_eps, s) : launch_r12<false, false>(p, ln_eps, s);
+int imd_launch_row_linear_k1280(const ConvGemmParams& p, int ln, float ln_eps, hipStream_t s) {
+    return row_wide_launch<R12_K, 64>(p, ln, ln_eps, s, "row_linear_k1280", 0, R12_KERNELS);
 }

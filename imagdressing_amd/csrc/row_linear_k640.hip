@@ -1,7 +1,8 @@
 // Row-resident linear layer for the 32x32-level token matrix (K = 640, N a multiple of 160): the K = N = 640 projections of
 // the level-1 transformer blocks (proj_in, attn1.to_out, attn2.to_q, attn2.to_out, proj_out -- 25 launches per denoising step,
-// M = 8192 rows) and `norm2 -> attn2.to_q` as one launch.  Same reference arithmetic and same reasons as row_linear.hip (the
-// tiled kernel walks K in ten dependent round trips to memory per workgroup and runs at ~0.11 of the MFMA peak on this shape).
+// M = 8192 rows) and `norm2 -> attn2.to_q` as one launch.  Row-resident scheme (row_common.h); same reference arithmetic and
+// same reasons as row_linear.hip (the tiled kernel walks K in ten dependent round trips to memory per workgroup and runs at
+// ~0.11 of the MFMA peak on this shape).
 //
 // A full 640-wide row block does not fit a wave's registers next to the accumulators, and M = 8192 gives only 64 blocks of
 // 128 rows, so the work is cut differently from the K = 320 kernel:
@@ -16,8 +17,7 @@
 //     what it receives and stores its 2 x 4 channels per token straight from registers -- bias from LDS, residual fetched one
 //     chunk ahead -- while the next chunk is being multiplied;
 //   * LayerNorm prologue: each wave sees half a row; the two halves exchange (sum, sum of squared deviations) through LDS.
-#include "gemm_common.h"
-#include "lds_dma.h"
+#include "row_common.h"
 
 namespace {
 
@@ -25,8 +25,9 @@ constexpr int R6_K = 640, R6_KH = 320;
 constexpr int R6_STEPS = R6_KH / 16;              // 20 k-steps per wave and chunk
 constexpr int R6_ROWB = R6_K * 2;                 // 1280 bytes per weight row = 80 pieces
 constexpr int R6_CHUNK = 32 * R6_ROWB;            // 40960
-constexpr int R6_RING = 3;
-constexpr int R6_NG = 160;                        // channels per workgroup
+constexpr int R6_RING = ROW_RING;
+constexpr int R6_NG = ROW_NG;                     // channels per workgroup
+static_assert(R6_CHUNK == ROW_CHUNK, "ring_stage moves 40 KB chunks");
 constexpr int R6_NC = R6_NG / 32;                 // 5 chunks
 constexpr int R6_OFF_RED = R6_RING * R6_CHUNK;    // 122880: partial-sum exchange, 2 buffers x 8 waves x 2 KB
 constexpr int R6_OFF_BIAS = R6_OFF_RED + 2 * 8 * 2048;     // 155648
@@ -59,36 +60,25 @@ __global__ __launch_bounds__(512, 1) void row_linear_k640_kernel(const ConvGemmP
     const __amdgpu_buffer_rsrc_t rs_x = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(p.x), 0, p.x_bytes, 0x00020000);
     const uint32_t xoff = (uint32_t)m * (uint32_t)(p.x_pix_stride * 2) + (uint32_t)(kh * (R6_KH * 2) + hi * 16);
     uint4 xf[R6_STEPS];
-#pragma unroll
-    for (int s = 0; s < R6_STEPS; ++s) xf[s] = buf_load16(rs_x, m < p.M ? xoff + s * 32 : OOB);
+    load_rows(xf, rs_x, m < p.M, xoff, 32);
     float bias_v = 0.f;
     if (tid < R6_NG && p.bias) bias_v = p.bias[n0 + tid];
 
     // ---- weight stream ----
     const v4i_t ds_w = raw_rsrc(p.w, p.w_bytes);
-    uint32_t woff[5];
+    uint32_t woff[ROW_PIECES];
 #pragma unroll
-    for (int j = 0; j < 5; ++j) {
-        const int q = (j * 8 + wave) * 64 + lane;
-        const int row = q / 80, pos = q - row * 80;
-        woff[j] = (uint32_t)((n0 + row) * R6_ROWB + ((pos ^ (row & 15)) << 4));
-    }
+    for (int j = 0; j < ROW_PIECES; ++j) woff[j] = ring_offset<80, 0, 15>(j, wave, lane, n0);
     const uint32_t lds0 = (uint32_t)(uintptr_t)smem;
-    auto stage = [&](int c) {
-        const uint32_t base = lds0 + (uint32_t)((c % R6_RING) * R6_CHUNK) + (uint32_t)wave * 1024u;
-#pragma unroll
-        for (int j = 0; j < 5; ++j) dma16(ds_w, base + j * 8192u, woff[j] + (uint32_t)c * R6_CHUNK);
-    };
+    auto stage = [&](int c) { ring_stage(ds_w, lds0, wave, woff, c); };
     stage(0);
     stage(1);
-    // hipcc counts only its own loads: pin their wait here (it also covers chunks 0 and 1, requested with them)
-#pragma unroll
-    for (int s = 0; s < R6_STEPS; ++s) asm volatile("" : "+v"(xf[s].x), "+v"(xf[s].y), "+v"(xf[s].z), "+v"(xf[s].w));
+    pin_rows(xf);
     if (tid < R6_NG) reinterpret_cast<float*>(smem + R6_OFF_BIAS)[tid] = bias_v;
 
     if constexpr (LN) {      // LayerNorm without affine over all 640 channels: the K halves meet in LDS twice (sum, squared deviations)
         float2* lnx = reinterpret_cast<float2*>(smem + R6_OFF_LN);
-        float sum = 0.f;
+        float sum = 0.f;      // (rows_sum / rows_sqdev written out: through the helpers hipcc commutes the additions of the partner's partials below)
 #pragma unroll
         for (int s = 0; s < R6_STEPS; ++s) {
             float f[8];
@@ -101,8 +91,7 @@ __global__ __launch_bounds__(512, 1) void row_linear_k640_kernel(const ConvGemmP
         __syncthreads();
         const float mean = (sum + lnx[(wave ^ 4) * 64 + lane].x) * (1.0f / R6_K);
         float sq = 0.f;
-#pragma unroll
-        for (int s = 0; s < R6_STEPS; ++s) asm volatile("" : "+v"(xf[s].x), "+v"(xf[s].y), "+v"(xf[s].z), "+v"(xf[s].w));
+        pin_rows(xf);
 #pragma unroll
         for (int s = 0; s < R6_STEPS; ++s) {
             float f[8];
@@ -115,16 +104,8 @@ __global__ __launch_bounds__(512, 1) void row_linear_k640_kernel(const ConvGemmP
         __syncthreads();
         const float rstd = rsqrtf((sq + lnx[(wave ^ 4) * 64 + lane].y) * (1.0f / R6_K) + ln_eps);
         const float shift = -mean * rstd;
-#pragma unroll
-        for (int s = 0; s < R6_STEPS; ++s) asm volatile("" : "+v"(xf[s].x), "+v"(xf[s].y), "+v"(xf[s].z), "+v"(xf[s].w));
-#pragma unroll
-        for (int s = 0; s < R6_STEPS; ++s) {
-            float f[8];
-            unpack8<F16>(xf[s], f);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) f[e] = fmaf(f[e], rstd, shift);
-            xf[s] = pack8<F16>(f);
-        }
+        pin_rows(xf);
+        rows_scale_shift<F16>(xf, rstd, shift);
     }
 
     if constexpr (GN) {      // (scratch = ring slot 2: nothing lands there before stage(2), issued behind the chunk loop's first barrier)
@@ -166,17 +147,11 @@ __global__ __launch_bounds__(512, 1) void row_linear_k640_kernel(const ConvGemmP
     const float osc = heads ? p.out_scale * p.hd[0].scale : p.out_scale;
     float own[8];                      // this wave's two quads of the previous chunk (its own partial sums)
     auto emit = [&](int c) {           // chunk c: own partial + the partner's, bias, scale, residual, one 16-byte (or two 8-byte) stores
-        typedef __attribute__((__vector_size__(2 * sizeof(uint32_t)))) uint32_t v2u;
-        typedef __attribute__((__vector_size__(4 * sizeof(uint32_t)))) uint32_t v4u_t;
         v2u pk[2];
         uint2 rres[2];                 // residual in accumulator layout
         if (has_res) {
             uint4 r = rraw[c & 1];
-            if (wide) {
-                const auto sx = __builtin_amdgcn_permlane32_swap(r.x, r.z, false, false);
-                const auto sy = __builtin_amdgcn_permlane32_swap(r.y, r.w, false, false);
-                r = make_uint4(sx[0], sy[0], sx[1], sy[1]);
-            }
+            if (wide) r = wide_to_quads(r);
             rres[0] = make_uint2(r.x, r.y); rres[1] = make_uint2(r.z, r.w);
         }
 #pragma unroll
@@ -192,14 +167,9 @@ __global__ __launch_bounds__(512, 1) void row_linear_k640_kernel(const ConvGemmP
             }
             pk[j] = v2u{E::pack2(v0, v1), E::pack2(v2, v3)};
         }
-        auto offset_of = [&](int n) -> uint32_t {
-            if (heads) { const int h = n / p.hD, dd = n - h * p.hD; return (uint32_t)((h * p.hd[0].L * p.hd[0].DP + dd) * 2); }
-            return (uint32_t)(n * 2);
-        };
+        auto offset_of = [&](int n) -> uint32_t { return heads ? heads_channel_offset(p, n) : (uint32_t)(n * 2); };
         if (wide) {                    // quads 2 kh (channels 16 kh + 4 hi ..) and 2 kh + 1 (16 kh + 8 + 4 hi ..) -> channels 16 kh + 8 hi + 0..7 of the chunk
-            const auto r0 = __builtin_amdgcn_permlane32_swap(pk[0][0], pk[1][0], false, false);
-            const auto r1 = __builtin_amdgcn_permlane32_swap(pk[0][1], pk[1][1], false, false);
-            const v4u_t w = {r0[0], r1[0], r0[1], r1[1]};
+            const v4u w = quads_to_wide(pk[0], pk[1]);
             __builtin_amdgcn_raw_buffer_store_b128(w, rs_o, (int)(obase == OOB ? OOB : obase + offset_of(n0 + 32 * c + 16 * kh + 8 * hi)), 0, 0);
         } else {
 #pragma unroll
@@ -242,44 +212,17 @@ __global__ __launch_bounds__(512, 1) void row_linear_k640_kernel(const ConvGemmP
 
 template <bool F16, bool LN, bool GN = false>
 int launch_r6(const ConvGemmParams& p, float eps, hipStream_t s) {
-    auto kern = row_linear_k640_kernel<F16, LN, GN>;
-    if (int rc_attr = imd_lds_attr(reinterpret_cast<const void*>(kern), R6_LDS, "row_linear_k640")) return rc_attr;
-    const unsigned grid = (unsigned)((((p.M + 127) / 128 + 7) / 8) * 8 * (p.N / R6_NG));
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(512), R6_LDS, s, p, eps);
-    return imd_check_launch("row_linear_k640");
+    return row_wide_launch_kernel<128>(row_linear_k640_kernel<F16, LN, GN>, R6_LDS, "row_linear_k640", p, eps, s);
 }
+constexpr RowLaunchFn R6_KERNELS[3][2] = {{launch_r6<true, false, true>, launch_r6<false, false, true>},
+                                          {launch_r6<true, true>, launch_r6<false, true>},
+                                          {launch_r6<true, false>, launch_r6<false, false>}};
 
 }  // namespace
 
-bool imd_row_linear_k640_supported(const ConvGemmParams& p) {
-    const bool direct = p.act == ACT_NONE && !p.out_f32 && p.rowvec == nullptr &&
-                        (p.mode == OUT_ROWMAJOR || (p.hd[0].kind == 0 && p.hd[0].ptr != nullptr && p.N == p.hC));
-    return direct && p.taps == 1 && p.K == R6_K && p.Cin == R6_K && p.stride == 1 && !p.ups && p.Hin == p.Hout && p.Win == p.Wout &&
-           p.N >= R6_NG && (p.N % R6_NG) == 0 && p.split_k <= 1 && p.gn_a == nullptr && (p.x_pix_stride % 8) == 0 &&
-           (p.mode != OUT_HEADS || (p.hD % 4) == 0);
-}
+bool imd_row_linear_k640_supported(const ConvGemmParams& p) { return row_wide_supported<R6_K>(p); }
 
-int imd_launch_row_linear_k640(const ConvGemmParams& p_in, int ln, float ln_eps, hipStream_t s) {
-    ConvGemmParams p = p_in;
-    if (p_in.res_rows != 0) return imd_set_error("row_linear_k640: a periodic residual (res_rows) exists in the K = 320 row-resident projection only");
-    if (!imd_row_linear_k640_supported(p))
-        return imd_set_error("row_linear_k640: needs a plain linear layer with K = 640, N a multiple of 160 and a bias / scale / residual epilogue "
-                             "(got N=%d K=%d taps=%d act=%d)", p.N, p.K, p.taps, p.act);
-    if (p.dtype != IMD_DTYPE_BF16 && p.dtype != IMD_DTYPE_F16) return imd_set_error("row_linear_k640: unknown dtype %d", p.dtype);
-    const size_t xb = ((size_t)(p.M - 1) * p.x_pix_stride + p.K) * 2, wb = (size_t)p.N * p.K * 2;
-    const size_t ob = p.mode == OUT_HEADS ? (size_t)(p.M / (p.Hout * p.Wout)) * p.hH * p.hd[0].L * p.hd[0].DP * 2 : ((size_t)(p.M - 1) * p.out_ld + p.N) * 2;
-    const size_t rb = p.res ? ((size_t)(p.M - 1) * p.res_ld + p.N) * 2 : 0;
-    if (xb >= 0xffffffffull || ob >= 0x80000000ull || rb >= 0x80000000ull) return imd_set_error("row_linear_k640: operand too large");
-    p.x_bytes = (uint32_t)xb;
-    p.w_bytes = (uint32_t)wb;
-    p.split_k = 1;
-    p.flags = (g_gemm_flags & 1024) ? 0 : 1024;        // bit 10: wide (16-byte) stores of the direct epilogue
-    const bool h = p.dtype == IMD_DTYPE_F16;
-    if (p.gn_in_partial != nullptr) {
-        if (ln || !gn_in_ok(p, R6_K, 128))
-            return imd_set_error("row_linear_k640: gn_in_* needs K = 640, K %% groups == 0, groups <= 64, H W %% 128 == 0 and no LayerNorm prologue (ask imd_row_linear_gn_in_supported())");
-        return h ? launch_r6<true, false, true>(p, ln_eps, s) : launch_r6<false, false, true>(p, ln_eps, s);
-    }
-    if (ln) return h ? launch_r6<true, true>(p, ln_eps, s) : launch_r6<false, true>(p, ln_eps, s);
-    return h ? launch_r6<true, false>(p, ln_eps, s) : launch_r6<false, false>(p, ln_eps, s);
+int imd_launch_row_linear_k640(const ConvGemmParams& p, int ln, float ln_eps, hipStream_t s) {
+    // flags bit 10: wide (16-byte) stores of the direct epilogue
+    return row_wide_launch<R6_K, 128>(p, ln, ln_eps, s, "row_linear_k640", (g_gemm_flags & 1024) ? 0 : 1024, R6_KERNELS);
 }

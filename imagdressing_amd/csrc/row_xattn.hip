@@ -7,7 +7,7 @@
 // call sites adapter/attention_processor.py:568 (to_q), :589-612 (attention), :617 (to_out)).  The chain is row-local, so
 // Q, P and O never exist in memory: the launch reads x and writes the block output.
 //
-// Geometry = row_linear.hip: 512 threads own 128 token rows; wave (rb, chh) keeps ITS 32 rows x 320 channels in 80 VGPRs
+// Row-resident scheme (row_common.h), geometry = row_linear.hip: 512 threads own 128 token rows; wave (rb, chh) keeps ITS 32 rows x 320 channels in 80 VGPRs
 // in MFMA B-operand layout (LayerNorm prologue in registers, affine folded into W_q' / b_q' by the caller) and everything
 // else streams through a 3 x 40 KB LDS ring by LDS-DMA as ONE sequence of 15 chunks, one barrier per chunk:
 //   chunks 0..5   W_q' with every head padded to 48 rows: wave half chh owns heads 4 chh .. 4 chh + 3 (192 rows = six 32-row
@@ -25,8 +25,7 @@
 //                 residual = the un-normalised x re-read from L2 one chunk ahead) while the next chunk is multiplied.
 // 16-bit rounding points (the same four as the three-launch path): q (after bias and scale), P = exp2(s - max), O = sum / l,
 // out.  All chunk images carry their LDS swizzle on the source side: every DMA piece is a linear 1 KB copy.
-#include "gemm_common.h"
-#include "lds_dma.h"
+#include "row_common.h"
 
 namespace {
 
@@ -34,8 +33,8 @@ constexpr int XA_C = 320;
 constexpr int XA_STEPS = XA_C / 16;                 // 20 MFMA k-steps of the two projections
 constexpr int XA_ROWB = XA_C * 2;                   // bytes per weight row
 constexpr int XA_CHUNK = 64 * XA_ROWB;              // 40960: one ring slot
-constexpr int XA_PIECES = XA_CHUNK / (8 * 1024);    // DMA pieces per wave per chunk: 5
-constexpr int XA_RING = 3;
+constexpr int XA_PIECES = ROW_PIECES;               // DMA pieces per wave per chunk: 5
+constexpr int XA_RING = ROW_RING;
 constexpr int XA_BM = 128;
 constexpr int XA_NQ = 6, XA_NKV = 4, XA_NO = 5;     // chunks of the three stages
 constexpr int XA_NCHUNK = XA_NQ + XA_NKV + XA_NO;
@@ -47,15 +46,13 @@ constexpr int XA_HEADB = XA_KBYTES + 48 * XA_VROW;  // 19200 bytes per head; a c
 constexpr int XA_XB = 8 * 5 * 512;                  // O exchange buffer of one head: 8 waves x 5 channel groups x 64 lanes x 8 bytes
 constexpr int XA_OFF_X = XA_RING * XA_CHUNK;        // exchange area (2 buffers); its first bytes hold b_q' during the Q stage and b_o during the out stage
 constexpr int XA_LDS = XA_OFF_X + 2 * XA_XB;        // 163840: all of a CU's LDS
-static_assert(XA_PIECES == 5, "dma_wait_keep5 assumes five pieces per chunk");
+static_assert(XA_CHUNK == ROW_CHUNK, "the ring of the family: 40 KB chunks in five pieces per wave");
 static_assert(2 * XA_HEADB <= XA_CHUNK && XA_LDS <= 160 * 1024, "LDS budget");
 static_assert(64 * XA_NQ * 4 <= XA_XB && XA_C * 4 <= XA_XB, "bias tables live in the exchange area");
 
 template <bool F16>
 __global__ __launch_bounds__(512, 1) void text_xattn320_kernel(const imd_xattn_params p) {
     using E = El<F16>;
-    typedef __attribute__((__vector_size__(2 * sizeof(uint32_t)))) uint32_t v2u;
-    typedef __attribute__((__vector_size__(4 * sizeof(uint32_t)))) uint32_t v4u_t;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -71,8 +68,7 @@ __global__ __launch_bounds__(512, 1) void text_xattn320_kernel(const imd_xattn_p
     const int m = m0 + rb * 32 + col;
     const uint32_t xoff = (uint32_t)m * (uint32_t)(p.x_ld * 2) + hi * 16;
     uint4 xf[XA_STEPS];
-#pragma unroll
-    for (int s = 0; s < XA_STEPS; ++s) xf[s] = buf_load16(rs_x, m < p.M ? xoff + s * 32 : OOB);
+    load_rows(xf, rs_x, m < p.M, xoff, 32);
     float bq_v = 0.f, bo_v = 0.f;      // requested behind the activation rows; parked in LDS when their stage begins
     if (tid < 64 * XA_NQ) bq_v = p.bq[tid];
     if (tid < XA_C) bo_v = p.bo[tid];
@@ -92,48 +88,11 @@ __global__ __launch_bounds__(512, 1) void text_xattn320_kernel(const imd_xattn_p
     };
     stage(0);
     stage(1);
-    // (as in row_linear.hip: pin the wait for the activation loads here, where it also covers chunks 0 and 1)
-#pragma unroll
-    for (int s = 0; s < XA_STEPS; ++s) asm volatile("" : "+v"(xf[s].x), "+v"(xf[s].y), "+v"(xf[s].z), "+v"(xf[s].w));
+    pin_rows(xf);
     float* bias_s = reinterpret_cast<float*>(smem + XA_OFF_X);
     if (tid < 64 * XA_NQ) bias_s[tid] = bq_v;                                // published by the first barrier of the chunk loop
 
-    // ---- LayerNorm (no affine) of the rows, in place: two-pass fp32 (row_linear.hip) ----
-    {
-        float sum = 0.f;
-#pragma unroll
-        for (int s = 0; s < XA_STEPS; ++s) {
-            float f[8];
-            unpack8<F16>(xf[s], f);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) sum += f[e];
-        }
-        sum += __shfl_xor(sum, 32);
-        const float mean = sum * (1.0f / XA_C);
-        float sq = 0.f;
-#pragma unroll
-        for (int s = 0; s < XA_STEPS; ++s) asm volatile("" : "+v"(xf[s].x), "+v"(xf[s].y), "+v"(xf[s].z), "+v"(xf[s].w));
-#pragma unroll
-        for (int s = 0; s < XA_STEPS; ++s) {
-            float f[8];
-            unpack8<F16>(xf[s], f);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) { const float d = f[e] - mean; sq = fmaf(d, d, sq); }
-        }
-        sq += __shfl_xor(sq, 32);
-        const float rstd = rsqrtf(sq * (1.0f / XA_C) + p.ln_eps);
-        const float shift = -mean * rstd;
-#pragma unroll
-        for (int s = 0; s < XA_STEPS; ++s) asm volatile("" : "+v"(xf[s].x), "+v"(xf[s].y), "+v"(xf[s].z), "+v"(xf[s].w));
-#pragma unroll
-        for (int s = 0; s < XA_STEPS; ++s) {
-            float f[8];
-            unpack8<F16>(xf[s], f);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) f[e] = fmaf(f[e], rstd, shift);
-            xf[s] = pack8<F16>(f);
-        }
-    }
+    ln_rows_inplace<F16, XA_C>(xf, p.ln_eps);      // norm2 (affine folded into W_q' / b_q' by the caller)
 
     const f32x16 zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     const int wrow = chh * 32 + col;                                     // weight row inside a chunk
@@ -144,7 +103,7 @@ __global__ __launch_bounds__(512, 1) void text_xattn320_kernel(const imd_xattn_p
     uint4 qf[2 * XA_NQ];
 #pragma unroll
     for (int c = 0; c < XA_NQ; ++c) {
-        dma_wait_keep5();                                         // this wave's pieces of chunk c have landed (chunk c + 1 may still fly)
+        dma_wait_keep_n<XA_PIECES>();                                         // this wave's pieces of chunk c have landed (chunk c + 1 may still fly)
         __syncthreads();                                          // ... and everybody else's; all waves are done with chunk c - 1
         stage(c + 2);
         const char* Ws = wlane + (c % XA_RING) * XA_CHUNK;
@@ -163,9 +122,8 @@ __global__ __launch_bounds__(512, 1) void text_xattn320_kernel(const imd_xattn_p
         }
 #pragma unroll
         for (int t = 0; t < 2; ++t) {      // groups 2 t, 2 t + 1 (4 rows each per lane half) -> rows 16 t + 8 hi + 0..7 of the block
-            const auto r0 = __builtin_amdgcn_permlane32_swap(pk[2 * t][0], pk[2 * t + 1][0], false, false);
-            const auto r1 = __builtin_amdgcn_permlane32_swap(pk[2 * t][1], pk[2 * t + 1][1], false, false);
-            qf[2 * c + t] = make_uint4(r0[0], r1[0], r0[1], r1[1]);
+            const v4u w = quads_to_wide(pk[2 * t], pk[2 * t + 1]);
+            qf[2 * c + t] = make_uint4(w[0], w[1], w[2], w[3]);
         }
     }
     // q slot 40 of every head = 1: it meets K column 40 (0 for a key, a large negative value for a pad key)
@@ -184,7 +142,7 @@ __global__ __launch_bounds__(512, 1) void text_xattn320_kernel(const imd_xattn_p
 #pragma unroll
     for (int hl = 0; hl < XA_NKV; ++hl) {
         const int c = XA_NQ + hl;
-        dma_wait_keep5();
+        dma_wait_keep_n<XA_PIECES>();
         __syncthreads();
         stage(c + 2);
         if (hl > 0) {
@@ -249,10 +207,8 @@ __global__ __launch_bounds__(512, 1) void text_xattn320_kernel(const imd_xattn_p
         uint2 rres[4];              // residual in accumulator layout: group j = channels 8 j + 4 hi .. + 3
 #pragma unroll
         for (int t = 0; t < 2; ++t) {
-            uint4 r = rraw[c & 1][t];
-            const auto sx = __builtin_amdgcn_permlane32_swap(r.x, r.z, false, false);
-            const auto sy = __builtin_amdgcn_permlane32_swap(r.y, r.w, false, false);
-            rres[2 * t] = make_uint2(sx[0], sy[0]); rres[2 * t + 1] = make_uint2(sx[1], sy[1]);
+            const uint4 r = wide_to_quads(rraw[c & 1][t]);
+            rres[2 * t] = make_uint2(r.x, r.y); rres[2 * t + 1] = make_uint2(r.z, r.w);
         }
         v2u pk[4];
 #pragma unroll
@@ -264,9 +220,7 @@ __global__ __launch_bounds__(512, 1) void text_xattn320_kernel(const imd_xattn_p
         }
 #pragma unroll
         for (int t = 0; t < 2; ++t) {
-            const auto r0 = __builtin_amdgcn_permlane32_swap(pk[2 * t][0], pk[2 * t + 1][0], false, false);
-            const auto r1 = __builtin_amdgcn_permlane32_swap(pk[2 * t][1], pk[2 * t + 1][1], false, false);
-            const v4u_t w = {r0[0], r1[0], r0[1], r1[1]};
+            const v4u w = quads_to_wide(pk[2 * t], pk[2 * t + 1]);
             const uint32_t off = (uint32_t)((c * 64 + chh * 32 + 16 * t + 8 * hi) * 2);
             __builtin_amdgcn_raw_buffer_store_b128(w, rs_o, (int)(obase == OOB ? OOB : obase + off), 0, 0);
         }
