@@ -136,6 +136,17 @@ class ImagePackParams(_Sized):
                 ("B", C.c_int), ("H", C.c_int), ("W", C.c_int), ("ld", C.c_int), ("dtype", C.c_int)]
 
 
+class ImageOverlayParams(_Sized):
+    _fields_ = [("struct_bytes", C.c_uint32), ("orig", C.c_void_p), ("mask", C.c_void_p), ("gen", C.c_void_p), ("out", C.c_void_p),
+                ("B", C.c_int), ("Bo", C.c_int), ("H0", C.c_int), ("W0", C.c_int),
+                ("x1", C.c_int), ("y1", C.c_int), ("cw", C.c_int), ("ch", C.c_int)]
+
+
+class ImageInpaintConditionParams(_Sized):
+    _fields_ = [("struct_bytes", C.c_uint32), ("image", C.c_void_p), ("mask", C.c_void_p), ("out", C.c_void_p),
+                ("B", C.c_int), ("H", C.c_int), ("W", C.c_int), ("dtype", C.c_int)]
+
+
 # every symbol include/imagdressing_hip.h declares: name -> (restype, argtypes)
 SYMBOLS = {
     "imd_abi_version": (C.c_int, []),
@@ -180,6 +191,8 @@ SYMBOLS = {
     "imd_image_resample": (C.c_int, [C.POINTER(ImageResampleParams), C.c_void_p]),
     "imd_image_resample_form": (C.c_int, [C.POINTER(ImageResampleParams)]),
     "imd_image_pack_u8": (C.c_int, [C.POINTER(ImagePackParams), C.c_void_p]),
+    "imd_image_overlay": (C.c_int, [C.POINTER(ImageOverlayParams), C.c_void_p]),
+    "imd_image_inpaint_condition": (C.c_int, [C.POINTER(ImageInpaintConditionParams), C.c_void_p]),
     "imd_timestep_embedding": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "imd_add": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_long, C.c_int, C.c_float, C.c_int, C.c_void_p]),
     "imd_embed_tokens": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_long, C.c_int, C.c_int, C.c_void_p]),

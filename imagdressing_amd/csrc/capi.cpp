@@ -310,6 +310,18 @@ int imd_image_pack_u8(const imd_image_pack_params* p, void* stream) {
     return imd_launch_image_pack_u8(*p, (hipStream_t)stream);
 }
 
+int imd_image_overlay(const imd_image_overlay_params* p, void* stream) {
+    IMD_REQUIRE(p != nullptr, "image_overlay: null params");
+    IMD_REQUIRE_SIZE(p, "image_overlay");
+    return imd_launch_image_overlay(*p, (hipStream_t)stream);
+}
+
+int imd_image_inpaint_condition(const imd_image_inpaint_condition_params* p, void* stream) {
+    IMD_REQUIRE(p != nullptr, "image_inpaint_condition: null params");
+    IMD_REQUIRE_SIZE(p, "image_inpaint_condition");
+    return imd_launch_image_inpaint_condition(*p, (hipStream_t)stream);
+}
+
 int imd_ddim_cfg_step_rows(const imd_ddim_params* p, const float* guidance, void* stream) {
     IMD_REQUIRE(p != nullptr, "ddim_cfg_step_rows: null params");
     IMD_REQUIRE_SIZE(p, "ddim_cfg_step_rows");

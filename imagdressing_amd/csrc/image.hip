@@ -12,6 +12,14 @@
 //
 // image_pack_u8: decoder output [B, H, W, 4 | 8] 16-bit -> uint8 RGB, rint(clamp(x / 2 + 0.5, 0, 1) * 255) in fp32, so that one
 // byte per channel value crosses to the host instead of four.
+//
+// image_overlay: the inpainting result composited into the person image, Pillow's Image.composite per byte (one rounding):
+// out = orig outside the box, ((t >> 8) + t) >> 8 with t = orig (255 - m) + gen m + 128 inside.  The one bandwidth-bound kernel of this
+// file: a lane owns 16 consecutive bytes of `out` (5 1/3 pixels, at most 6 mask bytes); lanes whose bytes lie in one row and wholly
+// inside or wholly outside the box columns move them as one 16-byte access each (orig, gen -- at whatever byte offset the box gives
+// it -- and out), every other lane (row ends, box edges, the tail of the batch) goes byte by byte.
+//
+// image_inpaint_condition: make_inpaint_condition of the inpainting script on uint8 inputs -> the ControlNet's 16-bit NHWC8 image.
 #include "common.h"
 #include "imd_kernels.h"
 
@@ -188,6 +196,87 @@ __global__ __launch_bounds__(256) void pack_u8_kernel(const bf16_t* __restrict__
     }
 }
 
+typedef __attribute__((ext_vector_type(4))) uint32_t u32x4_t;
+
+struct OverlayGeom {
+    int B, Bo, H0, W0, x1, y1, cw, ch;
+};
+
+IMD_DEVINL uint32_t composite8(uint32_t o, uint32_t g, uint32_t m) {
+    const uint32_t t = o * (255u - m) + g * m + 128u;
+    return ((t >> 8) + t) >> 8;
+}
+
+// 16 bytes at any byte address (the compiler picks the widest access the target allows for an alignment of 1)
+IMD_DEVINL u32x4_t load16(const uint8_t* p) {
+    u32x4_t v;
+    __builtin_memcpy(&v, p, 16);
+    return v;
+}
+
+IMD_DEVINL void store16(uint8_t* p, u32x4_t v) { __builtin_memcpy(p, &v, 16); }
+
+__global__ __launch_bounds__(256) void overlay_kernel(const uint8_t* __restrict__ orig, const uint8_t* __restrict__ mask,
+                                                      const uint8_t* __restrict__ gen, uint8_t* __restrict__ out, OverlayGeom q) {
+    const int rowb = q.W0 * 3;                                   // bytes of a row
+    const long img = (long)q.H0 * rowb, total = (long)q.B * img; // bytes of an image (< 2^31: the launcher checks) and of the batch
+    const long pixels = (long)q.H0 * q.W0, grow = (long)q.cw * 3;
+    const int bx0 = q.x1 * 3, bx1 = (q.x1 + q.cw) * 3;           // the box's byte columns
+    for (long i = blockIdx.x * 256L + threadIdx.x; i * 16 < total; i += (long)gridDim.x * 256L) {
+        const long g0 = i * 16;
+        const int b = (int)(g0 / img), r0 = (int)(g0 - (long)b * img);
+        const int y = r0 / rowb, xb = r0 - y * rowb;
+        const bool whole = g0 + 16 <= total && xb + 16 <= rowb;  // 16 bytes of one row of one image
+        const bool row_in = y >= q.y1 && y < q.y1 + q.ch;
+        const uint8_t* src = orig + (q.Bo == 1 ? (long)r0 : g0);
+        if (whole && (!row_in || xb + 16 <= bx0 || xb >= bx1)) {
+            store16(out + g0, load16(src));
+        } else if (whole && xb >= bx0 && xb + 16 <= bx1) {
+            const u32x4_t o = load16(src);
+            const u32x4_t g = load16(gen + ((long)b * q.ch + (y - q.y1)) * grow + (xb - bx0));
+            const int px = xb / 3, c0 = xb - px * 3, npx = (xb + 15) / 3 - px + 1;          // 6 pixels (5 or 6 when c0 == 0)
+            const uint8_t* mrow = mask + (q.Bo == 1 ? 0L : b * pixels) + (long)y * q.W0 + px;
+            uint64_t mm = 0;
+#pragma unroll
+            for (int j = 0; j < 6; ++j)
+                if (j < npx) mm |= (uint64_t)mrow[j] << (8 * j);
+            u32x4_t w;
+#pragma unroll
+            for (int k = 0; k < 16; ++k) {
+                const uint32_t sh = 8 * (k & 3);
+                const uint32_t m = (uint32_t)(mm >> (8 * ((c0 + k) / 3))) & 255u;
+                const uint32_t v = composite8((o[k >> 2] >> sh) & 255u, (g[k >> 2] >> sh) & 255u, m);
+                w[k >> 2] = (k & 3) ? (w[k >> 2] | (v << sh)) : v;
+            }
+            store16(out + g0, w);
+        } else {
+            for (int k = 0; k < 16 && g0 + k < total; ++k) {
+                const long gk = g0 + k;
+                const int bb = (int)(gk / img), r = (int)(gk - (long)bb * img);
+                const int yy = r / rowb, xx = r - yy * rowb;
+                uint32_t v = orig[q.Bo == 1 ? (long)r : gk];
+                if (yy >= q.y1 && yy < q.y1 + q.ch && xx >= bx0 && xx < bx1) {
+                    const uint32_t m = mask[(q.Bo == 1 ? 0L : bb * pixels) + (long)yy * q.W0 + xx / 3];
+                    v = composite8(v, gen[((long)bb * q.ch + (yy - q.y1)) * grow + (xx - bx0)], m);
+                }
+                out[gk] = (uint8_t)v;
+            }
+        }
+    }
+}
+
+template <bool F16>
+__global__ __launch_bounds__(256) void inpaint_condition_kernel(const uint8_t* __restrict__ image, const uint8_t* __restrict__ mask,
+                                                                uint4* __restrict__ out, long pixels) {
+    for (long i = blockIdx.x * 256L + threadIdx.x; i < pixels; i += (long)gridDim.x * 256L) {
+        const bool masked = __fdiv_rn((float)mask[i], 255.0f) > 0.5f;
+        float f[3];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) f[c] = masked ? -1.0f : __fdiv_rn((float)image[i * 3 + c], 255.0f);
+        out[i] = make_uint4(El<F16>::pack2(f[0], f[1]), El<F16>::pack2(f[2], 0.f), 0u, 0u);
+    }
+}
+
 int grid_1d(long n) {
     const long g = (n + 255) / 256;
     return (int)(g < 1 ? 1 : (g > 65535 ? 65535 : g));
@@ -305,4 +394,30 @@ int imd_launch_image_pack_u8(const ImagePackParams& p, hipStream_t s) {
     else if (p.dtype == IMD_DTYPE_BF16) hipLaunchKernelGGL(pack_u8_kernel<false>, dim3(grid_1d(pixels)), dim3(256), 0, s, p.src, p.out, pixels, p.ld);
     else return imd_set_error("image_pack_u8: unknown dtype %d", p.dtype);
     return imd_check_launch("image_pack_u8");
+}
+
+int imd_launch_image_overlay(const ImageOverlayParams& p, hipStream_t s) {
+    if (!p.orig || !p.mask || !p.gen || !p.out) return imd_set_error("image_overlay: null pointer (orig / mask / gen / out)");
+    if (p.B <= 0 || p.H0 <= 0 || p.W0 <= 0) return imd_set_error("image_overlay: empty image (B %d, %d x %d)", p.B, p.H0, p.W0);
+    if (p.Bo != 1 && p.Bo != p.B) return imd_set_error("image_overlay: Bo (%d) must be 1 (shared) or B (%d)", p.Bo, p.B);
+    if (p.cw < 1 || p.ch < 1) return imd_set_error("image_overlay: empty box (%d x %d)", p.ch, p.cw);
+    if (p.x1 < 0 || p.y1 < 0 || p.cw > p.W0 || p.ch > p.H0 || p.x1 > p.W0 - p.cw || p.y1 > p.H0 - p.ch)
+        return imd_set_error("image_overlay: box (x1 %d, y1 %d, %d x %d) outside the image (%d x %d)", p.x1, p.y1, p.ch, p.cw, p.H0, p.W0);
+    if ((long)p.H0 * p.W0 * 3 > 0x7fffffffL) return imd_set_error("image_overlay: an image of %d x %d exceeds 2^31 bytes", p.H0, p.W0);
+    const OverlayGeom q = {p.B, p.Bo, p.H0, p.W0, p.x1, p.y1, p.cw, p.ch};
+    const long lanes = ((long)p.B * p.H0 * p.W0 * 3 + 15) / 16;
+    hipLaunchKernelGGL(overlay_kernel, dim3(grid_1d(lanes)), dim3(256), 0, s, p.orig, p.mask, p.gen, p.out, q);
+    return imd_check_launch("image_overlay");
+}
+
+int imd_launch_image_inpaint_condition(const ImageInpaintConditionParams& p, hipStream_t s) {
+    if (!p.image || !p.mask || !p.out) return imd_set_error("image_inpaint_condition: null pointer (image / mask / out)");
+    if (p.B <= 0 || p.H <= 0 || p.W <= 0) return imd_set_error("image_inpaint_condition: empty image (B %d, %d x %d)", p.B, p.H, p.W);
+    if ((uintptr_t)p.out & 15) return imd_set_error("image_inpaint_condition: the NHWC8 output must be 16-byte aligned");
+    const long pixels = (long)p.B * p.H * p.W;
+    uint4* out = reinterpret_cast<uint4*>(p.out);
+    if (p.dtype == IMD_DTYPE_F16) hipLaunchKernelGGL(inpaint_condition_kernel<true>, dim3(grid_1d(pixels)), dim3(256), 0, s, p.image, p.mask, out, pixels);
+    else if (p.dtype == IMD_DTYPE_BF16) hipLaunchKernelGGL(inpaint_condition_kernel<false>, dim3(grid_1d(pixels)), dim3(256), 0, s, p.image, p.mask, out, pixels);
+    else return imd_set_error("image_inpaint_condition: unknown dtype %d", p.dtype);
+    return imd_check_launch("image_inpaint_condition");
 }

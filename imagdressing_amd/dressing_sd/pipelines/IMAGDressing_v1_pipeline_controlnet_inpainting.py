@@ -6,8 +6,144 @@ from typing import Any, Callable, Dict, List, Optional, Union
 
 import torch
 
-from ._base import (PipelineBase, RefSAttnProcessor2_0, RequestLayout, as_batch, controlnet_keep, first, min_guidance, per_call_value,
-                    randn_tensor, set_scale_by_type)
+from ...unet import nchw_to_nhwc8
+from ._base import (PipelineBase, RefSAttnProcessor2_0, RequestLayout, StableDiffusionPipelineOutput, as_batch, controlnet_keep, first,
+                    min_guidance, per_call_value, randn_tensor, set_scale_by_type, to_image_tensor)
+
+
+def _pil_images(value, name: str, mode: Optional[str]) -> list:
+    """``image`` / ``mask_image`` of a call with ``padding_mask_crop``, ``overlay`` or the built-in inpaint condition: one PIL image or
+    uint8 array ([H, W], [H, W, C]; [B, H, W, C]: one entry per row) or a list of them -> PIL images (converted to ``mode`` if given)"""
+    import numpy as np
+    from PIL import Image
+    if value is None:
+        raise ValueError(f"padding_mask_crop, overlay and control_image=None need {name} as a PIL image or uint8 array, got None")
+    items = list(value) if isinstance(value, (list, tuple)) else [value]
+    out = []
+    for it in items:
+        if hasattr(it, "convert") and hasattr(it, "resize"):
+            out.append(it)
+            continue
+        a = None if isinstance(it, torch.Tensor) else np.asarray(it)
+        if a is None or a.dtype != np.uint8 or a.ndim not in (2, 3, 4):
+            raise ValueError(f"padding_mask_crop, overlay and control_image=None need {name} as a PIL image or uint8 array "
+                             f"(latents and float tensors cannot be cropped or composited), got {type(it).__name__}")
+        for row in (a if a.ndim == 4 else [a]):
+            out.append(Image.fromarray(row[..., 0] if row.ndim == 3 and row.shape[-1] == 1 else row))
+    if not out:
+        raise ValueError(f"{name} is empty")
+    return [im if mode is None or im.mode == mode else im.convert(mode) for im in out]
+
+
+class _InpaintImages:
+    """The person image(s) and mask(s) of a call that crops (``padding_mask_crop``), composites (``overlay``) or builds the inpaint
+    condition itself: pair j = (image j, mask j) of request j (one pair: shared), its crop box, and its inputs on either image route --
+    the host route through Pillow, the device route (``enable_device_image_io``) from ONE upload of each image as uint8, windows being
+    tensor views."""
+
+    def __init__(self, pipe, image, mask_image, size, pad, device):
+        from ...image import get_crop_region
+        self.pipe, self.size, self.device = pipe, size, torch.device(device)          # size = (height, width), VAE multiples
+        self.images, self.masks = _pil_images(image, "image", "RGB"), _pil_images(mask_image, "mask_image", None)
+        self.n = max(len(self.images), len(self.masks))
+        if len(self.images) not in (1, self.n) or len(self.masks) not in (1, self.n):
+            raise ValueError(f"image has {len(self.images)} entries and mask_image {len(self.masks)} (give one, shared, or one per request)")
+        self.masks_l = [m if m.mode == "L" else m.convert("L") for m in self.masks]
+        for j in range(self.n):
+            if self.image(j).size != self.mask(j).size:
+                raise ValueError(f"image is {self.image(j).size} and mask_image {self.mask(j).size} (width, height): padding_mask_crop / "
+                                 "overlay / control_image=None need them of equal size")
+        self.cropped = pad is not None
+        self.boxes = [get_crop_region(self.mask_l(j), size[1], size[0], pad=pad) if self.cropped
+                      else (0, 0) + self.image(j).size for j in range(self.n)]
+        self.on_device = bool(getattr(pipe, "_device_image_io", False)) and self.device.type == "cuda"
+        self._up = {}
+
+    def image(self, j):
+        return self.images[j if len(self.images) > 1 else 0]
+
+    def mask(self, j):
+        return self.masks[j if len(self.masks) > 1 else 0]
+
+    def mask_l(self, j):
+        return self.masks_l[j if len(self.masks) > 1 else 0]
+
+    def uploaded(self, kind: str, j: int) -> torch.Tensor:
+        """uint8 [1, H0, W0, 3 | 1] on the device: kind "image" (RGB), "mask_l" (L) or "mask_rgb", uploaded once"""
+        src, mode = {"image": (self.images, "RGB"), "mask_l": (self.masks_l, "L"), "mask_rgb": (self.masks, "RGB")}[kind]
+        key = (kind, j if len(src) > 1 else 0)
+        if key not in self._up:
+            self._up[key] = self.pipe._image_processor()._upload(src[key[1]], mode)
+        return self._up[key]
+
+    @staticmethod
+    def window(t: torch.Tensor, box) -> torch.Tensor:
+        x1, y1, x2, y2 = box
+        return t[:, y1:y2, x1:x2, :]
+
+    def image_tensor(self, multiple: int) -> torch.Tensor:
+        """the windows of the person images, Lanczos to the processing size, in [-1, 1]: fp32 [n, 3, H, W]"""
+        if self.on_device:
+            views = [self.window(self.uploaded("image", j), self.boxes[j]) for j in range(self.n)]
+            return self.pipe._image_processor().preprocess(views, size=self.size, resample="lanczos", out="nchw", normalize=True, multiple=multiple)
+        return to_image_tensor([self.image(j).crop(self.boxes[j]) for j in range(self.n)], self.device, True, size=self.size, multiple=multiple)
+
+    def mask_latents(self, h: int, w: int) -> torch.Tensor:
+        """the windows of the masks, binarised at 0.5 and nearest-resized to the latent size: fp32 [n, 1, h, w]"""
+        rows = []
+        for j in range(self.n):
+            if self.on_device:
+                gray = self.mask(j).mode in ("1", "L")          # (their RGB conversion repeats the one channel)
+                view = self.window(self.uploaded("mask_l" if gray else "mask_rgb", j), self.boxes[j])
+                m = self.pipe._image_processor().preprocess(view, size=None, out="nchw", normalize=False, binarize=True,
+                                                            mode="L" if gray else "RGB")[:, :1]
+            else:
+                m = to_image_tensor(self.mask(j).crop(self.boxes[j]), self.device, False)[:, :1]
+            rows.append(torch.nn.functional.interpolate((m >= 0.5).float(), size=(h, w)))
+        return torch.cat(rows)
+
+    def control(self, control_image, multiple: int) -> torch.Tensor:
+        """the ControlNet image per pair: ``control_image`` (PIL / uint8: window, Lanczos; a float tensor [*, 3, H0, W0] of the image's
+        size: window, nearest -- the -1 markers of ``make_inpaint_condition`` survive), or for None that condition built here at the
+        processing size.  fp32 NCHW [n, 3, H, W] on the host route, the engines' NHWC8 on the device route."""
+        from ...image import inpaint_condition_host
+        if control_image is None:
+            if self.on_device:
+                proc = self.pipe._image_processor()
+                return torch.cat([proc.inpaint_condition(self.uploaded("image", j), self.uploaded("mask_l", j), self.size,
+                                                         self.boxes[j] if self.cropped else None) for j in range(self.n)])
+            conds = [inpaint_condition_host(self.image(j), self.mask_l(j), self.boxes[j] if self.cropped else None, self.size)
+                     for j in range(self.n)]
+            return torch.stack([torch.from_numpy(c) for c in conds]).permute(0, 3, 1, 2).to(self.device)
+        if isinstance(control_image, torch.Tensor):
+            entries = [control_image[None]] if control_image.dim() == 3 else [control_image[i:i + 1] for i in range(control_image.shape[0])]
+        else:
+            entries = [e[None] if isinstance(e, torch.Tensor) and e.dim() == 3 else e
+                       for e in (control_image if isinstance(control_image, (list, tuple)) else [control_image])]
+        if len(entries) not in (1, self.n):
+            raise ValueError(f"control_image has {len(entries)} entries for {self.n} image / mask pairs")
+        rows = []
+        for j in range(self.n):
+            e, (x1, y1, x2, y2) = entries[j if len(entries) > 1 else 0], self.boxes[j]
+            W0, H0 = self.image(j).size
+            if isinstance(e, torch.Tensor):
+                if not e.is_floating_point() or e.dim() != 4 or tuple(e.shape[-2:]) != (H0, W0):
+                    raise ValueError(f"padding_mask_crop: a tensor control_image is a float [*, 3, {H0}, {W0}] tensor of the image's size "
+                                     f"(only then the crop window is defined), got {e.dtype} {tuple(e.shape)}")
+                rows.append(to_image_tensor(e[..., y1:y2, x1:x2], self.device, False, size=self.size, multiple=multiple))
+                continue
+            pil = _pil_images(e, "control_image", "RGB")[0]
+            if pil.size != (W0, H0):
+                raise ValueError(f"padding_mask_crop: control_image is {pil.size} and image {(W0, H0)} (width, height)")
+            if self.on_device:
+                view = self.window(self.pipe._image_processor()._upload(pil, "RGB"), self.boxes[j])
+                rows.append(self.pipe._image_processor().preprocess(view, size=self.size, resample="lanczos", out="nhwc8", normalize=False,
+                                                                    multiple=multiple))
+            else:
+                rows.append(to_image_tensor(pil.crop(self.boxes[j]), self.device, False, size=self.size, multiple=multiple))
+        if any(r.shape[-1] == 8 and r.dtype == self.pipe.unet.dtype for r in rows):          # device route: every row in the engines' layout
+            rows = [r if r.shape[-1] == 8 and r.dtype == self.pipe.unet.dtype else nchw_to_nhwc8(r.to(self.device), self.pipe.unet.dtype) for r in rows]
+        return torch.cat(rows)
 
 
 class IMAGDressing_v1(PipelineBase):
@@ -28,6 +164,35 @@ class IMAGDressing_v1(PipelineBase):
         x = self._image_tensor(image, p.device, normalize=True, size=size, multiple=self.vae_scale_factor)[0].to(p.dtype)
         return self.vae.encode(x).latent_dist.sample(generator) * self.vae.config.scaling_factor
 
+    def _decode_overlay(self, latents, output_type, front: _InpaintImages):
+        """``_decode`` to uint8, then every image composited into its request's person image (``overlay=True``): the decoded image
+        Lanczos-resized to the request's box, pasted, and ``Image.composite`` with the original through the unbinarised mask.  Host
+        route: those Pillow calls.  Device route: pack, one resample and one ``imd_image_overlay`` launch per request, one copy back."""
+        import numpy as np
+        from ...image import overlay_host
+        B = latents.shape[0]
+        per = B // front.n if front.n > 1 else B                        # rows of one image / mask pair (request-major)
+        if front.on_device:
+            if not hasattr(self.vae, "decode_nhwc"):
+                raise TypeError("enable_device_image_io() needs the engine VAE (imagdressing_amd.vae.AutoencoderKL.decode_nhwc), got "
+                                f"{type(self.vae).__module__}.{type(self.vae).__name__}")
+            proc = self._image_processor()
+            parts = [proc.pack(y) for y in self._decode_nhwc(latents)]
+            packed = parts[0] if len(parts) == 1 else torch.cat(parts)
+            same = len({front.image(j).size for j in range(front.n)}) == 1
+            W0, H0 = front.image(0).size
+            whole = torch.empty(B, H0, W0, 3, dtype=torch.uint8, device=packed.device) if same else None
+            outs = [proc.overlay(packed[j * per:(j + 1) * per], front.uploaded("image", j), front.uploaded("mask_l", j), front.boxes[j],
+                                 out=None if whole is None else whole[j * per:(j + 1) * per]) for j in range(B // per)]
+            arrs = list(whole.cpu().numpy()) if same else [a for o in outs for a in o.cpu().numpy()]
+        else:
+            dec = self._decode(latents, "np").images
+            arrs = [np.asarray(overlay_host(dec[b], front.image(b // per), front.mask_l(b // per), front.boxes[b // per])) for b in range(B)]
+        if output_type == "np":
+            return StableDiffusionPipelineOutput(images=np.stack(arrs), nsfw_content_detected=None)
+        from PIL import Image
+        return StableDiffusionPipelineOutput(images=[Image.fromarray(a) for a in arrs], nsfw_content_detected=None)
+
     @torch.no_grad()
     def __call__(self, prompt, null_prompt, negative_prompt, ref_image, width, height, num_inference_steps, guidance_scale,
                  ref_clip_image=None, num_images_per_prompt=1, image_scale=1.0, num_samples=1, strength: float = 1.0,
@@ -42,7 +207,8 @@ class IMAGDressing_v1(PipelineBase):
                  control_guidance_start: Union[float, List[float]] = 0.0, control_guidance_end: Union[float, List[float]] = 1.0,
                  ref_clip_hidden_states: Optional[torch.Tensor] = None, ref_image_latents: Optional[torch.Tensor] = None,
                  image_latents: Optional[torch.Tensor] = None, mask_latents: Optional[torch.Tensor] = None,
-                 noise: Optional[torch.Tensor] = None, shard_over_ranks: bool = False, trace: Optional[list] = None, **kwargs):
+                 noise: Optional[torch.Tensor] = None, shard_over_ranks: bool = False, trace: Optional[list] = None,
+                 overlay: bool = False, **kwargs):
         R = self._request_count(dict(prompt=prompt, prompt_embeds=prompt_embeds, negative_prompt=negative_prompt, null_prompt=null_prompt,
                                      negative_prompt_embeds=negative_prompt_embeds, ref_image=ref_image, ref_clip_image=ref_clip_image,
                                      ref_clip_hidden_states=ref_clip_hidden_states, ref_image_latents=ref_image_latents,
@@ -52,9 +218,22 @@ class IMAGDressing_v1(PipelineBase):
                                      controlnet_conditioning_scale=controlnet_conditioning_scale), shard_over_ranks)
         num_inference_steps, strength, eta = (per_call_value("num_inference_steps", num_inference_steps), per_call_value("strength", strength),
                                               per_call_value("eta", eta))
-        if guess_mode or min_guidance(guidance_scale) <= 1.0 or padding_mask_crop is not None or timesteps:
-            raise NotImplementedError("guess_mode, guidance_scale <= 1, padding_mask_crop and custom timesteps are not implemented "
+        if guess_mode or min_guidance(guidance_scale) <= 1.0 or timesteps:
+            raise NotImplementedError("guess_mode, guidance_scale <= 1 and custom timesteps are not implemented "
                                       "(the reference script uses none of them)")
+        # padding_mask_crop / overlay / control_image=None (the condition built here): the image and mask as images, one box per request
+        front = None
+        if padding_mask_crop is not None or overlay or (control_image is None and image is not None and mask_image is not None):
+            if padding_mask_crop is not None and (image_latents is not None or mask_latents is not None):
+                raise ValueError("padding_mask_crop crops image and mask_image; image_latents / mask_latents cannot be cropped")
+            if overlay and output_type not in ("pil", "np"):
+                raise ValueError(f"overlay=True composites uint8 images: output_type must be 'pil' or 'np', got {output_type!r}")
+            if overlay and shard_over_ranks:
+                raise NotImplementedError("overlay=True with shard_over_ranks: each rank holds a part of the rows; composite per rank instead")
+            vsf = self.vae_scale_factor
+            front = _InpaintImages(self, image, mask_image, (height // vsf * vsf, width // vsf * vsf), padding_mask_crop, self.device)
+            if overlay and output_type == "np" and len({front.image(j).size for j in range(front.n)}) > 1:
+                raise ValueError("overlay=True with output_type='np' needs person images of one size (one array holds them); use 'pil'")
         if not 0.0 < float(strength) <= 1.0:
             raise ValueError(f"The value of strength should in (0.0, 1.0] but is {strength}")           # diffusers check_inputs (0.0 leaves no step)
         callback = kwargs.pop("callback", None)
@@ -68,8 +247,12 @@ class IMAGDressing_v1(PipelineBase):
         ref_lat, cloth_tokens, G = self._request_garments(R, null_prompt, ref_image, ref_image_latents, ref_clip_image,
                                                           ref_clip_hidden_states, device)
         steps_run = min(int(num_inference_steps * float(strength)), num_inference_steps)          # the gate is over the timesteps actually run (:376-381)
-        control = dict(image=self._image_tensor(as_batch(control_image, "control_image"), device, normalize=False, size=(height, width),
-                                                multiple=self.vae_scale_factor, layout="nhwc8")[0],
+        if front is not None and (front.cropped or control_image is None):
+            control_tensor = front.control(control_image, self.vae_scale_factor)
+        else:
+            control_tensor = self._image_tensor(as_batch(control_image, "control_image"), device, normalize=False, size=(height, width),
+                                                multiple=self.vae_scale_factor, layout="nhwc8")[0]
+        control = dict(image=control_tensor,
                        prompt_embeds=prompt_embeds,
                        negative_prompt_embeds=negative_prompt_embeds, scale=float(first(controlnet_conditioning_scale)),
                        keep=controlnet_keep(max(steps_run, 1), float(first(control_guidance_start)), float(first(control_guidance_end))))
@@ -78,7 +261,11 @@ class IMAGDressing_v1(PipelineBase):
         # strength == 1.0: start from pure noise; the SAME noise re-noises the original latents in the blend (:496-498).
         # strength < 1.0 (:316-341 -> diffusers get_timesteps / prepare_latents): run the last int(steps * strength) timesteps,
         # starting from add_noise(image_latents, noise, first of them).  Explicit ``latents`` are taken as the noise, as diffusers does.
-        if image_latents is None:                                             # (before the noise draw, like diffusers' prepare_latents)
+        if image_latents is None and front is not None and front.cropped:
+            p = next(self.vae.parameters())
+            x = front.image_tensor(self.vae_scale_factor).to(device=p.device, dtype=p.dtype)
+            image_latents = self.vae.encode(x).latent_dist.sample(generator) * self.vae.config.scaling_factor
+        elif image_latents is None:                                           # (before the noise draw, like diffusers' prepare_latents)
             image_latents = self._image_latents(as_batch(image, "image"), device, generator, size=(height, width))
         if noise is None:
             noise = latents if latents is not None else randn_tensor((B, 4, h, w), generator=generator, device=device, dtype=torch.float32)
@@ -96,7 +283,9 @@ class IMAGDressing_v1(PipelineBase):
             if il.shape[0] != B:                                              # one person image shared, or one per request (request-major rows)
                 il = il.expand(B, -1, -1, -1) if il.shape[0] == 1 else RequestLayout(R, num_images_per_prompt).expand(il, "image / image_latents")
             lat = self.scheduler.add_noise(il, noise.to(device=device, dtype=torch.float32), t0)
-        if mask_latents is None:                                              # prepare_mask_latents: nearest resize to h x w
+        if mask_latents is None and front is not None and front.cropped:
+            mask_latents = front.mask_latents(h, w)
+        elif mask_latents is None:                                            # prepare_mask_latents: nearest resize to h x w
             m = self._image_tensor(as_batch(mask_image, "mask_image"), device, normalize=False, binarize=True)[0][:, :1]
             m = (m >= 0.5).float()
             mask_latents = torch.nn.functional.interpolate(m, size=(h, w))
@@ -108,4 +297,6 @@ class IMAGDressing_v1(PipelineBase):
                            control=control, inpaint=inpaint, callback=callback, callback_steps=callback_steps, trace=trace,
                            eta=eta, generator=generator, variance_noise=kwargs.get("variance_noise"), t_start=t_start,
                            requests=R, image_scale=scale_rows)
+        if overlay:
+            return self._decode_overlay(out, output_type, front)
         return self._decode(out, output_type, generator)

@@ -516,6 +516,14 @@ class PipelineBase:
         p = next(self.vae.parameters())
         return self.vae.encode(ref_image.to(dtype=p.dtype, device=p.device)).latent_dist.mean * 0.18215   # :457-458
 
+    def _decode_nhwc(self, latents) -> list:
+        """final latents -> the decoder's 16-bit NHWC output, one tensor (or one per image: VAE slicing) -- the device image route"""
+        p = next(self.vae.parameters())
+        z = (latents / self.vae.config.scaling_factor).to(p.dtype)
+        ops.ensure_device(z.device)
+        slices = z.split(1) if getattr(self.vae, "use_slicing", False) and z.shape[0] > 1 else (z,)
+        return [self.vae.decode_nhwc(nchw_to_nhwc8(zb.float(), self.vae.dtype)) for zb in slices]       # (AutoencoderKL.decode, without its NCHW copy)
+
     def _decode(self, latents, output_type, generator=None):
         if output_type == "latent":
             return StableDiffusionPipelineOutput(images=latents, nsfw_content_detected=None)
@@ -524,10 +532,7 @@ class PipelineBase:
             if not hasattr(self.vae, "decode_nhwc"):
                 raise TypeError("enable_device_image_io() needs the engine VAE (imagdressing_amd.vae.AutoencoderKL.decode_nhwc), got "
                                 f"{type(self.vae).__module__}.{type(self.vae).__name__}")
-            z = (latents / self.vae.config.scaling_factor).to(p.dtype)
-            ops.ensure_device(z.device)
-            slices = z.split(1) if getattr(self.vae, "use_slicing", False) and z.shape[0] > 1 else (z,)
-            ys = [self.vae.decode_nhwc(nchw_to_nhwc8(zb.float(), self.vae.dtype)) for zb in slices]       # (AutoencoderKL.decode, without its NCHW copy)
+            ys = self._decode_nhwc(latents)
             return StableDiffusionPipelineOutput(images=self._image_processor().postprocess(ys, output_type), nsfw_content_detected=None)
         image = self.vae.decode((latents / self.vae.config.scaling_factor).to(p.dtype), return_dict=False)[0]
         image = (image.float() / 2 + 0.5).clamp(0, 1)

@@ -6,6 +6,10 @@ horizontal one.  ``resample_tables`` builds the table in float64 exactly as Pill
 applies it on the GPU and fuses what follows the resize on the host today -- crop, /255, normalisation, the NCHW / NHWC8 layout.
 ``resample_reference`` is the same integer formula in numpy (tests, tools/make_image_goldens.py).
 
+``get_crop_region`` (``padding_mask_crop`` of the inpainting pipeline), ``overlay_host`` / ``overlay_reference`` and
+``inpaint_condition_host`` are the host side of the inpainting front and back end; ``DeviceImageProcessor.overlay`` /
+``.inpaint_condition`` give the same bytes from the GPU (``imd_image_overlay``, ``imd_image_inpaint_condition``).
+
 ``DeviceImageProcessor`` is what the pipelines use after ``enable_device_image_io()``: the only host work left per image is
 ``convert("RGB" | "L")``, one copy of the uint8 pixels into pinned memory and their upload; the decoder's output comes back as ONE uint8 copy instead of fp32 NCHW.
 """
@@ -167,6 +171,100 @@ def _is_pil(im) -> bool:
     return hasattr(im, "convert") and hasattr(im, "resize")
 
 
+def mask_as_l(mask) -> np.ndarray:
+    """a mask -- PIL image of any mode, uint8 [H, W], [H, W, 1] or [H, W, 3] -- as "L": uint8 [H, W]"""
+    if not _is_pil(mask):
+        a = np.asarray(mask)
+        if a.dtype != np.uint8 or a.ndim not in (2, 3) or (a.ndim == 3 and a.shape[-1] not in (1, 3)):
+            raise TypeError(f"a mask is a PIL image or a uint8 [H, W], [H, W, 1] or [H, W, 3] array, got {a.dtype} {a.shape}")
+        if a.ndim == 2 or a.shape[-1] == 1:
+            return np.ascontiguousarray(a.reshape(a.shape[0], a.shape[1]))
+        from PIL import Image
+        mask = Image.fromarray(a)
+    return np.asarray(mask.convert("L"))
+
+
+def get_crop_region(mask, width: int, height: int, pad: int = 0) -> Tuple[int, int, int, int]:
+    """diffusers' ``VaeImageProcessor.get_crop_region``: the box (x1, y1, x2, y2) around the non-zero pixels of ``mask`` (a PIL image or
+    uint8 array, read as "L"), grown by ``pad`` and then along one axis to the aspect ratio of the processing size ``width`` x
+    ``height``, kept inside the image.  An all-zero mask raises ValueError (the library divides by zero there)."""
+    m = mask_as_l(mask)
+    h, w = m.shape
+    cols, rows = np.flatnonzero(m.any(axis=0)), np.flatnonzero(m.any(axis=1))
+    if cols.size == 0:
+        raise ValueError("get_crop_region: the mask is all zero, there is no region to crop to")
+    crop_left, crop_right = int(cols[0]), w - 1 - int(cols[-1])
+    crop_top, crop_bottom = int(rows[0]), h - 1 - int(rows[-1])
+    pad = int(pad)
+    x1, y1 = max(crop_left - pad, 0), max(crop_top - pad, 0)
+    x2, y2 = min(w - crop_right + pad, w), min(h - crop_bottom + pad, h)
+    ratio_crop, ratio_processing = (x2 - x1) / (y2 - y1), width / height
+    if ratio_crop > ratio_processing:
+        d = int((x2 - x1) / ratio_processing - (y2 - y1))
+        y1 -= d // 2
+        y2 += d - d // 2
+        if y2 >= h:
+            diff = y2 - h
+            y2 -= diff
+            y1 -= diff
+        if y1 < 0:
+            y2 -= y1
+            y1 = 0
+        if y2 >= h:
+            y2 = h
+    else:
+        d = int((y2 - y1) * ratio_processing - (x2 - x1))
+        x1 -= d // 2
+        x2 += d - d // 2
+        if x2 >= w:
+            diff = x2 - w
+            x2 -= diff
+            x1 -= diff
+        if x1 < 0:
+            x2 -= x1
+            x1 = 0
+        if x2 >= w:
+            x2 = w
+    return x1, y1, x2, y2
+
+
+def overlay_reference(orig: np.ndarray, gen: np.ndarray, mask: np.ndarray, box: Tuple[int, int, int, int]) -> np.ndarray:
+    """``Image.composite`` in numpy: uint8 ``orig`` [..., H0, W0, 3], ``mask`` [..., H0, W0], ``gen`` [..., ch, cw, 3] already at the size
+    of ``box`` = (x1, y1, x2, y2) -> ``orig`` outside the box, ((t >> 8) + t) >> 8 with t = orig (255 - m) + gen m + 128 inside."""
+    x1, y1, x2, y2 = box
+    out = np.array(np.broadcast_to(orig, gen.shape[:-3] + orig.shape[-3:]))
+    o = out[..., y1:y2, x1:x2, :].astype(np.uint32)
+    m = np.asarray(mask)[..., y1:y2, x1:x2, None].astype(np.uint32)
+    t = o * (255 - m) + gen.astype(np.uint32) * m + 128
+    out[..., y1:y2, x1:x2, :] = (((t >> 8) + t) >> 8).astype(np.uint8)
+    return out
+
+
+def overlay_host(gen: np.ndarray, orig, mask, box: Tuple[int, int, int, int]):
+    """The host route of ``overlay=True``: decoded uint8 ``gen`` [H, W, 3] resized to ``box`` = (x1, y1, x2, y2) with Lanczos, pasted
+    into a copy of the PIL image ``orig`` ("RGB") and composited with ``orig`` through the PIL mask ``mask`` ("L") -> PIL image"""
+    from PIL import Image
+    x1, y1, x2, y2 = box
+    gen_r = Image.fromarray(gen).resize((x2 - x1, y2 - y1), Image.LANCZOS)
+    base = orig.copy()
+    base.paste(gen_r, (x1, y1))
+    return Image.composite(base, orig, mask)
+
+
+def inpaint_condition_host(image, mask, box: Optional[Tuple[int, int, int, int]], size: Tuple[int, int]) -> np.ndarray:
+    """The inpainting script's ``make_inpaint_condition`` at the processing size: the window ``box`` (None: all) of the PIL ``image``
+    ("RGB") and ``mask`` ("L"), each resized with Lanczos to ``size`` = (height, width) -> fp32 [H, W, 3]: image / 255, -1 in the
+    three channels where mask / 255 > 0.5."""
+    from PIL import Image
+    if box is not None:
+        image, mask = image.crop(box), mask.crop(box)
+    img_r = np.asarray(image.resize((size[1], size[0]), Image.LANCZOS))
+    m_r = np.asarray(mask.resize((size[1], size[0]), Image.LANCZOS))
+    cond = img_r.astype(np.float32) / 255.0
+    cond[m_r.astype(np.float32) / 255.0 > 0.5] = -1.0
+    return cond
+
+
 class DeviceImageProcessor:
     """Image input and output of the pipelines on the GPU.  ``dtype`` is the 16-bit type of the engines (``out="nhwc8"``,
     ``clip_preprocess``)."""
@@ -201,6 +299,8 @@ class DeviceImageProcessor:
         if not t.is_cuda:
             t = t.contiguous()
             t = (t if t.is_pinned() or self.device.type != "cuda" else t.pin_memory()).to(self.device, non_blocking=True)
+        elif t.stride(3) == 1 and t.stride(2) == want:
+            return t                           # a window of an uploaded image (rows strided): ``imd_image_resample`` reads it in place
         return t.contiguous()
 
     @staticmethod
@@ -267,7 +367,27 @@ class DeviceImageProcessor:
             i += n
         return dst if self.dtype == torch.float32 else dst.to(self.dtype)
 
+    def inpaint_condition(self, image, mask, size: Tuple[int, int], box: Optional[Tuple[int, int, int, int]] = None) -> torch.Tensor:
+        """``inpaint_condition_host`` on the device: ``image`` (PIL / uint8 [1, H0, W0, 3]) and ``mask`` ("L"; PIL / uint8 [1, H0, W0, 1]),
+        their window ``box`` = (x1, y1, x2, y2) resized with Lanczos to ``size`` = (height, width) -> ``dtype`` [1, H, W, 8], the
+        16-bit rounding of the host values"""
+        img, m = self._upload(image, "RGB"), self._upload(mask, "L")
+        if img.shape[:3] != m.shape[:3]:
+            raise ValueError(f"inpaint_condition: the image is {tuple(img.shape[1:3])} and the mask {tuple(m.shape[1:3])}")
+        if box is not None:
+            x1, y1, x2, y2 = box
+            img, m = img[:, y1:y2, x1:x2, :], m[:, y1:y2, x1:x2, :]
+        return ops.image_inpaint_condition(resize_to(img, size, "lanczos"), resize_to(m, size, "lanczos"), self.dtype)
+
     # ---- output ----
+    def overlay(self, decoded: torch.Tensor, orig, mask, box: Tuple[int, int, int, int], out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """``overlay_host`` on the device: uint8 ``decoded`` [B, H, W, 3] (``pack``) resized to ``box`` = (x1, y1, x2, y2) with Lanczos and
+        composited into ``orig`` (PIL / uint8 [1 | B, H0, W0, 3]) through ``mask`` ("L"; PIL / uint8 [1 | B, H0, W0, 1]) ->
+        uint8 [B, H0, W0, 3] on the device"""
+        x1, y1, x2, y2 = (int(v) for v in box)
+        gen = resize_to(self._upload(decoded, "RGB"), (y2 - y1, x2 - x1), "lanczos")
+        return ops.image_overlay(self._upload(orig, "RGB").contiguous(), self._upload(mask, "L").contiguous(), gen, (x1, y1, x2, y2), out=out)
+
     def pack(self, nhwc16: torch.Tensor) -> torch.Tensor:
         """decoder output [B, H, W, 4 | 8] 16-bit -> uint8 [B, H, W, 3] on the device"""
         return ops.image_pack_u8(nhwc16)
@@ -285,4 +405,5 @@ class DeviceImageProcessor:
         return [Image.fromarray(a) for a in arr]
 
 
-__all__ = ["resample_tables", "resample_reference", "tile_rows", "device_tables", "resize_to", "DeviceImageProcessor", "CLIP_MEAN", "CLIP_STD"]
+__all__ = ["resample_tables", "resample_reference", "tile_rows", "device_tables", "resize_to", "DeviceImageProcessor", "CLIP_MEAN", "CLIP_STD",
+           "get_crop_region", "mask_as_l", "overlay_reference", "overlay_host", "inpaint_condition_host"]

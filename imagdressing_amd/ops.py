@@ -1266,7 +1266,8 @@ def sampler_step(z, eps, x_next, *, guidance, coefs, hist=None, noise=None, mask
 IMAGE_U8, IMAGE_F32_NCHW, IMAGE_16_NHWC8 = 0, 1, 2          # IMD_IMG_*
 IMAGE_FORCE_TWO_PASS = 1                                    # IMD_IMG_FORCE_TWO_PASS
 IMAGE_TILE_W, IMAGE_TILE_H, IMAGE_LDS_BYTES = 32, 8, 32768  # IMD_IMG_TILE_W / _TILE_H / _LDS_BYTES
-IMAGE_IO_COUNTER = {"resample": 0, "resample_single": 0, "resample_two_pass": 0, "pack_u8": 0}      # calls made (tests, tools/image_io_bench.py)
+IMAGE_IO_COUNTER = {"resample": 0, "resample_single": 0, "resample_two_pass": 0, "pack_u8": 0, "overlay": 0,
+                    "inpaint_condition": 0}                 # calls made (tests, tools/image_io_bench.py, tools/inpaint_overlay_bench.py)
 
 
 def image_resample(src: torch.Tensor, size: Tuple[int, int], table_h: Optional[dict], table_v: Optional[dict], *, kind: int = IMAGE_U8,
@@ -1344,6 +1345,67 @@ def image_pack_u8(x: torch.Tensor) -> torch.Tensor:
     p.B, p.H, p.W, p.ld = (int(v) for v in x.shape)
     L.check(L.load().imd_image_pack_u8(C.byref(p), _stream()))
     IMAGE_IO_COUNTER["pack_u8"] += 1
+    return out
+
+
+def _u8_images(t, name: str, channels: int):
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise L.ImdError(f"{name}: tensor is on {getattr(t, 'device', type(t))}; imagdressing_amd runs on MI355X only (no CPU path)")
+    want = 4 if channels else 3
+    if t.dtype != torch.uint8 or t.dim() != want or (channels and t.shape[-1] != channels) or not t.is_contiguous():
+        raise L.ImdError(f"{name}: expected contiguous uint8 [B, H, W{', %d' % channels if channels else ''}], got {t.dtype} {tuple(t.shape)}")
+    return t
+
+
+def image_overlay(orig: torch.Tensor, mask: torch.Tensor, gen: torch.Tensor, box: Tuple[int, int, int, int],
+                  out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``Image.composite(orig with gen pasted at the box, orig, mask)`` per byte on the device: uint8 ``orig`` [Bo, H0, W0, 3] and
+    ``mask`` [Bo, H0, W0] (Bo = 1: shared by every output, or B), ``gen`` [B, ch, cw, 3] = the generated window at the size of ``box``
+    = (x1, y1, x2, y2) -> uint8 [B, H0, W0, 3]: ``orig`` outside the box, ((t >> 8) + t) >> 8 with t = orig (255 - m) + gen m + 128
+    inside."""
+    orig, gen = _u8_images(orig, "orig", 3), _u8_images(gen, "gen", 3)
+    if isinstance(mask, torch.Tensor) and mask.dim() == 4 and mask.shape[-1] == 1:
+        mask = mask[..., 0]
+    mask = _u8_images(mask, "mask", 0)
+    ensure_device(orig.device)
+    x1, y1, x2, y2 = (int(v) for v in box)
+    B, Bo, H0, W0 = int(gen.shape[0]), int(orig.shape[0]), int(orig.shape[1]), int(orig.shape[2])
+    if tuple(mask.shape) != (Bo, H0, W0):
+        raise L.ImdError(f"mask: expected {(Bo, H0, W0)} beside orig {tuple(orig.shape)}, got {tuple(mask.shape)}")
+    if tuple(gen.shape[1:3]) != (y2 - y1, x2 - x1):
+        raise L.ImdError(f"gen: the box {tuple(box)} is {y2 - y1} x {x2 - x1}, gen is {tuple(gen.shape)}")
+    if out is None:
+        out = torch.empty(B, H0, W0, 3, dtype=torch.uint8, device=orig.device)
+    elif tuple(out.shape) != (B, H0, W0, 3):
+        raise L.ImdError(f"out: expected shape {(B, H0, W0, 3)}, got {tuple(out.shape)}")
+    p = L.ImageOverlayParams()
+    p.orig, p.mask, p.gen, p.out = orig.data_ptr(), mask.data_ptr(), gen.data_ptr(), _dev(out, torch.uint8, "out")
+    p.B, p.Bo, p.H0, p.W0 = B, Bo, H0, W0
+    p.x1, p.y1, p.cw, p.ch = x1, y1, x2 - x1, y2 - y1
+    L.check(L.load().imd_image_overlay(C.byref(p), _stream()))
+    IMAGE_IO_COUNTER["overlay"] += 1
+    return out
+
+
+def image_inpaint_condition(image: torch.Tensor, mask: torch.Tensor, dtype) -> torch.Tensor:
+    """uint8 ``image`` [B, H, W, 3] and ``mask`` [B, H, W] (or [B, H, W, 1]) -> the inpainting ControlNet's condition, ``dtype``
+    [B, H, W, 8]: image / 255, -1 in the three channels where mask / 255 > 0.5, channels 3..7 zero."""
+    image = _u8_images(image, "image", 3)
+    if isinstance(mask, torch.Tensor) and mask.dim() == 4 and mask.shape[-1] == 1:
+        mask = mask[..., 0]
+    mask = _u8_images(mask, "mask", 0)
+    if tuple(mask.shape) != tuple(image.shape[:3]):
+        raise L.ImdError(f"mask: expected {tuple(image.shape[:3])} beside image {tuple(image.shape)}, got {tuple(mask.shape)}")
+    if dtype not in DTYPE_CODE:
+        raise L.ImdError(f"image_inpaint_condition: the output is bfloat16 or float16, got {dtype}")
+    ensure_device(image.device)
+    out = torch.empty(*image.shape[:3], 8, dtype=dtype, device=image.device)
+    p = L.ImageInpaintConditionParams()
+    p.image, p.mask, p.out = image.data_ptr(), mask.data_ptr(), out.data_ptr()
+    p.B, p.H, p.W = (int(v) for v in image.shape[:3])
+    p.dtype = _code(out, "out")
+    L.check(L.load().imd_image_inpaint_condition(C.byref(p), _stream()))
+    IMAGE_IO_COUNTER["inpaint_condition"] += 1
     return out
 
 

@@ -369,6 +369,40 @@ typedef struct imd_image_pack_params {
     int dtype;             /* IMD_DTYPE_* of src */
 } imd_image_pack_params;
 
+/* Inpainting result composited into the person image on the device (imd_image_overlay): what diffusers' apply_overlay does on the
+ * host behind StableDiffusionControlNetInpaintPipeline, as ONE Image.composite(base, orig, mask) -- base = orig with the generated
+ * window pasted at (x1, y1) -- per byte, integer only:
+ *   inside the box  [y1, y1 + ch) x [x1, x1 + cw):  t = orig * (255 - m) + gen * m + 128;  out = ((t >> 8) + t) >> 8
+ *   outside:                                        out = orig
+ * with m = mask[b][y][x] (not binarised: a feathered mask feathers the seam); m = 0 returns orig and m = 255 returns gen exactly.
+ * Equal to Pillow's Image.composite on all 256^3 (orig, gen, m) triples.  gen is the decoded window already resized to the box
+ * (imd_image_resample, IMD_IMG_U8).  orig / mask hold Bo = 1 image shared by the B outputs, or B.  No pointer needs any alignment.
+ * Refused: null pointers, an empty image or box, Bo other than 1 or B, a box outside the image, an image of more than 2^31 bytes. */
+typedef struct imd_image_overlay_params {
+    uint32_t struct_bytes; /* sizeof(imd_image_overlay_params) in the caller's view; checked on entry */
+    const uint8_t* orig;   /* uint8 [Bo, H0, W0, 3] */
+    const uint8_t* mask;   /* uint8 [Bo, H0, W0] */
+    const uint8_t* gen;    /* uint8 [B, ch, cw, 3] */
+    uint8_t* out;          /* uint8 [B, H0, W0, 3] */
+    int B, Bo;             /* Bo: 1 (orig and mask shared by every output) or B */
+    int H0, W0;
+    int x1, y1, cw, ch;    /* the box: left, top, width, height */
+} imd_image_overlay_params;
+
+/* The ControlNet image of the inpainting script on the device (imd_image_inpaint_condition; make_inpaint_condition,
+ * inference_IMAGdressing_controlnetinpainting.py:48-59) from uint8 inputs of one size: per pixel and channel c < 3
+ *   v = (float(mask) / 255.0f > 0.5f) ? -1.0f : float(image[c]) / 255.0f          IEEE division
+ * rounded to nearest even into fp16 / bf16 [B, H, W, 8], channels 3..7 zero -- the values the IMD_IMG_16_NHWC8 stage of
+ * imd_image_resample gives with a = 1, b = 0, and -1 where the mask is set.  out must be 16-byte aligned. */
+typedef struct imd_image_inpaint_condition_params {
+    uint32_t struct_bytes; /* sizeof(imd_image_inpaint_condition_params) in the caller's view; checked on entry */
+    const uint8_t* image;  /* uint8 [B, H, W, 3] */
+    const uint8_t* mask;   /* uint8 [B, H, W] */
+    void* out;             /* fp16 / bf16 [B, H, W, 8] */
+    int B, H, W;
+    int dtype;             /* IMD_DTYPE_* of out */
+} imd_image_inpaint_condition_params;
+
 /* library / device */
 int imd_abi_version(void);
 const char* imd_last_error(void);
@@ -541,6 +575,10 @@ int imd_image_resample(const imd_image_resample_params* p, void* stream);
 int imd_image_resample_form(const imd_image_resample_params* p);
 /* Decoder output -> uint8 RGB on the device; see imd_image_pack_params. */
 int imd_image_pack_u8(const imd_image_pack_params* p, void* stream);
+/* Inpainting result -> the person image, Image.composite per byte; see imd_image_overlay_params. */
+int imd_image_overlay(const imd_image_overlay_params* p, void* stream);
+/* uint8 image + mask -> the inpainting ControlNet's 16-bit NHWC8 condition; see imd_image_inpaint_condition_params. */
+int imd_image_inpaint_condition(const imd_image_inpaint_condition_params* p, void* stream);
 
 /* diffusers Timesteps(dim, flip_sin_to_cos=True, freq_shift=0): out[B, dim] fp32 = [cos | sin]. */
 int imd_timestep_embedding(const float* t, float* out, int B, int dim, void* stream);
