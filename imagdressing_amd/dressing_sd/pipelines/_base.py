@@ -30,7 +30,7 @@ import torch
 from ... import ops
 from ...adapter.attention_processor import (IPAttnProcessor2_0, LoRAIPAttnProcessor2_0, LoraRefSAttnProcessor2_0,
                                             RefSAttnProcessor2_0)
-from ...unet import nchw_to_nhwc8
+from ...unet import DeepCache, nchw_to_nhwc8
 
 bf16 = torch.bfloat16
 
@@ -50,6 +50,16 @@ def randn_tensor(shape, generator=None, device=None, dtype=torch.float32):
     if gdev.type != device.type:
         return torch.randn(shape, generator=generator, device=gdev, dtype=dtype).to(device)
     return torch.randn(shape, generator=generator, device=device, dtype=dtype)
+
+
+def deepcache_plan(n_calls: int, cache_interval: int) -> List[bool]:
+    """Which UNet calls of a pipeline call are full (True) and which shallow (``enable_deepcache``): call c, counted from the first
+    EXECUTED call (``strength`` < 1 skips the head of the schedule; PNDM's extra call is just another index), is full iff
+    c % cache_interval == 0.  Call 0 is always full: it fills the feature cache and the processors' step-invariant K / V caches."""
+    cache_interval = int(cache_interval)
+    if cache_interval < 1:
+        raise ValueError(f"cache_interval must be >= 1, got {cache_interval}")
+    return [c % cache_interval == 0 for c in range(int(n_calls))]
 
 
 class PipelineBase:
@@ -104,8 +114,8 @@ class PipelineBase:
     def enable_step_graph(self, flag: bool = True):
         """Opt in to HIP-graph replay of the denoising step (see ``denoise``) -- DDIM and the deterministic samplers of the fused
         sampler step (DPM-Solver++, Euler, PNDM): same kernels, same arithmetic, one graph launch per step instead of ~500 kernel
-        launches.  Worth it where the loop is host-bound (small batches); ignored for UniPC, Euler-ancestral, step callbacks, traces
-        and per-step ControlNet gating."""
+        launches.  Worth it where the loop is host-bound (small batches); ignored for UniPC, Euler-ancestral, step callbacks, traces,
+        per-step ControlNet gating and while ``enable_deepcache`` is on."""
         self._step_graph = bool(flag)
         if not flag:
             self.release_step_graph()
@@ -126,6 +136,26 @@ class PipelineBase:
             self.release_step_graph()
         except Exception:        # noqa: BLE001  (interpreter shutdown)
             pass
+
+    def enable_deepcache(self, cache_interval: int = 3, depth: int = 1):
+        """Opt in to step-to-step feature caching (DeepCache, Ma et al., CVPR 2024; ``unet.DeepCache``): UNet call c of a pipeline call
+        is a full forward iff c % ``cache_interval`` == 0 (``deepcache_plan``); every other call recomputes only conv_in, the first
+        ``depth`` - 1 layers of the first down block and the last ``depth`` layers of the last up block around the deep feature the last
+        full call stored, and the ControlNet computes only the residuals those layers read.  The result CHANGES (that is the point);
+        what it does to image quality with real checkpoints is unmeasured, hence off by default.  ``cache_interval`` = 1 computes what
+        the switch-off loop computes.  While the switch is on, ``enable_step_graph`` is ignored (the call runs eagerly).  The cache
+        lives for one denoising call."""
+        if int(cache_interval) < 1:
+            raise ValueError(f"cache_interval must be >= 1, got {cache_interval}")
+        layers = getattr(getattr(self.unet, "config", None), "layers_per_block", 2)
+        if not 1 <= int(depth) <= layers + 1:
+            raise ValueError(f"depth must be in 1 .. {layers + 1} (layers_per_block + 1), got {depth}")
+        self._deepcache = (int(cache_interval), int(depth))
+        return self
+
+    def disable_deepcache(self):
+        self._deepcache = None
+        return self
 
     def enable_device_image_io(self, flag: bool = True):
         """Opt in to image input and output on the GPU (``imagdressing_amd.image.DeviceImageProcessor``): PIL / uint8 pose, control,
@@ -342,6 +372,18 @@ class PipelineBase:
         if variance_noise is not None and stochastic and len(variance_noise) < len(timesteps):
             raise ValueError(f"variance_noise has {len(variance_noise)} entries for {len(timesteps)} steps")
         ctrl_scale = 0.0 if control is None else float(control.get("scale", 1.0))
+        # DeepCache (enable_deepcache): one feature cache for this call, shared by the UNet and the ControlNet; UNet call i == loop index i
+        # (timesteps holds the executed calls only, PNDM's extra one included).  Switch off or interval 1: no cache, no keyword, today's calls
+        dc_on = getattr(self, "_deepcache", None) is not None
+        dc = DeepCache(self._deepcache[1]) if dc_on and self._deepcache[0] > 1 else None
+        dc_plan = deepcache_plan(len(timesteps), self._deepcache[0]) if dc is not None else None
+
+        def dc_kw(i):
+            """the cache keyword of UNet (and ControlNet) call ``i``, in the mode the plan gives it"""
+            if dc is None:
+                return {}
+            dc.full = dc_plan[i]
+            return {"deepcache": dc}
 
         def step_noise(i):
             vn = variance_noise[i] if variance_noise is not None else randn_tensor((B, Cl, h, w), generator=generator, device=dev, dtype=dt)
@@ -359,9 +401,10 @@ class PipelineBase:
             """ControlNet + UNet + ONE imd_sampler_step (CFG / update / history / noise / blend / next UNet input); ``t``, ``coefs`` as
             for ``ddim_step`` (graph replay: the coefficient row, history slot included, is read from device memory)."""
             down = mid = None
+            mode = {} if i is None else dc_kw(i)          # (i is None: the captured step of a graph replay, which never runs with the cache)
             if control is not None:
-                down, mid = self.controlnet.forward_nhwc(x_in, t, ctrl_ehs, ctrl_img, ctrl_scale * (keeps[0] if i is None else keeps[i]))
-            eps = self.unet.forward_nhwc(x_in, t, ehs, cak, down, mid, cfg_pair=True)
+                down, mid = self.controlnet.forward_nhwc(x_in, t, ctrl_ehs, ctrl_img, ctrl_scale * (keeps[0] if i is None else keeps[i]), **mode)
+            eps = self.unet.forward_nhwc(x_in, t, ehs, cak, down, mid, cfg_pair=True, **mode)
             kw = {}
             if inp is not None:
                 kw = dict(mask=inp["mask"], z_img=inp["z_img"], blend_noise=inp["noise"])
@@ -373,9 +416,10 @@ class PipelineBase:
             """ControlNet + UNet + CFG / DDIM / blend / next UNet input for one timestep; ``t`` a Python int (eager) or a device
             scalar with ``coefs`` the device-side schedule coefficients (graph replay: nothing step-specific is baked in)."""
             down = mid = None
+            mode = {} if i is None else dc_kw(i)
             if control is not None:
-                down, mid = self.controlnet.forward_nhwc(x_in, t, ctrl_ehs, ctrl_img, ctrl_scale * (keeps[0] if i is None else keeps[i]))
-            eps = self.unet.forward_nhwc(x_in, t, ehs, cak, down, mid, cfg_pair=True)     # x_in = [z; z]: both halves see the same latent
+                down, mid = self.controlnet.forward_nhwc(x_in, t, ctrl_ehs, ctrl_img, ctrl_scale * (keeps[0] if i is None else keeps[i]), **mode)
+            eps = self.unet.forward_nhwc(x_in, t, ehs, cak, down, mid, cfg_pair=True, **mode)     # x_in = [z; z]: both halves see the same latent
             kw = {}
             if inp is not None:
                 kw = dict(mask=inp["mask"], z_img=inp["z_img"], noise=inp["noise"])
@@ -401,7 +445,7 @@ class PipelineBase:
 
         def run_steps():
             nonlocal z
-            use_graph = (getattr(self, "_step_graph", False) and not multistep and not stochastic and callback is None and trace is None
+            use_graph = (getattr(self, "_step_graph", False) and not dc_on and not multistep and not stochastic and callback is None and trace is None
                          and len(timesteps) > 2 and (keeps is None or len(set(keeps)) == 1) and ops.ATTN_EVENT_HOOK is None)
             if use_graph:
                 # HIP-graph replay of the denoising step (opt-in, ``enable_step_graph``): step 0 runs eagerly on the pipeline's side stream
@@ -447,9 +491,10 @@ class PipelineBase:
             for i, t in enumerate(timesteps):
                 if multistep:
                     down = mid = None
+                    mode = dc_kw(i)
                     if control is not None:
-                        down, mid = self.controlnet.forward_nhwc(x_in, t, ctrl_ehs, ctrl_img, ctrl_scale * keeps[i])
-                    eps = self.unet.forward_nhwc(x_in, t, ehs, cak, down, mid, cfg_pair=True)
+                        down, mid = self.controlnet.forward_nhwc(x_in, t, ctrl_ehs, ctrl_img, ctrl_scale * keeps[i], **mode)
+                    eps = self.unet.forward_nhwc(x_in, t, ehs, cak, down, mid, cfg_pair=True, **mode)
                     z = sch.step_guided(eps.view(2 * B, HW, Cl), z, gs[0])
                     # emit the next 16-bit UNet input (both CFG halves) from z: the fused step with eps = 0, alpha = 1 is the identity on z
                     ops.ddim_cfg_step(z, ops.workspace("zero_eps", (2 * B, HW, Cl), torch.float32, dev), x_in.view(2 * B, HW, 8),
@@ -467,6 +512,8 @@ class PipelineBase:
         finally:
             for e in encs:
                 e.clear_time_embeddings()
+            if dc is not None:
+                dc.clear()          # the stored feature dies with the call, an exception included
 
     # ---- request-batched calls (RequestLayout) ----
     def _request_count(self, args: Dict[str, Any], per_call: Dict[str, Any], shard_over_ranks: bool) -> int:
@@ -755,6 +802,6 @@ def set_scale_by_type(unet, cls, **attrs):
                 setattr(proc, k, v)
 
 
-__all__ = ["RequestLayout", "request_count", "request_rows", "per_request_floats", "per_call_value", "as_batch", "min_guidance", "entries",
+__all__ = ["deepcache_plan", "RequestLayout", "request_count", "request_rows", "per_request_floats", "per_call_value", "as_batch", "min_guidance", "entries",
            "controlnet_keep", "first", "to_image_tensor", "PipelineBase", "StableDiffusionPipelineOutput", "randn_tensor", "set_scale_by_type",
            "RefSAttnProcessor2_0", "LoraRefSAttnProcessor2_0", "LoRAIPAttnProcessor2_0", "IPAttnProcessor2_0"]

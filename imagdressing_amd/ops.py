@@ -1471,6 +1471,17 @@ def repeat_batch(x: torch.Tensor, times: int = 2) -> torch.Tensor:
     return out
 
 
+def copy_into(dst: torch.Tensor, src: torch.Tensor) -> torch.Tensor:
+    """dst <- src for two contiguous 16-bit tensors of one shape (one strided 2-D copy, as :func:`repeat_batch`): a snapshot of an
+    activation into storage the caller owns."""
+    ensure_device(src.device)
+    if dst.shape != src.shape or dst.dtype != src.dtype or src.dtype not in DTYPE_CODE or not dst.is_contiguous():
+        raise L.ImdError(f"copy_into: {tuple(src.shape)} {src.dtype} -> {tuple(dst.shape)} {dst.dtype}: shapes and 16-bit element types must agree")
+    Cc = src.shape[-1]
+    L.check(L.load().imd_copy2d(_dev(src, src.dtype, "src"), Cc, dst.data_ptr(), Cc, src.numel() // Cc, Cc, _stream()))
+    return dst
+
+
 def f32_to_16(a: torch.Tensor, dtype=bf16) -> torch.Tensor:
     ensure_device(a.device)
     out = torch.empty(a.shape, dtype=dtype, device=a.device)

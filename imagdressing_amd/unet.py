@@ -392,6 +392,60 @@ class ResnetBlock:
         return self.conv2(h, res=sc, gn_stats_groups=self.groups)
 
 
+class DeepCache:
+    """Step-to-step feature cache of one denoising call (DeepCache, Ma et al., CVPR 2024), handed to ``forward_nhwc(deepcache=...)``.
+
+    ``depth`` = d in 1 .. layers_per_block + 1: the cut.  With L = layers_per_block, the last up block has L + 1 layers and layer j
+    consumes skip s(L - j) (s0 = conv_in's output, s1 .. sL = the outputs of the L layers of ``down_blocks[0]``); F_d is the hidden
+    state that ENTERS layer L + 1 - d of that block, before the concatenation with its skip.  ``full`` (set by the caller before each
+    forward) picks the mode: a full forward is today's forward plus a copy of F_d into a buffer THIS object owns (the activations
+    themselves are reused by later launches); a shallow forward runs conv_in, layers 0 .. d - 2 of ``down_blocks[0]``, takes F_d from
+    here and runs layers L + 1 - d .. L of the last up block and the output convolution.  One object serves the UNet and the ControlNet
+    of a loop (the ControlNet stores nothing: its shallow forward returns the first d residuals)."""
+
+    def __init__(self, depth: int = 1):
+        self.depth = int(depth)
+        self.full = True
+        self._feat: Optional[torch.Tensor] = None
+        self._sig = None            # (batch, H, W, dtype, depth) of the stored feature
+        self._ctrl_sig = None       # ... and of the ControlNet's last full forward
+
+    def check_depth(self, layers_per_block: int):
+        if not 1 <= self.depth <= layers_per_block + 1:
+            raise ValueError(f"deepcache depth must be in 1 .. {layers_per_block + 1} (layers_per_block + 1), got {self.depth}")
+
+    @staticmethod
+    def _signature(x, depth):
+        return (x.shape[0], x.shape[1], x.shape[2], x.dtype, depth)
+
+    def store(self, h: torch.Tensor, x: torch.Tensor):
+        """copy ``h`` (F_d of the full forward on ``x``) into storage this object owns"""
+        if self._feat is None or self._feat.shape != h.shape or self._feat.dtype != h.dtype or self._feat.device != h.device:
+            self._feat = torch.empty(h.shape, dtype=h.dtype, device=h.device)
+        ops.copy_into(self._feat, h)
+        self._sig = self._signature(x, self.depth)
+
+    def load(self, x: torch.Tensor) -> torch.Tensor:
+        self._match(self._sig, x, "UNet")
+        return self._feat
+
+    def note_controlnet(self, x: torch.Tensor):
+        self._ctrl_sig = self._signature(x, self.depth)
+
+    def check_controlnet(self, x: torch.Tensor):
+        self._match(self._ctrl_sig, x, "ControlNet")
+
+    def _match(self, sig, x, who):
+        if sig is None:
+            raise ValueError(f"deepcache: shallow {who} forward before any full one (the first call of a loop must be full)")
+        want = self._signature(x, self.depth)
+        if sig != want:
+            raise ValueError(f"deepcache: the cache holds (batch, height, width, dtype, depth) = {sig} and this {who} forward has {want}")
+
+    def clear(self):
+        self._feat = self._sig = self._ctrl_sig = None
+
+
 class _Encoder(PretrainedMixin):
     """conv_in + time embedding + down blocks + mid block (shared by the UNet and the ControlNet)."""
     _config_keys = ("in_channels", "out_channels", "block_out_channels", "layers_per_block", "attention_head_dim",
@@ -499,12 +553,15 @@ class _Encoder(PretrainedMixin):
         self._temb_table = None
         self._temb_fixed = None
 
-    def _run_down(self, x, temb_all, ehs, cak, pair_skip=None, pair_attn_done=False):
-        """``pair_skip``: the caller has already run conv_in and the first resnet on ONE half of a CFG batch whose halves are identical
+    def _run_down(self, x, temb_all, ehs, cak, pair_skip=None, pair_attn_done=False, layers: Optional[int] = None):
+        """``layers`` = n (a shallow DeepCache forward): stop after the first n layers of ``down_blocks[0]`` -> skips s0 .. sn.
+        ``pair_skip``: the caller has already run conv_in and the first resnet on ONE half of a CFG batch whose halves are identical
         up to there (``x`` = that resnet's output repeated for both halves, ``pair_skip`` = the half-batch conv_in output);
         ``pair_attn_done``: ... and the first transformer as well (``Transformer2D.call_pair_half``; ``x`` = its output)."""
         skips = [x if pair_skip is None else pair_skip]
         first = pair_skip is not None
+        if layers == 0:
+            return x, skips
         for blk in self.down_blocks:
             for j, r in enumerate(blk.resnets):
                 if first:
@@ -516,6 +573,8 @@ class _Encoder(PretrainedMixin):
                     if blk.attentions:
                         x = blk.attentions[j](x, ehs, cak)
                 skips.append(x)
+                if layers is not None and len(skips) > layers:
+                    return x, skips
             if blk.downsampler is not None:
                 x = blk.downsampler(x, stride=2, gn_stats_groups=self.cfg["norm_num_groups"])   # feeds the next level's norm1 (K-sliced: statistics from the finish launch)
                 skips.append(x)
@@ -598,16 +657,30 @@ class UNet2DConditionModel(_Encoder):
     def forward_nhwc(self, x: torch.Tensor, timestep, encoder_hidden_states: torch.Tensor,
                      cross_attention_kwargs: Optional[dict] = None,
                      down_block_additional_residuals: Optional[List[torch.Tensor]] = None,
-                     mid_block_additional_residual: Optional[torch.Tensor] = None, cfg_pair: bool = False) -> torch.Tensor:
+                     mid_block_additional_residual: Optional[torch.Tensor] = None, cfg_pair: bool = False,
+                     deepcache: Optional[DeepCache] = None) -> torch.Tensor:
         """x [B, H, W, 8] bf16 (latent channels zero-padded to 8) -> eps [B, H*W, 4] fp32.
         ``cfg_pair``: the caller guarantees x[B/2:] == x[:B/2] (the CFG batch of the sampling loop: the reference feeds the SAME latent to
         its cond and uncond UNet calls, IMAGDressing_v1_pipeline.py:483-512).  conv_in and the first resnet see neither the text nor the
-        garment, so their outputs are identical for the two halves: they run on one half and the result is repeated."""
+        garment, so their outputs are identical for the two halves: they run on one half and the result is repeated.
+        ``deepcache`` (:class:`DeepCache`; None: exactly today's forward): with ``deepcache.full`` the same forward, which also copies
+        the deep feature F_d into the cache; otherwise the shallow forward around the stored F_d -- the outermost ``depth`` skips and the
+        last ``depth`` layers of the last up block, nothing below them."""
         cak = dict(cross_attention_kwargs or {})
         B, H, W, _ = x.shape
         ehs = encoder_hidden_states
+        shallow = None                    # layers of down_blocks[0] a shallow forward runs
+        if deepcache is not None:
+            deepcache.check_depth(len(self.down_blocks[0].resnets))
+            if not deepcache.full:
+                feat = deepcache.load(x)          # (raises before anything is launched)
+                shallow = deepcache.depth - 1
         temb_all = self._time_embed(timestep, B, x.device)
-        if cfg_pair and B % 2 == 0 and ops.CFG_PAIR_DEDUP:
+        if shallow == 0:
+            # depth 1: the only skip is conv_in's output (one copy for both halves of a CFG pair, as in the full forward)
+            dedup = cfg_pair and B % 2 == 0 and ops.CFG_PAIR_DEDUP
+            h, skips = None, [self.conv_in(x[:B // 2] if dedup else x, gn_stats_groups=self.cfg["norm_num_groups"])]
+        elif cfg_pair and B % 2 == 0 and ops.CFG_PAIR_DEDUP:
             h0 = self.conv_in(x[:B // 2], gn_stats_groups=self.cfg["norm_num_groups"])
             blk0 = self.down_blocks[0]
             r0 = blk0.resnets[0](h0, temb_all)
@@ -615,18 +688,31 @@ class UNet2DConditionModel(_Encoder):
             # phase run once per image (Transformer2D.call_pair_half); the halves part ways at attn1's out-projection
             if ops.CFG_PAIR_ATTN and blk0.attentions and blk0.attentions[0].pair_half_ok(r0, cak):
                 h = blk0.attentions[0].call_pair_half(r0, ehs, cak)
-                h, skips = self._run_down(h, temb_all, ehs, cak, pair_skip=h0, pair_attn_done=True)
+                h, skips = self._run_down(h, temb_all, ehs, cak, pair_skip=h0, pair_attn_done=True, layers=shallow)
             else:
-                h, skips = self._run_down(ops.repeat_batch(r0), temb_all, ehs, cak, pair_skip=h0)
+                h, skips = self._run_down(ops.repeat_batch(r0), temb_all, ehs, cak, pair_skip=h0, layers=shallow)
         else:
             h = self.conv_in(x, gn_stats_groups=self.cfg["norm_num_groups"])          # (feeds the first resnet's norm1)
-            h, skips = self._run_down(h, temb_all, ehs, cak)
-        h = self._run_mid(h, temb_all, ehs, cak)
-        if mid_block_additional_residual is not None:
-            h = ops.add(h, mid_block_additional_residual)
+            h, skips = self._run_down(h, temb_all, ehs, cak, layers=shallow)
         ctrl = down_block_additional_residuals
-        for blk in self.up_blocks:
+        # DeepCache: F_d is the state that enters layer ``cut`` of the last up block
+        cut = None if deepcache is None else len(self.up_blocks[-1].resnets) - deepcache.depth
+        if shallow is None:
+            h = self._run_mid(h, temb_all, ehs, cak)
+            if mid_block_additional_residual is not None:
+                h = ops.add(h, mid_block_additional_residual)
+            up_blocks = self.up_blocks
+        else:
+            # the skips are s0 .. s(depth - 1): layers cut .. L of the last up block pop exactly those, around the stored F_d
+            h = feat
+            up_blocks = self.up_blocks[-1:]
+        for blk in up_blocks:
             for j, r in enumerate(blk.resnets):
+                if cut is not None and blk is self.up_blocks[-1]:
+                    if shallow is not None and j < cut:
+                        continue
+                    if shallow is None and j == cut:
+                        deepcache.store(h, x)          # a copy: the activation itself is reused by later launches
                 s = skips.pop()
                 c = None if ctrl is None else ctrl[len(skips)]
                 h = ops.concat_channels(h, s, c, gn_stats_groups=r.groups)          # cat([x, skip (+ ControlNet residual)]) + the statistics of the resnet's norm1
@@ -715,20 +801,32 @@ class ControlNetModel(_Encoder):
         self._cond_cache = (key, cond_nhwc8, e)
         return e
 
-    def forward_nhwc(self, x, timestep, encoder_hidden_states, cond_nhwc8, conditioning_scale: float = 1.0):
-        """x [B, H, W, 8]; cond [Bc, 8H, 8W, 8] with Bc == B or 1 -> (list of 12 NHWC residuals, mid)."""
+    def forward_nhwc(self, x, timestep, encoder_hidden_states, cond_nhwc8, conditioning_scale: float = 1.0,
+                     deepcache: Optional[DeepCache] = None):
+        """x [B, H, W, 8]; cond [Bc, 8H, 8W, 8] with Bc == B or 1 -> (list of 12 NHWC residuals, mid).
+        ``deepcache`` in its shallow mode (``not deepcache.full``): the residuals a shallow UNet forward reads -- conv_in, the conditioning
+        embedding, layers 0 .. depth - 2 of the first down block and zero-convs 0 .. depth - 1 -> (list of depth residuals, None)."""
         B = x.shape[0]
+        layers = None
+        if deepcache is not None:
+            deepcache.check_depth(len(self.down_blocks[0].resnets))
+            if deepcache.full:
+                deepcache.note_controlnet(x)
+            else:
+                deepcache.check_controlnet(x)
+                layers = deepcache.depth - 1
         temb_all = self._time_embed(timestep, B, x.device)
         emb = self.cond_embedding(cond_nhwc8)
         if emb.shape[0] != B:
             emb = emb.expand(B, -1, -1, -1).contiguous()
         h = self.conv_in(x, res=emb)
-        h, skips = self._run_down(h, temb_all, encoder_hidden_states, {})
-        h = self._run_mid(h, temb_all, encoder_hidden_states, {})
+        h, skips = self._run_down(h, temb_all, encoder_hidden_states, {}, layers=layers)
+        if layers is None:
+            h = self._run_mid(h, temb_all, encoder_hidden_states, {})
         down = []
         for s, zc in zip(skips, self.zero_convs):
             down.append(_scaled_conv1x1(zc, s, conditioning_scale))
-        mid = _scaled_conv1x1(self.zero_mid, h, conditioning_scale)
+        mid = None if layers is not None else _scaled_conv1x1(self.zero_mid, h, conditioning_scale)
         return down, mid
 
     def forward(self, sample, timestep, encoder_hidden_states, controlnet_cond, conditioning_scale=1.0,
