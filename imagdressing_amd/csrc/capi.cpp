@@ -293,6 +293,13 @@ int imd_sampler_step(const imd_sampler_params* p, void* stream) {
     return imd_launch_sampler_step(*p, (hipStream_t)stream);
 }
 
+int imd_sampler_step_rows(const imd_sampler_params* p, const float* coef_rows, void* stream) {
+    IMD_REQUIRE(p != nullptr, "sampler_step_rows: null params");
+    IMD_REQUIRE_SIZE(p, "sampler_step_rows");
+    IMD_REQUIRE(p->z && p->eps, "sampler_step_rows: null pointer");
+    return imd_launch_sampler_step_rows(*p, coef_rows, (hipStream_t)stream);
+}
+
 int imd_image_resample(const imd_image_resample_params* p, void* stream) {
     IMD_REQUIRE(p != nullptr, "image_resample: null params");
     IMD_REQUIRE_SIZE(p, "image_resample");

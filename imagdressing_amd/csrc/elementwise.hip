@@ -145,6 +145,78 @@ __global__ __launch_bounds__(256) void sampler_step_kernel(const SamplerParams p
     }
 }
 
+// sampler_step_rows: sampler_step with the coefficient block PER LATENT ROW (a denoising session: every row is a request at its own
+// position of its own schedule).  Row b reads 16 floats of device memory, coef_rows + 16 b, as four float4: [0..12] the block above,
+// [13] active.  An inactive row is skipped whole -- no load and no store of z, eps, the history or x_next -- so a free slot keeps its
+// bytes.  The per-pixel arithmetic is sampler_step_kernel's, statement for statement (same expression trees, same contraction): with
+// every row equal and active the two launches are bit-identical.  The row of a pixel is i / HW, so a block that spans several rows
+// (HW < 256) reads several blocks; at the real geometries (HW >= 64) the four loads are wave-uniform and hit one cache line.
+template <bool F16>
+__global__ __launch_bounds__(256) void sampler_step_rows_kernel(const SamplerParams p, const float* __restrict__ coef_rows) {
+    const long total = (long)p.B * p.HW;                   // one thread per pixel (4 channels = 16 B)
+    for (long i = blockIdx.x * 256L + threadIdx.x; i < total; i += (long)gridDim.x * 256L) {
+        const long b = i / p.HW;                           // the latent row of this pixel
+        const float4* row = reinterpret_cast<const float4*>(coef_rows) + b * (IMD_SAMPLER_ROW_FLOATS / 4);
+        const float4 r3 = row[3];
+        if (r3.y == 0.f) continue;                         // inactive: neither read nor written
+        const float4 r0 = row[0], r1 = row[1], r2 = row[2];
+        const float m_x = r0.x, m_e = r0.y, z_x = r0.z, z_m = r0.w;
+        const float zh[4] = {r1.x, r1.y, r1.z, r1.w};
+        const float z_n = r2.x, b_img = r2.y, b_noise = r2.z, in_scale = r2.w;
+        int store = (int)r3.x;
+        if (store >= p.K) store = -1;                      // (device coefficients are not seen by the launcher: never past the buffer)
+        const float4 z = reinterpret_cast<const float4*>(p.z)[i];
+        const float4 ec = reinterpret_cast<const float4*>(p.eps)[i];
+        const float4 eu = reinterpret_cast<const float4*>(p.eps)[i + total];
+        float zz[4] = {z.x, z.y, z.z, z.w};
+        const float g = p.guidance_rows ? p.guidance_rows[b] : p.guidance;
+        const float c[4] = {ec.x, ec.y, ec.z, ec.w};
+        const float u[4] = {eu.x, eu.y, eu.z, eu.w};
+        float hs[4][4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            float4 h = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (k < p.K && zh[k] != 0.f) h = reinterpret_cast<const float4*>(p.hist)[(long)k * total + i];
+            hs[k][0] = h.x; hs[k][1] = h.y; hs[k][2] = h.z; hs[k][3] = h.w;
+        }
+        float mk = 1.f;
+        float zi[4] = {0, 0, 0, 0}, nz[4] = {0, 0, 0, 0}, vn[4] = {0, 0, 0, 0};
+        if (p.noise) {
+            const float4 n = reinterpret_cast<const float4*>(p.noise)[i];
+            vn[0] = z_n * n.x; vn[1] = z_n * n.y; vn[2] = z_n * n.z; vn[3] = z_n * n.w;
+        }
+        if (p.mask) {
+            mk = p.mask[i];
+            const float4 a = reinterpret_cast<const float4*>(p.z_img)[i];
+            const float4 n = reinterpret_cast<const float4*>(p.blend_noise)[i];
+            zi[0] = a.x; zi[1] = a.y; zi[2] = a.z; zi[3] = a.w;
+            nz[0] = n.x; nz[1] = n.y; nz[2] = n.z; nz[3] = n.w;
+        }
+        float mm[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const float eps = u[e] + g * (c[e] - u[e]);
+            mm[e] = m_x * zz[e] + m_e * eps;
+            float zn = z_x * zz[e] + z_m * mm[e];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) zn += zh[k] * hs[k][e];
+            zn += vn[e];
+            if (p.mask) {
+                const float proper = b_img * zi[e] + b_noise * nz[e];
+                zn = (1.f - mk) * proper + mk * zn;
+            }
+            zz[e] = zn;
+        }
+        reinterpret_cast<float4*>(p.z)[i] = make_float4(zz[0], zz[1], zz[2], zz[3]);
+        if (store >= 0) reinterpret_cast<float4*>(p.hist)[(long)store * total + i] = make_float4(mm[0], mm[1], mm[2], mm[3]);
+        if (p.x_next) {
+            const uint4 o = make_uint4(El<F16>::pack2(in_scale * zz[0], in_scale * zz[1]), El<F16>::pack2(in_scale * zz[2], in_scale * zz[3]), 0u, 0u);
+            reinterpret_cast<uint4*>(p.x_next)[i] = o;
+            reinterpret_cast<uint4*>(p.x_next)[i + total] = o;
+        }
+    }
+}
+
 // diffusers Timesteps(dim, flip_sin_to_cos=True, downscale_freq_shift=0): [cos | sin]
 __global__ void timestep_embedding_kernel(const float* t, float* out, int B, int dim) {
     const int half = dim / 2;
@@ -306,22 +378,39 @@ int imd_launch_ddim_cfg_step_rows(const DdimParams& p, const float* guidance, hi
     return launch_ddim_cfg_step(p, s, "ddim_cfg_step_rows", guidance);
 }
 
-int imd_launch_sampler_step(const SamplerParams& p, hipStream_t s) {
+namespace {
+// what imd_sampler_step and imd_sampler_step_rows refuse alike (`rows`: the coefficients, store slot included, live in device memory)
+int sampler_step_refusal(const SamplerParams& p, const char* what, bool rows) {
     auto misaligned = [](const void* q, uintptr_t a) { return (reinterpret_cast<uintptr_t>(q) & (a - 1)) != 0; };
-    if (p.B <= 0 || p.HW <= 0) return imd_set_error("sampler_step: empty latent");
-    if (p.K < 0 || p.K > IMD_SAMPLER_MAX_HISTORY) return imd_set_error("sampler_step: K (%d) must be 0..%d history slots", p.K, IMD_SAMPLER_MAX_HISTORY);
-    if (p.K > 0 && !p.hist) return imd_set_error("sampler_step: K = %d history slots without a history buffer", p.K);
-    if (!p.coefs && (p.store < -1 || p.store >= p.K)) return imd_set_error("sampler_step: store slot %d outside -1..%d", p.store, p.K - 1);
-    if (p.mask && (!p.z_img || !p.blend_noise)) return imd_set_error("sampler_step: inpaint mask given without image latents / blend noise");
+    if (p.B <= 0 || p.HW <= 0) return imd_set_error("%s: empty latent", what);
+    if (p.K < 0 || p.K > IMD_SAMPLER_MAX_HISTORY) return imd_set_error("%s: K (%d) must be 0..%d history slots", what, p.K, IMD_SAMPLER_MAX_HISTORY);
+    if (p.K > 0 && !p.hist) return imd_set_error("%s: K = %d history slots without a history buffer", what, p.K);
+    if (!rows && !p.coefs && (p.store < -1 || p.store >= p.K)) return imd_set_error("%s: store slot %d outside -1..%d", what, p.store, p.K - 1);
+    if (p.mask && (!p.z_img || !p.blend_noise)) return imd_set_error("%s: inpaint mask given without image latents / blend noise", what);
     if (misaligned(p.z, 16) || misaligned(p.eps, 16) || misaligned(p.x_next, 16) || misaligned(p.hist, 16) || misaligned(p.noise, 16) ||
         misaligned(p.z_img, 16) || misaligned(p.blend_noise, 16))
-        return imd_set_error("sampler_step: z, eps, x_next, hist, noise, z_img and blend_noise must be 16-byte aligned");
-    if (misaligned(p.mask, 4) || misaligned(p.guidance_rows, 4) || misaligned(p.coefs, 4))
-        return imd_set_error("sampler_step: mask, guidance_rows and coefs must be 4-byte aligned");
+        return imd_set_error("%s: z, eps, x_next, hist, noise, z_img and blend_noise must be 16-byte aligned", what);
+    if (misaligned(p.mask, 4) || misaligned(p.guidance_rows, 4) || (!rows && misaligned(p.coefs, 4)))
+        return imd_set_error("%s: mask, guidance_rows and coefs must be 4-byte aligned", what);
+    if (p.dtype != IMD_DTYPE_F16 && p.dtype != IMD_DTYPE_BF16) return imd_set_error("%s: unknown dtype %d", what, p.dtype);
+    return 0;
+}
+}  // namespace
+
+int imd_launch_sampler_step(const SamplerParams& p, hipStream_t s) {
+    if (sampler_step_refusal(p, "sampler_step", false)) return 1;
     if (p.dtype == IMD_DTYPE_F16) hipLaunchKernelGGL(sampler_step_kernel<true>, dim3(grid_for((long)p.B * p.HW)), dim3(256), 0, s, p);
-    else if (p.dtype == IMD_DTYPE_BF16) hipLaunchKernelGGL(sampler_step_kernel<false>, dim3(grid_for((long)p.B * p.HW)), dim3(256), 0, s, p);
-    else return imd_set_error("sampler_step: unknown dtype %d", p.dtype);
+    else hipLaunchKernelGGL(sampler_step_kernel<false>, dim3(grid_for((long)p.B * p.HW)), dim3(256), 0, s, p);
     return imd_check_launch("sampler_step");
+}
+
+int imd_launch_sampler_step_rows(const SamplerParams& p, const float* coef_rows, hipStream_t s) {
+    if (!coef_rows) return imd_set_error("sampler_step_rows: null coef_rows");
+    if (reinterpret_cast<uintptr_t>(coef_rows) & 15) return imd_set_error("sampler_step_rows: coef_rows must be 16-byte aligned (four float4 per latent row)");
+    if (sampler_step_refusal(p, "sampler_step_rows", true)) return 1;
+    if (p.dtype == IMD_DTYPE_F16) hipLaunchKernelGGL(sampler_step_rows_kernel<true>, dim3(grid_for((long)p.B * p.HW)), dim3(256), 0, s, p, coef_rows);
+    else hipLaunchKernelGGL(sampler_step_rows_kernel<false>, dim3(grid_for((long)p.B * p.HW)), dim3(256), 0, s, p, coef_rows);
+    return imd_check_launch("sampler_step_rows");
 }
 
 int imd_launch_timestep_embedding(const float* t, float* out, int B, int dim, hipStream_t s) {

@@ -21,6 +21,11 @@ class IMAGDressing_v1(PipelineBase):
     def set_scale(self, scale):                                            # :342-345
         set_scale_by_type(self.unet, RefSAttnProcessor2_0, scale=scale)
 
+    def open_session(self, slots: int, width: int, height: int, controlnet_conditioning_scale: float = 1.0):
+        """In-flight batching: a :class:`imagdressing_amd.session.DenoiseSession` with ``slots`` slots at ``width`` x ``height``
+        (``controlnet_conditioning_scale`` is accepted for a uniform surface; this pipeline has no ControlNet)."""
+        return self._open_session(slots, width, height)
+
     @torch.no_grad()
     def __call__(self, prompt, null_prompt, negative_prompt, ref_image, width, height, num_inference_steps, guidance_scale,
                  ref_clip_image=None, num_images_per_prompt=1, image_scale=1.0, num_samples=1, eta: float = 0.0,

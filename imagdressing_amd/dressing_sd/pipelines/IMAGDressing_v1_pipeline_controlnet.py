@@ -31,6 +31,12 @@ class IMAGDressing_v1(PipelineBase):
                     negative_prompt_embeds=negative_prompt_embeds, scale=float(first(scale)),
                     keep=controlnet_keep(num_inference_steps, float(first(start)), float(first(end))))
 
+    def open_session(self, slots: int, width: int, height: int, controlnet_conditioning_scale: float = 1.0):
+        """In-flight batching: a :class:`imagdressing_amd.session.DenoiseSession` with ``slots`` slots at ``width`` x ``height``; every
+        request brings its own pose image, ``controlnet_conditioning_scale`` holds for the whole session (the gate is one scalar per
+        launch).  A pipeline built without a ControlNet opens the session of the base pipeline."""
+        return self._open_session(slots, width, height, controlnet_conditioning_scale, with_controlnet=self.controlnet is not None)
+
     @torch.no_grad()
     def __call__(self, prompt, null_prompt, negative_prompt, ref_image, width, height, num_inference_steps, guidance_scale,
                  pose_image=None, ref_clip_image=None, num_images_per_prompt=1, image_scale=1.0, num_samples=1, eta: float = 0.0,

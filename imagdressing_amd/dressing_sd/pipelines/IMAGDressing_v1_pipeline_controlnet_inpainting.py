@@ -193,6 +193,9 @@ class IMAGDressing_v1(PipelineBase):
         from PIL import Image
         return StableDiffusionPipelineOutput(images=[Image.fromarray(a) for a in arrs], nsfw_content_detected=None)
 
+    def open_session(self, *args, **kwargs):
+        raise NotImplementedError("open_session on the inpainting pipeline: the per-row blend coefficients are in imd_sampler_step_rows, the per-slot mask / image-latent buffers are not built yet")
+
     @torch.no_grad()
     def __call__(self, prompt, null_prompt, negative_prompt, ref_image, width, height, num_inference_steps, guidance_scale,
                  ref_clip_image=None, num_images_per_prompt=1, image_scale=1.0, num_samples=1, strength: float = 1.0,

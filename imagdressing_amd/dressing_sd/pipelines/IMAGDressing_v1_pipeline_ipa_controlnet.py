@@ -80,6 +80,9 @@ class IMAGDressing_v1(PipelineBase):
         set_scale_by_type(self.unet, LoRAIPAttnProcessor2_0, scale=ipa_scale, lora_scale=lora_scale)
         set_scale_by_type(self.unet, IPAttnProcessor2_0, scale=ipa_scale, lora_scale=lora_scale)
 
+    def open_session(self, *args, **kwargs):
+        raise NotImplementedError("open_session on the IP-Adapter pipeline: per-slot face tokens and LoRA scales are not built yet")
+
     @torch.no_grad()
     def __call__(self, prompt, null_prompt, negative_prompt, ref_image, width, height, num_inference_steps, guidance_scale,
                  pose_image=None, ref_clip_image=None, face_clip_image=None, faceid_embeds=None, num_images_per_prompt=1,

@@ -515,6 +515,14 @@ class PipelineBase:
             if dc is not None:
                 dc.clear()          # the stored feature dies with the call, an exception included
 
+    # ---- in-flight batching (imagdressing_amd/session.py) ----
+    def _open_session(self, slots: int, width: int, height: int, controlnet_conditioning_scale: float = 1.0, with_controlnet: bool = False):
+        """A denoising session of ``slots`` latent rows at one geometry: requests are submitted at any time, enter a free slot at the
+        start of any step, run their own number of steps and leave when done (``session.DenoiseSession``).  DPM-Solver++, Euler, PNDM
+        and DDIM (eta = 0); refused with UniPC, Euler-ancestral and while ``enable_deepcache`` is on; ``enable_step_graph`` is ignored."""
+        from ...session import DenoiseSession
+        return DenoiseSession(self, slots, width, height, controlnet_conditioning_scale, with_controlnet=with_controlnet)
+
     # ---- request-batched calls (RequestLayout) ----
     def _request_count(self, args: Dict[str, Any], per_call: Dict[str, Any], shard_over_ranks: bool) -> int:
         return request_count(args, per_call, shard_over_ranks=shard_over_ranks, scheduler=self.scheduler)

@@ -1205,28 +1205,23 @@ def sampler_coefs(m_x=0.0, m_e=1.0, z_x=1.0, z_m=0.0, z_h=(), z_n=0.0, b_img=1.0
     return [float(m_x), float(m_e), float(z_x), float(z_m)] + zh + [float(z_n), float(b_img), float(b_noise), float(in_scale), float(int(store))]
 
 
-def sampler_step(z, eps, x_next, *, guidance, coefs, hist=None, noise=None, mask=None, z_img=None, blend_noise=None):
-    """One fused step of an affine sampler (``imd_sampler_step``; DPM-Solver++, Euler, Euler-ancestral, PNDM -- the coefficients
-    come from imagdressing_amd/scheduler.py).  z [B,HW,4] fp32 (in place); eps [2B,HW,4] fp32; x_next [2B,HW,8] 16-bit or None;
-    ``hist`` [K, B, HW, 4] fp32 (one contiguous buffer, K <= 4) or None; ``noise`` [B,HW,4] fp32 (scaled by z_n);
-    ``mask`` [B,HW] + ``z_img`` + ``blend_noise`` [B,HW,4]: the inpainting blend.
-    ``coefs``: the 13 values of :func:`sampler_coefs` as a Python sequence (passed in the parameter block) or as a device fp32
-    tensor (read by the kernel: HIP-graph replay of a step).  ``guidance``: a float, or a device fp32 tensor [B]."""
+def _sampler_params(what, z, eps, x_next, guidance, hist, noise, mask, z_img, blend_noise):
+    """the tensor fields of ``imd_sampler_params`` (everything but the coefficients), checked: shared by the two entry points"""
     ensure_device(z.device)
     B, HW = z.shape[0], z.shape[1]
     n = B * HW * 4
     p = L.SamplerParams()
     p.z, p.eps = _dev(z, torch.float32, "z"), _dev(eps, torch.float32, "eps")
     if z.numel() != n or eps.numel() != 2 * n:
-        raise L.ImdError(f"sampler_step: z {tuple(z.shape)} / eps {tuple(eps.shape)}: expected [B, HW, 4] and [2B, HW, 4]")
+        raise L.ImdError(f"{what}: z {tuple(z.shape)} / eps {tuple(eps.shape)}: expected [B, HW, 4] and [2B, HW, 4]")
     p.dtype = 0 if x_next is None else _code(x_next, "x_next")
     p.x_next = None if x_next is None else _dev(x_next, x_next.dtype, "x_next")
     if x_next is not None and x_next.numel() != 4 * n:
-        raise L.ImdError(f"sampler_step: x_next has {x_next.numel()} elements, expected {4 * n}")
+        raise L.ImdError(f"{what}: x_next has {x_next.numel()} elements, expected {4 * n}")
     p.B, p.HW = B, HW
     if isinstance(guidance, torch.Tensor):
         if guidance.dtype != torch.float32 or guidance.numel() != B or not guidance.is_contiguous():
-            raise L.ImdError(f"sampler_step: per-row guidance must be a contiguous fp32 tensor of {B} values, got "
+            raise L.ImdError(f"{what}: per-row guidance must be a contiguous fp32 tensor of {B} values, got "
                              f"{guidance.dtype} {tuple(guidance.shape)}")
         p.guidance_rows, p.guidance = _dev(guidance, torch.float32, "guidance"), 0.0
     else:
@@ -1234,15 +1229,27 @@ def sampler_step(z, eps, x_next, *, guidance, coefs, hist=None, noise=None, mask
     p.K, p.hist = 0, None
     if hist is not None:
         if hist.numel() % n:
-            raise L.ImdError(f"sampler_step: hist has {hist.numel()} elements, not a multiple of {n}")
+            raise L.ImdError(f"{what}: hist has {hist.numel()} elements, not a multiple of {n}")
         p.K, p.hist = hist.numel() // n, _dev(hist, torch.float32, "hist")
     for name, t in (("noise", noise), ("z_img", z_img), ("blend_noise", blend_noise)):
         if t is not None and t.numel() != n:
-            raise L.ImdError(f"sampler_step: {name} has {t.numel()} elements, expected {n}")
+            raise L.ImdError(f"{what}: {name} has {t.numel()} elements, expected {n}")
     if mask is not None and mask.numel() != B * HW:
-        raise L.ImdError(f"sampler_step: mask has {mask.numel()} elements, expected {B * HW}")
+        raise L.ImdError(f"{what}: mask has {mask.numel()} elements, expected {B * HW}")
     p.noise = _opt(noise, torch.float32, "noise")
     p.mask, p.z_img, p.blend_noise = _opt(mask, torch.float32, "mask"), _opt(z_img, torch.float32, "z_img"), _opt(blend_noise, torch.float32, "blend_noise")
+    p.coefs, p.store = None, -1
+    return p
+
+
+def sampler_step(z, eps, x_next, *, guidance, coefs, hist=None, noise=None, mask=None, z_img=None, blend_noise=None):
+    """One fused step of an affine sampler (``imd_sampler_step``; DPM-Solver++, Euler, Euler-ancestral, PNDM -- the coefficients
+    come from imagdressing_amd/scheduler.py).  z [B,HW,4] fp32 (in place); eps [2B,HW,4] fp32; x_next [2B,HW,8] 16-bit or None;
+    ``hist`` [K, B, HW, 4] fp32 (one contiguous buffer, K <= 4) or None; ``noise`` [B,HW,4] fp32 (scaled by z_n);
+    ``mask`` [B,HW] + ``z_img`` + ``blend_noise`` [B,HW,4]: the inpainting blend.
+    ``coefs``: the 13 values of :func:`sampler_coefs` as a Python sequence (passed in the parameter block) or as a device fp32
+    tensor (read by the kernel: HIP-graph replay of a step).  ``guidance``: a float, or a device fp32 tensor [B]."""
+    p = _sampler_params("sampler_step", z, eps, x_next, guidance, hist, noise, mask, z_img, blend_noise)
     if isinstance(coefs, torch.Tensor):
         if coefs.numel() < SAMPLER_COEFS:
             raise L.ImdError(f"sampler_step: coefs needs {SAMPLER_COEFS} fp32 values")
@@ -1251,12 +1258,37 @@ def sampler_step(z, eps, x_next, *, guidance, coefs, hist=None, noise=None, mask
         c = [float(v) for v in coefs]
         if len(c) != SAMPLER_COEFS:
             raise L.ImdError(f"sampler_step: coefs needs {SAMPLER_COEFS} values (ops.sampler_coefs), got {len(c)}")
-        p.coefs = None
         p.m_x, p.m_e, p.z_x, p.z_m = c[0:4]
         p.z_h = (C.c_float * 4)(*c[4:8])
         p.z_n, p.b_img, p.b_noise, p.in_scale = c[8:12]
         p.store = int(c[12])
     L.check(L.load().imd_sampler_step(C.byref(p), _stream()))
+    return z
+
+
+SAMPLER_ROW_FLOATS = 16
+
+
+def sampler_coef_row(coefs13, active=True):
+    """One latent row of ``imd_sampler_step_rows``: the 13 values of :func:`sampler_coefs`, the ``active`` flag (0: the row is
+    skipped, nothing of it is read or written) and two reserved zeros -- 16 floats."""
+    c = [float(v) for v in coefs13]
+    if len(c) != SAMPLER_COEFS:
+        raise L.ImdError(f"sampler_coef_row: needs the {SAMPLER_COEFS} values of ops.sampler_coefs, got {len(c)}")
+    return c + [1.0 if active else 0.0, 0.0, 0.0]
+
+
+def sampler_step_rows(z, eps, x_next, *, guidance, coef_rows, hist=None, noise=None, mask=None, z_img=None, blend_noise=None):
+    """:func:`sampler_step` with one coefficient block PER LATENT ROW (``imd_sampler_step_rows``): ``coef_rows`` is a device fp32
+    tensor [B, 16] of :func:`sampler_coef_row` rows -- every row at its own step of its own schedule, with its own history slots; an
+    inactive row keeps every byte of its z, history and x_next.  The other arguments as for :func:`sampler_step`."""
+    p = _sampler_params("sampler_step_rows", z, eps, x_next, guidance, hist, noise, mask, z_img, blend_noise)
+    if (not isinstance(coef_rows, torch.Tensor) or coef_rows.dtype != torch.float32 or coef_rows.numel() != p.B * SAMPLER_ROW_FLOATS
+            or not coef_rows.is_contiguous()):
+        raise L.ImdError(f"sampler_step_rows: coef_rows must be a contiguous device fp32 tensor [{p.B}, {SAMPLER_ROW_FLOATS}] "
+                         f"(ops.sampler_coef_row per latent row), got {getattr(coef_rows, 'dtype', type(coef_rows))} "
+                         f"{tuple(getattr(coef_rows, 'shape', ()))}")
+    L.check(L.load().imd_sampler_step_rows(C.byref(p), _dev(coef_rows, torch.float32, "coef_rows"), _stream()))
     return z
 
 

@@ -316,6 +316,17 @@ class SamplerHistory:
         return ops.sampler_coefs(row.m_x, row.m_e, row.z_x, row.z_m, zh, row.z_n, row.b_img, row.b_noise, row.in_scale, store)
 
 
+def ddim_row(scheduler: "DDIMScheduler", t: int) -> SamplerRow:
+    """The deterministic (eta = 0) DDIM step at timestep ``t`` as a :class:`SamplerRow`, in float64: m = e and
+        z' = (sqrt(a_prev) / sqrt(a_t)) z + (sqrt(1 - a_prev) - sqrt(a_prev) sqrt(1 - a_t) / sqrt(a_t)) e
+    -- for the callers that give every latent row its own coefficients (``imd_sampler_step_rows``, the denoising session).  A function
+    and not a ``plan`` method of :class:`DDIMScheduler`: the pipelines' loop picks the fused-sampler path by that attribute, and the
+    default DDIM loop stays on ``imd_ddim_cfg_step``."""
+    a_t, a_prev = float(scheduler.alpha(t)), float(scheduler.alpha_prev(t))
+    sa_t, sa_p = np.sqrt(a_t), np.sqrt(a_prev)
+    return SamplerRow(m_x=0.0, m_e=1.0, z_x=sa_p / sa_t, z_m=np.sqrt(1.0 - a_prev) - sa_p * np.sqrt(1.0 - a_t) / sa_t, keep=False)
+
+
 def _train_alphas_cumprod(num_train_timesteps, beta_start, beta_end, beta_schedule):
     if beta_schedule == "scaled_linear":
         betas = np.linspace(beta_start ** 0.5, beta_end ** 0.5, num_train_timesteps, dtype=np.float64) ** 2

@@ -566,6 +566,16 @@ int imd_ddim_cfg_step_rows(const imd_ddim_params* p, const float* guidance, void
  * -1..K-1 (host coefficients), a mask without z_img / blend_noise, K > 0 without hist, misaligned pointers (16 bytes for the
  * float4 / uint4 tensors, 4 for mask, guidance_rows and coefs). */
 int imd_sampler_step(const imd_sampler_params* p, void* stream);
+/* The same fused step with the coefficient block read PER LATENT ROW (a denoising session: every row is a request at its own
+ * position of its own schedule).  Row b = pixel / HW reads coef_rows[b]; p->coefs and the scalar fields m_x .. store are ignored.
+ * Guidance: p->guidance_rows[b], or p->guidance when that pointer is NULL.  History slot k of row b is still p->hist + k B HW at the
+ * pixel, so each row has its own physical slot map through its own z_h[] and store (store >= K stores nothing).  A row whose
+ * `active` float is 0 is neither read nor written: its z, its pixels of every history slot and of both CFG halves of x_next keep
+ * their bytes.  With every row equal and active it is bit-identical to imd_sampler_step.  Errors without launching: a foreign
+ * struct_bytes, coef_rows NULL or not 16-byte aligned, and every pointer / K / mask condition of imd_sampler_step. */
+#define IMD_SAMPLER_ROW_FLOATS 16   /* per latent row: [0..12] the coefficient block in imd_sampler_params.coefs order,
+                                       [13] active (0: the row is skipped), [14..15] reserved, 0 */
+int imd_sampler_step_rows(const imd_sampler_params* p, const float* coef_rows /* DEVICE [B][16] fp32 */, void* stream);
 
 /* Pillow-exact resize (+ crop, normalise, layout) of uint8 images on the device; see imd_image_resample_params.  Errors without
  * launching: a foreign struct size, null src / out, C outside {1, 3}, an incomplete table or a skipped axis whose size changes, a
