@@ -436,9 +436,7 @@ __device__ __attribute__((always_inline)) bool attn40_body(const AttnParams& p) 
             constexpr int SLOT = decltype(slot_c)::value;
 #pragma unroll
             for (int i = 0; i < NPIECE; ++i) {
-                asm volatile("s_add_u32 m0, %1, %3\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %2, 0 offen lds"
-                             : : "v"(scur[i]), "s"(sdst[i]), "s"(sdsc[i]), "n"(SLOT * BUF_D) : "memory", "scc");
-                scur[i] += sstr[i];
+                dma16_run<SLOT * BUF_D>(sdsc[i], sdst[i], scur[i], sstr[i]);
             }
         };
         auto dma_unit = [&](int u, int bufi) {     // u >= 1 inside the loop: no range logic at all (rows / columns past the end read 0)

@@ -308,6 +308,7 @@ __global__ __launch_bounds__(WAVES_M * WAVES_N * 64, (WAVES_M * WAVES_N == 4) ? 
         if (wr + 1 < WAVES_M) __syncthreads();
     }
     if (want_stats) {
+        // (gemm_common.h::gn_stats_fold_store written out: as a helper, in any of four shapes, it moved registers in the split-K code behind it)
         __syncthreads();                        // the fp32 tile in LDS is dead: its head takes the NT x 4 partials
         float* red = reinterpret_cast<float*>(smem);
         *reinterpret_cast<float4*>(red + tid * 4) = make_float4(st[0], st[1], st[2], st[3]);

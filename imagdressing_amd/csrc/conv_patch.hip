@@ -15,65 +15,32 @@
 // Pipeline: A patch double-buffered across channel chunks (fetched during tap 0, written after tap 8), weight tile
 // double-buffered across taps, one barrier per tap; epilogue shared with conv_gemm.hip (bias / time-embedding
 // vector / residual / activation fused, coalesced 16-byte stores); optional split over channel chunks.
-#include <type_traits>
-
-#include "gemm_common.h"
-#include "lds_dma.h"
+//
+// The blocks shared with the other halo-patch kernels -- the tile constants (TH, TW, PW, NPIX, CK, BN, CLD, EROWS), the MFMA-column ->
+// pixel table, the tile decode, the K-slice range, the LDS-DMA geometry PD<CKD>, the staging piece, the host-side predicates and launch
+// body -- live in patch_common.h.
+#include "patch_common.h"
 
 namespace {
 
-constexpr int TH = 8, TW = 16;                 // output pixels per workgroup: 8 rows x 16 columns
-constexpr int PW = TW + 2, PH = TH + 2;        // halo patch
-constexpr int NPIX = PH * PW;                  // 180 patch pixels
-constexpr int CK = 32;                         // channels per chunk
-constexpr int RSTR = CK * 2 + 16;              // 80-byte LDS rows (5 x 16 B: odd slot count)
-constexpr int BN = 128;
+constexpr int RSTR = CK * 2 + 16;              // register-staged form: 80-byte LDS rows (5 x 16 B: odd slot count)
 constexpr int A_BYTES = NPIX * RSTR;           // 14,400
 constexpr int W_BYTES = BN * RSTR;             // 10,240
 constexpr int MAIN_LDS = 2 * A_BYTES + 2 * W_BYTES;   // 49,280
-constexpr int CLD = BN + 4;
-constexpr int EROWS = 64;
-constexpr int EPI_LDS = EROWS * CLD * 4;       // 33,792
 constexpr int PATCH_LDS = MAIN_LDS > EPI_LDS ? MAIN_LDS : EPI_LDS;
 constexpr int A_VECS = (NPIX * (CK / 8) + 255) / 256;   // 3
-// MFMA column (lane & 31) -> pixel of the wave's 2 x 16 pixel block.  ds_read_b128 is serviced in the 16-lane groups
-// {0-3,12-15,20-27} / {4-11,16-19,28-31}; with the identity mapping the second image row (patch rows +18) lands two
-// lanes of a group on one 16-byte bank slot (2-way conflict on every activation fragment).  This permutation gives
-// each group 16 patch rows that are distinct mod 16, i.e. conflict-free at the 80-byte row stride.
-__device__ constexpr unsigned char kColPix[32] = {0, 1, 2, 3, 8, 9, 10, 11, 12, 13, 14, 15, 4, 5, 6, 7,
-                                                  30, 31, 16, 17, 22, 23, 24, 25, 26, 27, 28, 29, 18, 19, 20, 21};
 constexpr int W_VECS = BN * (CK / 8) / 256;             // 2
 
 // DMA (round 3): BOTH operands reach LDS by LDS-DMA (`buffer_load ... lds`), nothing is staged through registers.  The halo patch
 // of a 32-channel chunk (180 pixel rows x 64 B, 12 one-KB pieces) and the weight tile of a tap (128 rows x 64 B, 8 pieces) are
-// written lane-linear, i.e. as unpadded 64-byte rows; fragment reads stay conflict-free through a SOURCE-side swizzle -- piece
-// c of row r sits at position c ^ ((r >> 2) & 3), so the 16 rows of a ds_read_b128 lane group (any 8 + 8 consecutive rows of the
-// patch, or 4 aligned row quadruples of the weight tile) fall on 16 distinct 16-byte bank slots.  Weight tiles run through a
-// ring of three taps (tap t + 2 in flight while tap t is multiplied, counted s_waitcnt); the next chunk's patch is fetched at
-// tap 5 into the other patch buffer; out-of-image halo pixels and rows / taps past the end are out-of-range offsets that the
-// DMA turns into zeros.  Against the register-staged form: no VGPR -> LDS stores (the slow LDS write path: ~79 B/clk) and no
-// staging registers.  48 KB of LDS -> 3 workgroups per CU as before.  The fused GroupNorm prologue needs the values in
-// registers and keeps the register-staged kernel.
-constexpr int AB_D = 12 * 1024, WB_D = 8 * 1024, NWR_D = 3;
-constexpr int PATCH_DMA_LDS = 2 * AB_D + NWR_D * WB_D;            // 49,152 (>= EPI_LDS)
-static_assert(PATCH_DMA_LDS >= EPI_LDS, "the epilogue tile must fit the main-loop LDS");
-// CKD = 64 (tile config 29, round 4): 64-channel chunks = 128-BYTE rows.  The L2 hands a CU whole 128-byte lines (tools/probes/staging_probe.hip:
-// 62 GB/s per CU in 64-byte segments, 113 in 128-byte ones); the 64-byte rows above use half of every line they pull.  Patch 180 x 128 B (23 pieces,
-// six per wave with one empty), weight tile 128 x 128 B (16 pieces, four per wave), piece c of row r at c ^ ((r >> 1) & 7); 16 MFMAs per wave and
-// tap.  80 KB of LDS with a TWO-slot weight ring (the next tap's tile lands while this tap is multiplied) -> two workgroups per CU.
-template <int CKD> struct PD {
-    static constexpr int RB = CKD * 2, LPR = RB / 16;                       // row bytes, 16-byte pieces per row
-    static constexpr int APIECES = (NPIX * RB + 1023) / 1024;               // 12 | 23
-    static constexpr int APW = (APIECES + 3) / 4;                           // patch pieces per wave: 3 | 6
-    static constexpr int AB = APW * 4 * 1024;                               // 12,288 | 24,576
-    static constexpr int WPW = BN * RB / 1024 / 4;                          // weight pieces per wave and tap: 2 | 4
-    static constexpr int WB = WPW * 4 * 1024;                               // 8,192 | 16,384
-    static constexpr int NWR = CKD == 32 ? 3 : 2;
-    static constexpr int LDS = 2 * AB + NWR * WB;                           // 49,152 | 81,920
-    static_assert(LDS >= EPI_LDS, "the epilogue tile must fit the main-loop LDS");
-    static __device__ __forceinline__ int swz(int r) { return CKD == 32 ? (r >> 2) & 3 : (r >> 1) & 7; }
-};
-
+// written lane-linear as unpadded, source-side swizzled rows (patch_common.h::PD).  Weight tiles run through a ring of three taps
+// (tap t + 2 in flight while tap t is multiplied, counted s_waitcnt); the next chunk's patch is fetched at tap 5 into the other
+// patch buffer; out-of-image halo pixels and rows / taps past the end are out-of-range offsets that the DMA turns into zeros.
+// Against the register-staged form: no VGPR -> LDS stores (the slow LDS write path: ~79 B/clk) and no staging registers.  48 KB of
+// LDS -> 3 workgroups per CU as before.  The fused GroupNorm prologue needs the values in registers and keeps the register-staged
+// kernel.
+// CKD = 64 (tile config 29, round 4): 64-channel chunks = 128-byte rows, 16 MFMAs per wave and tap, a TWO-slot weight ring (the next
+// tap's tile lands while this tap is multiplied), 80 KB of LDS -> two workgroups per CU (geometry and why 128-byte rows: PD).
 template <bool F16, bool DMA, int CKD = 32>
 __global__ __launch_bounds__(256, CKD == 32 ? 3 : 2) void conv3x3_patch_kernel(const ConvGemmParams p) {
     static_assert(CKD == 32 || DMA, "64-channel chunks exist for the LDS-DMA form only");
@@ -81,7 +48,7 @@ __global__ __launch_bounds__(256, CKD == 32 ? 3 : 2) void conv3x3_patch_kernel(c
     using E = El<F16>;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* const Abuf = smem;
-    char* const Wbuf = smem + 2 * A_BYTES;
+    char* const Wbuf = smem + 2 * A_BYTES;      // (both of the register-staged form only; they stay here: moved into its branch with their users, that form compiled differently)
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -92,27 +59,11 @@ __global__ __launch_bounds__(256, CKD == 32 ? 3 : 2) void conv3x3_patch_kernel(c
     const int cpix = kColPix[col];             // pixel (0..31) this lane's MFMA column stands for
 
     const int H = p.Hout, W = p.Wout;          // output map = logical input map (fused nearest-2x upsample: twice the stored input, DMA path only)
-    // ragged maps (96 x 72 latents of the 768 x 576 configuration: W = 72, 36, 18): the last tile row / column hangs over the
-    // edge; its patch pixels outside the image read as zero like any halo pixel and its output pixels are not stored
-    const int tiles_x = (W + TW - 1) / TW, tiles_y = (H + TH - 1) / TH;
-    const int n_tiles = (p.N + BN - 1) / BN;
-    int bid, tile_n;
-    xcd_tile_order(p.flags, (int)(gridDim.x / n_tiles), n_tiles, bid, tile_n);      // bid = pixel-tile index
-    const int tile_id = bid * n_tiles + tile_n;
-    const int tx = bid % tiles_x; bid /= tiles_x;
-    const int ty = bid % tiles_y;
-    const int b = bid / tiles_y;
-    const int y0 = ty * TH, x0 = tx * TW, n0 = tile_n * BN;
-
-    const int nchunks = p.Cin / CKD;
+    const HaloTile tl = halo_tile<TH, TW, BN>(p, H, W);
+    const int b = tl.b, y0 = tl.ty * TH, x0 = tl.tx * TW, n0 = tl.tile_n * BN;
     const int split = blockIdx.y;
-    const int per = (nchunks + p.split_k - 1) / p.split_k;
-    const int c_begin = split * per;
-#ifdef PATCH_T_NOLOOP
-    const int c_end = c_begin;                  // timing probe: launch + prologue + epilogue only
-#else
-    const int c_end = min(nchunks, c_begin + per);
-#endif
+    const KSlice ks = k_slice<CKD>(p, split);
+    const int c_begin = ks.c_begin, c_end = ks.c_end;
 
     const __amdgpu_buffer_rsrc_t rs_x = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(p.x), 0, p.x_bytes, 0x00020000);
     const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(p.w), 0, p.w_bytes, 0x00020000);
@@ -218,9 +169,8 @@ __global__ __launch_bounds__(256, CKD == 32 ? 3 : 2) void conv3x3_patch_kernel(c
         //   * every LDS address of the loop is a compile-time offset from a loop-invariant register: the 9 x 2 x 2 activation-fragment
         //     addresses (tap, pixel block, 16-deep slice) are computed ONCE, the chunk loop is unrolled over its two patch buffers and the
         //     nine taps over the three weight-ring slots;
-        //   * a staging piece is three instructions (s_add m0 / s_nop / buffer_load ... lds) on a RUNNING source offset (+ one add per tap);
-        //     out-of-image halo pixels and channel rows past N carry the offset 2^31, which stays out of range under the running adds (the
-        //     operands are < 2 GiB: checked by the launcher); pieces staged past the last tap / chunk read in-range bytes nobody multiplies;
+        //   * a staging piece is three instructions on a RUNNING source offset (+ one add per tap); out-of-image halo pixels and channel
+        //     rows past N carry the offset 2^31 (lds_dma.h::dma16_run has the piece, its hazard and the 2^31 argument);
         //   * the "this wave owns no valid channel" test (last channel tile of N = 320) is a scalar branch.
         // Same MFMA order per accumulator as before: bit-identical results.
         const int wv = __builtin_amdgcn_readfirstlane(wave);
@@ -235,10 +185,8 @@ __global__ __launch_bounds__(256, CKD == 32 ? 3 : 2) void conv3x3_patch_kernel(c
             acur[i] = FAR;
             if (pp < NPIX) {
                 const int iy = y0 - 1 + pp / PW, ix = x0 - 1 + pp % PW;        // logical pixel; the zero halo is applied AFTER the upsample
-                if ((unsigned)iy < (unsigned)H && (unsigned)ix < (unsigned)W) {
-                    const int sy = p.ups ? (iy >> 1) : iy, sx = p.ups ? (ix >> 1) : ix;     // nearest-2x: source pixel = logical pixel >> 1
-                    acur[i] = (uint32_t)(((b * p.Hin + sy) * p.Win + sx) * p.x_pix_stride + piece * 8 + c_begin * CKD) * 2u;
-                }
+                if ((unsigned)iy < (unsigned)H && (unsigned)ix < (unsigned)W)
+                    acur[i] = (uint32_t)(halo_src_pixel(p, b, iy, ix) * p.x_pix_stride + piece * 8 + c_begin * CKD) * 2u;
             }
             adst[i] = smem_base + (uint32_t)((wv * G::APW + i) * 1024);
         }
@@ -251,21 +199,13 @@ __global__ __launch_bounds__(256, CKD == 32 ? 3 : 2) void conv3x3_patch_kernel(c
         const uint32_t w_tap = (uint32_t)(p.Cin * 2), w_chunk = (uint32_t)(CKD * 2) - 8u * w_tap;      // next tap / tap 8 -> tap 0 of the next chunk
         auto dma_patch = [&](auto buf_c) __attribute__((always_inline)) {
 #pragma unroll
-            for (int i = 0; i < G::APW; ++i) {
-                asm volatile("s_add_u32 m0, %1, %3\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %2, 0 offen lds"
-                             : : "v"(acur[i]), "s"(adst[i]), "s"(dx), "n"(decltype(buf_c)::value * G::AB) : "memory", "scc");
-                acur[i] += (uint32_t)(CKD * 2);
-            }
+            for (int i = 0; i < G::APW; ++i) dma16_run<decltype(buf_c)::value * G::AB>(dx, adst[i], acur[i], (uint32_t)(CKD * 2));
         };
         auto dma_w = [&](auto ring_c, auto cross_c) __attribute__((always_inline)) {
 #pragma unroll
-            for (int i = 0; i < G::WPW; ++i) {
-                asm volatile("s_add_u32 m0, %1, %3\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %2, 0 offen lds"
-                             : : "v"(wcur[i]), "s"(wdst[i]), "s"(dw), "n"(decltype(ring_c)::value * G::WB) : "memory", "scc");
-                wcur[i] += decltype(cross_c)::value ? w_chunk : w_tap;
-            }
+            for (int i = 0; i < G::WPW; ++i) dma16_run<decltype(ring_c)::value * G::WB>(dw, wdst[i], wcur[i], decltype(cross_c)::value ? w_chunk : w_tap);
         };
-        // fragment addresses (bytes inside a patch buffer / a ring slot), all loop-invariant
+        // fragment addresses (bytes inside a patch buffer / a ring slot), all loop-invariant (inline in every member: as a helper one v_bitop3 got its operands swapped)
         int w_fr[2], xa[9][2];            // 16-deep slice kk = 0; slice kk is the same address ^ (kk << 5) (one VALU in the loop instead of more live registers)
 #pragma unroll
         for (int a = 0; a < 2; ++a) {
@@ -444,12 +384,7 @@ __global__ __launch_bounds__(256, CKD == 32 ? 3 : 2) void conv3x3_patch_kernel(c
 #pragma unroll
             for (int bb = 0; bb < 2; ++bb)
 #pragma unroll
-                for (int a = 0; a < 2; ++a)
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        float* dst = Cs + (bb * 32 + cpix) * CLD + wn0 + a * 32 + 8 * j + 4 * hi;
-                        *reinterpret_cast<float4*>(dst) = make_float4(acc[a][bb][4 * j], acc[a][bb][4 * j + 1], acc[a][bb][4 * j + 2], acc[a][bb][4 * j + 3]);
-                    }
+                for (int a = 0; a < 2; ++a) acc_to_lds<CLD>(Cs, bb * 32 + cpix, wn0 + a * 32, hi, acc[a][bb]);
         }
         __syncthreads();
 #pragma unroll
@@ -470,9 +405,7 @@ __global__ __launch_bounds__(256, CKD == 32 ? 3 : 2) void conv3x3_patch_kernel(c
 #pragma unroll
                     for (int e = 0; e < 8; ++e) {
                         if (e < nv) {
-                            // statistics of the STORED tensor (the value after rounding to 16 bits): what the standalone gn_stats_kernel and the
-                            // reference's GroupNorm see, so the result does not depend on which kernel produced the tensor
-                            const float r = E::tof(E::fromf(v[e]));
+                            const float r = E::tof(E::fromf(v[e]));       // statistics of the STORED tensor (gemm_common.h)
                             if (e < st_split) { st[0] += r; st[1] += r * r; }
                             else { st[2] += r; st[3] += r * r; }
                         }
@@ -482,33 +415,11 @@ __global__ __launch_bounds__(256, CKD == 32 ? 3 : 2) void conv3x3_patch_kernel(c
         }
         if (wr == 0) __syncthreads();
     }
-    if (want_stats) {
-        __syncthreads();                        // the fp32 tile in LDS is dead: reuse its head for the 256 x 4 partials
-        float* red = reinterpret_cast<float*>(smem);
-        *reinterpret_cast<float4*>(red + tid * 4) = make_float4(st[0], st[1], st[2], st[3]);
-        __syncthreads();
-        const int G = p.gn_stats_groups;
-        if (tid < G) {                          // fixed summation order: column chunk, then row lane (deterministic)
-            const int g = tid;
-            float S = 0.f, Q = 0.f;
-            for (int j = 0; j < CPR; ++j) {
-                const int nj = n0 + 8 * j;
-                if (nj >= p.N) break;
-                const int gj = nj / cpg;
-                if (gj == g || gj + 1 == g) {
-                    const int o = (gj == g) ? 0 : 2;
-                    for (int rl = 0; rl < 256 / CPR; ++rl) { S += red[(j + CPR * rl) * 4 + o]; Q += red[(j + CPR * rl) * 4 + o + 1]; }
-                }
-            }
-            const int nparts = tiles_y * tiles_x * n_tiles;
-            const int part = (ty * tiles_x + tx) * n_tiles + tile_n;
-            float* dst = p.gn_stats_out + (((size_t)b * nparts + part) * G + g) * 2;
-            dst[0] = S; dst[1] = Q;
-        }
-    }
+    if (want_stats)
+        gn_stats_fold_store<CPR, 256 / CPR>(p, smem, tid, make_float4(st[0], st[1], st[2], st[3]), n0, cpg, b, tl.tiles_y * tl.tiles_x * tl.n_tiles, (tl.ty * tl.tiles_x + tl.tx) * tl.n_tiles + tl.tile_n);
     // K slices summed in-kernel by the tile's last-arriving workgroup (gemm_common.h::splitk_last_arrival)
     if (slab != nullptr && p.splitk_counters != nullptr) {
-        if (splitk_last_arrival(p.splitk_counters, tile_id, p.split_k, tid)) {
+        if (splitk_last_arrival(p.splitk_counters, tl.tile_id, p.split_k, tid)) {
             for (int ch = tid; ch < TH * TW * CPR; ch += 256) {
                 const int q = ch / CPR, cc = (ch - q * CPR) * 8;
                 const int oy = y0 + q / TW, ox = x0 + q % TW;
@@ -524,289 +435,17 @@ __global__ __launch_bounds__(256, CKD == 32 ? 3 : 2) void conv3x3_patch_kernel(c
     }
 }
 
-// ---- nearest-2x upsample + 3x3 conv as four 2x2 PHASE convolutions (Upsample2D: interpolate -> conv) ----
-// After a nearest-2x upsample the four pixels of a 2 x 2 output block see the same 2 x 2 source pixels, so for output phase (py, px)
-//   out[2y + py, 2x + px] = bias + sum_{dy, dx in {0, 1}} W'[py, px][dy, dx] . src[y + py - 1 + dy, x + px - 1 + dx]
-// with W' the 3x3 taps that fall on one source pixel pre-summed (rows: py = 0: {ky 0}, {ky 1, 2}; py = 1: {ky 0, 1}, {ky 2}; the same in x;
-// ops.pack_upsample_phase, once per layer): four taps instead of nine.  A workgroup owns an 8 x 16 tile of SOURCE pixels of one image x 128
-// output channels x one phase and stages the (8+2) x (16+2) source patch of a 32-channel chunk as the 9-tap kernel above does -- directly, no
-// source pixel more than once.  The problem is laid out as N' = 4 N weight rows [phase][channel][tap][Cin]; the phase is the FAST part of the
-// channel-tile index, so the four phases of a pixel tile run next to each other and share the patch in the XCD's L2.
-// Schedule: the three-slot weight ring of the 9-tap kernel with the flattened tap index it = 4 chunk + tap (tap it + 2 in flight while tap it
-// is multiplied); ring slot it % 3 and patch buffer chunk % 2 repeat every 6 chunks = 24 taps, which are unrolled with every LDS address a
-// compile-time offset.  The next chunk's patch is fetched at tap 1 BEHIND that tap's weight pieces; in-order retirement then gives the waits:
-//   end of tap 1: in flight W[it+1], W[it+2], P      -> keep WPW + APW
-//   end of tap 2: in flight W[it+1], P, W[it+2]      -> keep WPW + APW   (W[k] = weight pieces of flattened tap k, `it` = this tap)
-//   end of tap 3: in flight P, W[it+1], W[it+2]      -> keep WPW: the patch has landed before the next chunk's tap 0
-//   end of tap 0: in flight W[it+1], W[it+2]         -> keep WPW
-// Epilogue: bias only (the consumers -- the skip concatenation, the VAE's GroupNorm -- take their own statistics); source pixel (y, x) is
-// stored to output row (b 2H + 2y + py) 2W + 2x + px.
-template <bool F16>
-__global__ __launch_bounds__(256, 3) void conv_ups_phase_kernel(const ConvGemmParams p) {
-    using G = PD<32>;
-    using E = El<F16>;
-    constexpr int CKD = 32, NT = 4;
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = tid >> 6;
-    const int wm0 = (wave >> 1) * 64;          // 2 x 2 waves, each 64 pixels x 64 channels
-    const int wn0 = (wave & 1) * 64;
-    const int hi = lane >> 5, col = lane & 31;
-    const int cpix = kColPix[col];
-
-    const int H = p.Hin, W = p.Win;            // the SOURCE map: tiles, patch and halo live there
-    const int tiles_x = (W + TW - 1) / TW, tiles_y = (H + TH - 1) / TH;
-    const int n_tiles = 4 * ((p.N + BN - 1) / BN);                  // (channel tile, phase), phase fastest
-    int bid, tile_n;
-    xcd_tile_order(p.flags, (int)(gridDim.x / n_tiles), n_tiles, bid, tile_n);
-    const int phase = tile_n & 3, py = phase >> 1, px = phase & 1;
-    const int tx = bid % tiles_x; bid /= tiles_x;
-    const int ty = bid % tiles_y;
-    const int b = bid / tiles_y;
-    const int y0 = ty * TH, x0 = tx * TW, n0 = (tile_n >> 2) * BN;
-    const int nch = p.Cin / CKD;               // >= 1 (launcher)
-
-    const int wv = __builtin_amdgcn_readfirstlane(wave);
-    const uint32_t smem_base = (uint32_t)(uintptr_t)smem;
-    const v4i_t dx = raw_rsrc(p.x, p.x_bytes), dw = raw_rsrc(p.w, p.w_bytes);
-    constexpr uint32_t FAR = 0x80000000u;      // out-of-range under every running add (operands < 2 GiB: launcher)
-    uint32_t acur[G::APW], wcur[G::WPW], adst[G::APW], wdst[G::WPW];
-#pragma unroll
-    for (int i = 0; i < G::APW; ++i) {
-        const int slot = (wv * G::APW + i) * 64 + lane, pp = slot / G::LPR, piece = (slot % G::LPR) ^ G::swz(pp);
-        acur[i] = FAR;
-        if (pp < NPIX) {
-            const int iy = y0 - 1 + pp / PW, ix = x0 - 1 + pp % PW;
-            if ((unsigned)iy < (unsigned)H && (unsigned)ix < (unsigned)W)
-                acur[i] = (uint32_t)(((b * H + iy) * W + ix) * p.x_pix_stride + piece * 8) * 2u;
-        }
-        adst[i] = smem_base + (uint32_t)((wv * G::APW + i) * 1024);
-    }
-    const int Kp = NT * p.Cin;                 // elements of a packed weight row: [tap][Cin]
-#pragma unroll
-    for (int i = 0; i < G::WPW; ++i) {
-        const int slot = (wv * G::WPW + i) * 64 + lane, row = slot / G::LPR, piece = (slot % G::LPR) ^ G::swz(row);
-        wcur[i] = (n0 + row < p.N) ? (uint32_t)((((size_t)phase * p.N + n0 + row) * Kp + piece * 8) * 2) : FAR;
-        wdst[i] = smem_base + (uint32_t)(2 * G::AB + (wv * G::WPW + i) * 1024);
-    }
-    const uint32_t w_tap = (uint32_t)(p.Cin * 2), w_chunk = (uint32_t)(CKD * 2) - (uint32_t)(NT - 1) * w_tap;     // next tap / tap 3 -> tap 0 of the next chunk
-    auto dma_patch = [&](auto buf_c) __attribute__((always_inline)) {
-#pragma unroll
-        for (int i = 0; i < G::APW; ++i) {
-            asm volatile("s_add_u32 m0, %1, %3\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %2, 0 offen lds"
-                         : : "v"(acur[i]), "s"(adst[i]), "s"(dx), "n"(decltype(buf_c)::value * G::AB) : "memory", "scc");
-            acur[i] += (uint32_t)(CKD * 2);
-        }
-    };
-    auto dma_w = [&](auto ring_c) __attribute__((always_inline)) {
-#pragma unroll
-        for (int i = 0; i < G::WPW; ++i) {
-            asm volatile("s_add_u32 m0, %1, %3\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %2, 0 offen lds"
-                         : : "v"(wcur[i]), "s"(wdst[i]), "s"(dw), "n"(decltype(ring_c)::value * G::WB) : "memory", "scc");
-            wcur[i] += w_tap;
-        }
-    };
-    int w_fr[2], xa[NT][2];       // fragment addresses of the 16-deep slice kk = 0 (slice kk: the same address ^ (kk << 5)), loop-invariant
-#pragma unroll
-    for (int a = 0; a < 2; ++a) {
-        const int row = wn0 + a * 32 + col;
-        w_fr[a] = row * G::RB + ((hi ^ G::swz(row)) << 4);
-    }
-#pragma unroll
-    for (int bb = 0; bb < 2; ++bb) {
-        const int q = wm0 + bb * 32 + cpix, r0 = (q / TW) * PW + (q % TW);
-#pragma unroll
-        for (int t = 0; t < NT; ++t) {
-            const int rw = r0 + (py + (t >> 1)) * PW + (px + (t & 1));      // tap (dy, dx) of phase (py, px): patch rows + py + dy, columns + px + dx
-            xa[t][bb] = rw * G::RB + ((hi ^ G::swz(rw)) << 4);
-        }
-    }
-    const bool live = __builtin_amdgcn_readfirstlane((int)(n0 + (wv & 1) * 64 < p.N)) != 0;      // scalar: the whole wave or nothing
-
-    f32x16 acc[2][2];
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int bb = 0; bb < 2; ++bb)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[a][bb][r] = 0.f;
-
-    const std::integral_constant<int, 0> i0{}; const std::integral_constant<int, 1> i1{}; const std::integral_constant<int, 2> i2{};
-    dma_patch(i0);
-    dma_w(i0);
-    dma_w(i1);
-    dma_wait();
-    __syncthreads();
-    auto chunk = [&](auto j_c) __attribute__((always_inline)) {           // chunk 6 k + J: patch buffer J % 2, ring position (4 J) % 3
-        constexpr int J = decltype(j_c)::value, AB = J & 1;
-        const char* As = smem + AB * G::AB;
-#pragma unroll
-        for (int t = 0; t < NT; ++t) {
-            const int cur = (NT * J + t) % 3, nxt = (NT * J + t + 2) % 3;           // (compile-time after unrolling)
-            if (nxt == 0) dma_w(i0); else if (nxt == 1) dma_w(i1); else dma_w(i2);
-            if (t == 1) {                      // (the piece just staged was tap 3: the next one is tap 0 of the next chunk)
-#pragma unroll
-                for (int i = 0; i < G::WPW; ++i) wcur[i] += w_chunk - w_tap;
-                dma_patch(std::integral_constant<int, AB ^ 1>{});            // (always APW pieces: the counted waits rely on it)
-            }
-            if (live) {
-                const char* Wsm = smem + 2 * G::AB + cur * G::WB;
-                uint4 wf[2][2], xf[2][2];
-#pragma unroll
-                for (int kk = 0; kk < 2; ++kk) {
-#pragma unroll
-                    for (int a = 0; a < 2; ++a) wf[kk][a] = *reinterpret_cast<const uint4*>(Wsm + (w_fr[a] ^ (kk * 32)));
-#pragma unroll
-                    for (int bb = 0; bb < 2; ++bb) xf[kk][bb] = *reinterpret_cast<const uint4*>(As + (xa[t][bb] ^ (kk * 32)));
-                }
-#pragma unroll
-                for (int kk = 0; kk < 2; ++kk)
-#pragma unroll
-                    for (int a = 0; a < 2; ++a)
-#pragma unroll
-                        for (int bb = 0; bb < 2; ++bb) acc[a][bb] = E::mfma(wf[kk][a], xf[kk][bb], acc[a][bb]);
-            }
-            if (t == 1 || t == 2) dma_wait_keep_n<G::WPW + G::APW>(); else dma_wait_keep_n<G::WPW>();      // (derivation: head of the kernel)
-            __syncthreads();
-        }
-    };
-    {
-        int left = nch;
-#pragma unroll 1
-        for (;;) {
-            chunk(std::integral_constant<int, 0>{}); if (--left == 0) break;
-            chunk(std::integral_constant<int, 1>{}); if (--left == 0) break;
-            chunk(std::integral_constant<int, 2>{}); if (--left == 0) break;
-            chunk(std::integral_constant<int, 3>{}); if (--left == 0) break;
-            chunk(std::integral_constant<int, 4>{}); if (--left == 0) break;
-            chunk(std::integral_constant<int, 5>{}); if (--left == 0) break;
-        }
-    }
-    dma_wait();                  // pieces staged past the end are still landing: the epilogue reuses this LDS
-    __syncthreads();
-
-    // ---- epilogue: one 64-pixel wave-row group at a time through LDS, + bias, 16-byte stores to the phase's output pixels ----
-    float* Cs = reinterpret_cast<float*>(smem);
-    constexpr int CPR = BN / 8;
-    const int cc = (tid % CPR) * 8, n = n0 + cc;
-    const int nv = (n + 8 <= p.N) ? 8 : 4;
-    float4 b0 = make_float4(0, 0, 0, 0), b1 = b0;
-    if (p.bias != nullptr && n < p.N) {
-        b0 = *reinterpret_cast<const float4*>(p.bias + n);
-        if (nv == 8) b1 = *reinterpret_cast<const float4*>(p.bias + n + 4);
-    }
-    bf16_t* const outp = reinterpret_cast<bf16_t*>(p.out);
-#pragma unroll
-    for (int wr = 0; wr < 2; ++wr) {
-        if ((wave >> 1) == wr) {
-#pragma unroll
-            for (int bb = 0; bb < 2; ++bb)
-#pragma unroll
-                for (int a = 0; a < 2; ++a)
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        float* dst = Cs + (bb * 32 + cpix) * CLD + wn0 + a * 32 + 8 * j + 4 * hi;
-                        *reinterpret_cast<float4*>(dst) = make_float4(acc[a][bb][4 * j], acc[a][bb][4 * j + 1], acc[a][bb][4 * j + 2], acc[a][bb][4 * j + 3]);
-                    }
-        }
-        __syncthreads();
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int row = (tid + 256 * i) / CPR;                  // 0 .. 63 (the column block `cc` is the same for every i: 256 % CPR == 0)
-            const int q = wr * EROWS + row;
-            const int sy = y0 + q / TW, sx = x0 + q % TW;
-            if (n >= p.N || sy >= H || sx >= W) continue;
-            const size_t m = ((size_t)(b * 2 * H + 2 * sy + py)) * (size_t)(2 * W) + (size_t)(2 * sx + px);
-            const float4 v0 = *reinterpret_cast<const float4*>(Cs + row * CLD + cc);
-            const float4 v1 = *reinterpret_cast<const float4*>(Cs + row * CLD + cc + 4);
-            const float v[8] = {v0.x + b0.x, v0.y + b0.y, v0.z + b0.z, v0.w + b0.w, v1.x + b1.x, v1.y + b1.y, v1.z + b1.z, v1.w + b1.w};
-            bf16_t* dst = outp + m * (size_t)p.out_ld + n;
-            if (nv == 8) *reinterpret_cast<uint4*>(dst) = pack8<F16>(v);
-            else *reinterpret_cast<uint2*>(dst) = make_uint2(E::pack2(v[0], v[1]), E::pack2(v[2], v[3]));
-        }
-        if (wr == 0) __syncthreads();
-    }
-}
-
 }  // namespace
-
-// tile-padded multiply counts per image and output channel, in units of 128 pixels x one tap: the phase form runs 4 phases x 4 taps per
-// 8 x 16 SOURCE tile, the 9-tap form 9 taps per 8 x 16 tile of the OUTPUT map
-static long ups_phase_units(int Hin, int Win) { return 16L * ((Hin + TH - 1) / TH) * ((Win + TW - 1) / TW); }
-static long ups_9tap_units(int Hout, int Wout) { return 9L * ((Hout + TH - 1) / TH) * ((Wout + TW - 1) / TW); }
-
-// Upsample2D as four phase convolutions: p describes the 9-tap problem (taps = 9, K = 9 Cin, ups = 1), p.w holds the PHASE weights.
-// What the kernel can RUN (the launcher's own check) ...
-static bool ups_phase_can_run(const ConvGemmParams& p) {
-    if (!(p.taps == 9 && p.stride == 1 && p.ups && !p.pad_br_only && p.Hin > 0 && p.Win > 0 && p.Hout == 2 * p.Hin && p.Wout == 2 * p.Win)) return false;
-    if (p.Cin < CK || (p.Cin % CK) != 0 || p.K != 9 * p.Cin || p.N <= 0 || (p.N % 4) != 0 || p.M <= 0 || (p.M % (p.Hout * p.Wout)) != 0) return false;
-    if (p.x_pix_stride != p.Cin || p.out_ld != p.N || p.out_f32 || p.mode != OUT_ROWMAJOR) return false;                 // contiguous 16-bit input and output
-    if (p.dtype != IMD_DTYPE_BF16 && p.dtype != IMD_DTYPE_F16) return false;
-    // bias only
-    if (p.res != nullptr || p.res_rows != 0 || p.rowvec != nullptr || p.gn_a != nullptr || p.gn_b != nullptr || p.gn_stats_out != nullptr || p.gn_in_partial != nullptr ||
-        p.gn_out_gamma != nullptr || p.act != ACT_NONE || p.split_k > 1 || p.out_scale != 1.0f)
-        return false;
-    const size_t xb = (size_t)(p.M / 4) * p.Cin * 2, wb = (size_t)16 * p.N * p.Cin * 2, ob = (size_t)p.M * p.N * 2;
-    return xb < 0x80000000ull && wb < 0x80000000ull && ob < 0x80000000ull;
-}
-
-static long ups_phase_blocks(const ConvGemmParams& p) {
-    return (long)(p.M / (p.Hout * p.Wout)) * ((p.Hin + TH - 1) / TH) * ((p.Win + TW - 1) / TW) * 4 * ((p.N + BN - 1) / BN);
-}
-
-// ... and where it PAYS (the query a dispatcher asks): only there does a layer leave the 9-tap path, whose results it does not reproduce bit for bit
-constexpr long UPS_PHASE_MIN_BLOCKS = 160;
-bool imd_conv_ups_phase_supported_of(const ConvGemmParams& p) {
-    if (!ups_phase_can_run(p)) return false;
-    // The kernel takes no K slices, so a grid that leaves most CUs idle loses to the K-sliced 9-tap launch: measured 41.2 against 43.4 us (launch + finish) at
-    // 80 workgroups (one image, 16 x 16 source, 1280 channels) -- no gain -- and 24.5 against 44.4 / 43.0 against 69.4 us at 160 (one image 32 x 32 x 640 / two
-    // images 16 x 16 x 1280).  160 is the smallest grid at which a gain has been measured; smaller layers stay where they were
-    if (ups_phase_blocks(p) < UPS_PHASE_MIN_BLOCKS) return false;
-    // The phase form must do clearly fewer tile-padded multiplies than the 9-tap form.  It stages 4 weight tiles per patch fetch instead of 9
-    // (about 18 % more staged bytes per MFMA), so its count is weighted 6 / 5: an 8 x 8 source (16 units against the 18 of its 16 x 16 output map:
-    // the half-empty source tile eats the gain) is refused, the 2.25 x of whole tiles is not
-    return 6 * ups_phase_units(p.Hin, p.Win) < 5 * ups_9tap_units(p.Hout, p.Wout);
-}
-
-int imd_launch_conv_ups_phase(const ConvGemmParams& p_in, hipStream_t s) {
-    // (the launcher runs whatever the kernel computes correctly; whether the launch pays is the query's business)
-    if (!ups_phase_can_run(p_in))
-        return imd_set_error("conv_ups_phase: unsupported problem (needs 3x3 stride 1 with ups, Hout = 2 Hin, Wout = 2 Win, Cin %% 32 == 0, contiguous 16-bit input / output "
-                             "< 2 GiB, bias only)");
-    ConvGemmParams p = p_in;
-    const unsigned tag = (unsigned)p_in.flags & IMD_TUNING_TAG_MASK;
-    if (tag != 0 && tag != (unsigned)IMD_TUNING_PER_CALL)
-        return imd_set_error("conv_ups_phase: flags = 0x%x on entry is neither 0 nor IMD_TUNING_PER_CALL | bits (an uninitialised parameter block?)", (unsigned)p_in.flags);
-    const int gf = (tag == (unsigned)IMD_TUNING_PER_CALL) ? ((p_in.flags & 31) | (g_gemm_flags & ~31)) : g_gemm_flags;
-    p.flags = (gf & 4) ? (4 | (gf & 16)) : 0;          // row-tile major: the four phases (and all channel tiles) of a pixel tile share one XCD's L2
-    p.x_bytes = (uint32_t)((size_t)(p.M / 4) * p.Cin * 2);
-    p.w_bytes = (uint32_t)((size_t)16 * p.N * p.Cin * 2);
-    const bool h = p.dtype == IMD_DTYPE_F16;
-    typedef void (*kern_t)(const ConvGemmParams);
-    const kern_t kern = h ? conv_ups_phase_kernel<true> : conv_ups_phase_kernel<false>;
-    if (int rc_attr = imd_lds_attr(reinterpret_cast<const void*>(kern), PD<32>::LDS, "conv_ups_phase")) return rc_attr;
-    const long blocks = ups_phase_blocks(p);
-    if (blocks > 0x7fffffffL) return imd_set_error("conv_ups_phase: grid too large");
-    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(256), PD<32>::LDS, s, p);
-    return imd_check_launch("conv_ups_phase");
-}
 
 // statistic partials per image written through gn_stats_out (0: this launch cannot produce them)
 int imd_conv_patch_stats_parts_of(const ConvGemmParams& p) {
-    if (!imd_conv_patch_supported(p) || p.split_k > 1 || p.out_f32 || p.gn_stats_groups <= 0 || p.gn_stats_groups > 64 ||
-        p.N % p.gn_stats_groups || (p.N / p.gn_stats_groups) < 8)
-        return 0;
-    return ((p.Hout + TH - 1) / TH) * ((p.Wout + TW - 1) / TW) * ((p.N + BN - 1) / BN);
+    if (!imd_conv_patch_supported(p) || !halo_stats_ok(p)) return 0;
+    return halo_tiles(p.Hout, p.Wout, p.N, TH, TW, BN);
 }
 
 bool imd_conv_patch_supported(const ConvGemmParams& p) {
     // the fused nearest-2x upsample (Upsample2D: interpolate -> conv) is a source-pixel map of the LDS-DMA staging only
-    const bool geom = p.ups ? (p.Hout == 2 * p.Hin && p.Wout == 2 * p.Win && p.gn_a == nullptr && !(g_gemm_flags & 512))
-                            : (p.Hin == p.Hout && p.Win == p.Wout);
-    return p.taps == 9 && p.stride == 1 && !p.pad_br_only && geom && p.Hout >= TH && p.Wout >= TW && (p.Cin % CK) == 0 &&
-           p.mode == OUT_ROWMAJOR && p.act != ACT_GEGLU;
+    return halo_geometry(p, TH, TW, CK) && (!p.ups || (p.gn_a == nullptr && !(g_gemm_flags & 512)));
 }
 
 // tile config 29: the LDS-DMA form with 64-channel chunks (128-byte rows)
@@ -817,13 +456,8 @@ bool imd_conv_patch64_supported(const ConvGemmParams& p) {
 int imd_launch_conv_patch64(const ConvGemmParams& p, hipStream_t s) {
     if (!imd_conv_patch64_supported(p)) return imd_set_error("conv_patch (128-byte rows): unsupported problem (needs 3x3 stride 1, H >= 8, W >= 16, Cin %% 64 == 0, operands < 2 GiB, no fused GroupNorm)");
     const bool h = p.dtype == IMD_DTYPE_F16;
-    typedef void (*kern_t)(const ConvGemmParams);
-    const kern_t kern = h ? conv3x3_patch_kernel<true, true, 64> : conv3x3_patch_kernel<false, true, 64>;
-    if (int rc_attr = imd_lds_attr(reinterpret_cast<const void*>(kern), PD<64>::LDS, "conv_patch")) return rc_attr;
-    const int B = p.M / (p.Hout * p.Wout);
-    const long blocks = (long)B * ((p.Hout + TH - 1) / TH) * ((p.Wout + TW - 1) / TW) * ((p.N + BN - 1) / BN);
-    hipLaunchKernelGGL(kern, dim3((unsigned)blocks, (unsigned)p.split_k), dim3(256), PD<64>::LDS, s, p);
-    return imd_check_launch("conv_patch (128-byte rows)");
+    return halo_launch(h ? conv3x3_patch_kernel<true, true, 64> : conv3x3_patch_kernel<false, true, 64>, p, halo_blocks(p, TH, TW, BN), p.split_k, 256, PD<64>::LDS,
+                       "conv_patch (128-byte rows)", s);
 }
 
 int imd_launch_conv_patch(const ConvGemmParams& p, hipStream_t s) {
@@ -833,13 +467,7 @@ int imd_launch_conv_patch(const ConvGemmParams& p, hipStream_t s) {
     // bit 9 selects the round-1/2 register-staged form (A/B)
     const bool dma = p.gn_a == nullptr && !(g_gemm_flags & 512) && (p.ups || (p.x_bytes < 0x80000000u && p.w_bytes < 0x80000000u));   // (the DMA loop marks out-of-range pieces with offset 2^31)
     if (p.ups && (p.x_bytes >= 0x80000000u || p.w_bytes >= 0x80000000u)) return imd_set_error("conv_patch: fused upsample needs operands < 2 GiB");
-    typedef void (*kern_t)(const ConvGemmParams);
-    const kern_t kern = dma ? (h ? conv3x3_patch_kernel<true, true> : conv3x3_patch_kernel<false, true>)
-                            : (h ? conv3x3_patch_kernel<true, false> : conv3x3_patch_kernel<false, false>);
-    const int lds = dma ? PATCH_DMA_LDS : PATCH_LDS;
-    if (int rc_attr = imd_lds_attr(reinterpret_cast<const void*>(kern), lds, "conv_patch")) return rc_attr;
-    const int B = p.M / (p.Hout * p.Wout);
-    const long blocks = (long)B * ((p.Hout + TH - 1) / TH) * ((p.Wout + TW - 1) / TW) * ((p.N + BN - 1) / BN);
-    hipLaunchKernelGGL(kern, dim3((unsigned)blocks, (unsigned)p.split_k), dim3(256), lds, s, p);
-    return imd_check_launch("conv_patch");
+    const halo_kern_t kern = dma ? (h ? conv3x3_patch_kernel<true, true> : conv3x3_patch_kernel<false, true>)
+                                 : (h ? conv3x3_patch_kernel<true, false> : conv3x3_patch_kernel<false, false>);
+    return halo_launch(kern, p, halo_blocks(p, TH, TW, BN), p.split_k, 256, dma ? PD<32>::LDS : PATCH_LDS, "conv_patch", s);
 }

@@ -13,8 +13,11 @@
 //   both operands by LDS-DMA, unpadded 64-byte rows with the source-side swizzle of conv_patch.hip (piece c of row r at
 //   c ^ ((r >> 2) & 3)); counted waits; fused nearest-2x upsample by source-pixel map; K slices over channel chunks (fp32 slabs +
 //   the shared finish launch); epilogue shared with conv_gemm.hip.  GroupNorm statistics from the epilogue are NOT produced here.
-#include "gemm_common.h"
-#include "lds_dma.h"
+//
+// This kernel is on the older loop form (dma16 with per-use offsets and out-of-range selects, run-time LDS addresses); of the family's
+// shared blocks (patch_common.h) it uses the MFMA-column -> pixel table, the tile decode, the K-slice range, the accumulator -> LDS
+// copy and the host side.
+#include "patch_common.h"
 
 namespace {
 
@@ -29,9 +32,6 @@ constexpr int PATCH2_LDS = 2 * AB2 + NWR2 * WB2;      // 73,728
 constexpr int CLD2 = BN2 + 4;
 constexpr int EROWS2 = 64;
 static_assert(PATCH2_LDS >= EROWS2 * CLD2 * 4, "the epilogue tile must fit the main-loop LDS");
-// MFMA column (lane & 31) -> pixel of a 2 x 16 pixel block: conv_patch.hip's permutation (conflict-free ds_read_b128 groups)
-__device__ constexpr unsigned char kColPix2[32] = {0, 1, 2, 3, 8, 9, 10, 11, 12, 13, 14, 15, 4, 5, 6, 7,
-                                                   30, 31, 16, 17, 22, 23, 24, 25, 26, 27, 28, 29, 18, 19, 20, 21};
 
 template <bool F16>
 __global__ __launch_bounds__(256, 2) void conv3x3_patch2_kernel(const ConvGemmParams p) {
@@ -43,23 +43,14 @@ __global__ __launch_bounds__(256, 2) void conv3x3_patch2_kernel(const ConvGemmPa
     const int wm0 = (wave >> 1) * 128;         // 2 x 2 waves, each 128 pixels (8 image rows of the tile) x 64 channels
     const int wn0 = (wave & 1) * 64;
     const int hi = lane >> 5, col = lane & 31;
-    const int cpix = kColPix2[col];
+    const int cpix = kColPix[col];
 
     const int H = p.Hout, W = p.Wout;          // output map = logical input map (fused nearest-2x upsample: twice the stored input)
-    const int tiles_x = (W + T2W - 1) / T2W, tiles_y = (H + T2H - 1) / T2H;      // ragged maps: tiles hang over the edge (zeros in, no stores out)
-    const int n_tiles = (p.N + BN2 - 1) / BN2;
-    int bid, tile_n;
-    xcd_tile_order(p.flags, (int)(gridDim.x / n_tiles), n_tiles, bid, tile_n);  // bid = pixel-tile index
-    const int tx = bid % tiles_x; bid /= tiles_x;
-    const int ty = bid % tiles_y;
-    const int b = bid / tiles_y;
-    const int y0 = ty * T2H, x0 = tx * T2W, n0 = tile_n * BN2;
-
-    const int nchunks = p.Cin / CK2;
+    const HaloTile tl = halo_tile<T2H, T2W, BN2>(p, H, W);
+    const int b = tl.b, y0 = tl.ty * T2H, x0 = tl.tx * T2W, n0 = tl.tile_n * BN2;
     const int split = blockIdx.y;
-    const int per = (nchunks + p.split_k - 1) / p.split_k;
-    const int c_begin = split * per;
-    const int c_end = min(nchunks, c_begin + per);
+    const KSlice ks = k_slice<CK2>(p, split);
+    const int c_begin = ks.c_begin, c_end = ks.c_end;
     const int total = max(0, c_end - c_begin) * 9;
 
     f32x16 acc[2][4];
@@ -81,10 +72,8 @@ __global__ __launch_bounds__(256, 2) void conv3x3_patch2_kernel(const ConvGemmPa
         a_src[i] = OOB;
         if (pp < NPIX2) {
             const int iy = y0 - 1 + pp / P2W, ix = x0 - 1 + pp % P2W;            // logical pixel; the zero halo is applied AFTER the upsample
-            if ((unsigned)iy < (unsigned)H && (unsigned)ix < (unsigned)W) {
-                const int sy = p.ups ? (iy >> 1) : iy, sx = p.ups ? (ix >> 1) : ix;
-                a_src[i] = (uint32_t)(((b * p.Hin + sy) * p.Win + sx) * p.x_pix_stride + piece * 8) * 2u;
-            }
+            if ((unsigned)iy < (unsigned)H && (unsigned)ix < (unsigned)W)
+                a_src[i] = (uint32_t)(halo_src_pixel(p, b, iy, ix) * p.x_pix_stride + piece * 8) * 2u;
         }
     }
 #pragma unroll
@@ -181,13 +170,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_patch2_kernel(const ConvGemmPa
 #pragma unroll
             for (int b2 = 0; b2 < 2; ++b2)
 #pragma unroll
-                for (int a = 0; a < 2; ++a)
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        const int bb = 2 * (wr & 1) + b2;
-                        float* dst = Cs + (b2 * 32 + cpix) * CLD2 + wn0 + a * 32 + 8 * j + 4 * hi;
-                        *reinterpret_cast<float4*>(dst) = make_float4(acc[a][bb][4 * j], acc[a][bb][4 * j + 1], acc[a][bb][4 * j + 2], acc[a][bb][4 * j + 3]);
-                    }
+                for (int a = 0; a < 2; ++a) acc_to_lds<CLD2>(Cs, b2 * 32 + cpix, wn0 + a * 32, hi, acc[a][2 * (wr & 1) + b2]);
         }
         __syncthreads();
         for (int ch = tid; ch < CHUNKS; ch += 256) {
@@ -213,9 +196,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_patch2_kernel(const ConvGemmPa
 }  // namespace
 
 bool imd_conv_patch2_supported(const ConvGemmParams& p) {
-    const bool geom = p.ups ? (p.Hout == 2 * p.Hin && p.Wout == 2 * p.Win) : (p.Hin == p.Hout && p.Win == p.Wout);
-    return p.taps == 9 && p.stride == 1 && !p.pad_br_only && geom && p.Hout >= T2H && p.Wout >= T2W && (p.Cin % CK2) == 0 && p.K == 9 * p.Cin &&
-           p.mode == OUT_ROWMAJOR && p.act != ACT_GEGLU && p.gn_a == nullptr && (p.x_pix_stride % 8) == 0;
+    return halo_geometry(p, T2H, T2W, CK2) && p.K == 9 * p.Cin && p.gn_a == nullptr && (p.x_pix_stride % 8) == 0;
 }
 
 int imd_launch_conv_patch2(const ConvGemmParams& p_in, hipStream_t s) {
@@ -224,11 +205,5 @@ int imd_launch_conv_patch2(const ConvGemmParams& p_in, hipStream_t s) {
     ConvGemmParams p = p_in;
     p.gn_stats_out = nullptr;
     const bool h = p.dtype == IMD_DTYPE_F16;
-    typedef void (*kern_t)(const ConvGemmParams);
-    const kern_t kern = h ? conv3x3_patch2_kernel<true> : conv3x3_patch2_kernel<false>;
-    if (int rc_attr = imd_lds_attr(reinterpret_cast<const void*>(kern), PATCH2_LDS, "conv_patch2")) return rc_attr;
-    const int B = p.M / (p.Hout * p.Wout);
-    const long blocks = (long)B * ((p.Hout + T2H - 1) / T2H) * ((p.Wout + T2W - 1) / T2W) * ((p.N + BN2 - 1) / BN2);
-    hipLaunchKernelGGL(kern, dim3((unsigned)blocks, (unsigned)p.split_k), dim3(256), PATCH2_LDS, s, p);
-    return imd_check_launch("conv_patch2");
+    return halo_launch(h ? conv3x3_patch2_kernel<true> : conv3x3_patch2_kernel<false>, p, halo_blocks(p, T2H, T2W, BN2), p.split_k, 256, PATCH2_LDS, "conv_patch2", s);
 }

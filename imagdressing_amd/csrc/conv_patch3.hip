@@ -22,10 +22,10 @@
 // sustains IS their 66-69 us -- and that stream is mostly weights, whose bytes per MFMA fall with the
 // PIXELS a staged weight tile serves.  Here one 10 KB weight tile serves 256 pixels (154 B of staging per MFMA instead of 290), and
 // N = 320 at the bench batch is 128 pixel tiles x 2 channel tiles = 256 workgroups: one per CU, no tail.  78 KB of LDS.
-#include <type_traits>
-
-#include "gemm_common.h"
-#include "lds_dma.h"
+//
+// The blocks shared with the other halo-patch kernels (the MFMA-column -> pixel table, tile decode, K-slice range, staging piece,
+// GroupNorm-statistics epilogue, host-side predicates and launch body): patch_common.h.
+#include "patch_common.h"
 
 namespace {
 
@@ -45,9 +45,6 @@ template <int NW> struct T3 {
     static_assert(APIECES * 16 >= NPIX, "the patch must fit its pieces");
     static_assert(LDS >= EROWS3 * CLD3 * 4, "the epilogue tile must fit the main-loop LDS");
 };
-// MFMA column (lane & 31) -> pixel of a 2 x 16 pixel block: conv_patch.hip's permutation (conflict-free ds_read_b128 groups)
-__device__ constexpr unsigned char kColPix3[32] = {0, 1, 2, 3, 8, 9, 10, 11, 12, 13, 14, 15, 4, 5, 6, 7,
-                                                   30, 31, 16, 17, 22, 23, 24, 25, 26, 27, 28, 29, 18, 19, 20, 21};
 
 // (launch bound 2 also for NW = 8, which runs one workgroup per CU: under the resulting 128-register cap hipcc fits the eight-wave body in 100 VGPRs
 // with NO scratch (-Rpass-analysis=kernel-resource-usage); with the cap lifted it takes 198 for the same loop -- the shipped, measured code is kept)
@@ -61,23 +58,14 @@ __global__ __launch_bounds__(NW * 64, 2) void conv3x3_patch3_kernel(const ConvGe
     const int lane = tid & 63;
     const int wave = tid >> 6;
     const int hi = lane >> 5, col = lane & 31;
-    const int cpix = kColPix3[col];
+    const int cpix = kColPix[col];
 
     const int H = p.Hout, W = p.Wout;          // output map = logical input map (fused nearest-2x upsample: twice the stored input)
-    const int tiles_x = (W + T3W - 1) / T3W, tiles_y = (H + T3H - 1) / T3H;      // ragged maps: tiles hang over the edge (zeros in, no stores out)
-    const int n_tiles = (p.N + BN3 - 1) / BN3;
-    int bid, tile_n;
-    xcd_tile_order(p.flags, (int)(gridDim.x / n_tiles), n_tiles, bid, tile_n);  // bid = pixel-tile index
-    const int tx = bid % tiles_x; bid /= tiles_x;
-    const int ty = bid % tiles_y;
-    const int b = bid / tiles_y;
-    const int y0 = ty * T3H, x0 = tx * T3W, n0 = tile_n * BN3;
-
-    const int nchunks = p.Cin / CK3;
+    const HaloTile tl = halo_tile<T3H, T3W, BN3>(p, H, W);
+    const int b = tl.b, y0 = tl.ty * T3H, x0 = tl.tx * T3W, n0 = tl.tile_n * BN3;
     const int split = blockIdx.y;
-    const int per = (nchunks + p.split_k - 1) / p.split_k;
-    const int c_begin = split * per;
-    const int c_end = min(nchunks, c_begin + per);
+    const KSlice ks = k_slice<CK3>(p, split);
+    const int c_begin = ks.c_begin, c_end = ks.c_end;
     const int total = (c_end - c_begin) * 9;
 
     const int wv = __builtin_amdgcn_readfirstlane(wave);
@@ -92,10 +80,8 @@ __global__ __launch_bounds__(NW * 64, 2) void conv3x3_patch3_kernel(const ConvGe
         acur[i] = FAR;
         if (pp < NPIX3) {
             const int iy = y0 - 1 + pp / P3W, ix = x0 - 1 + pp % P3W;      // logical pixel; the zero halo is applied AFTER the upsample
-            if ((unsigned)iy < (unsigned)H && (unsigned)ix < (unsigned)W) {
-                const int sy = p.ups ? (iy >> 1) : iy, sx = p.ups ? (ix >> 1) : ix;
-                acur[i] = (uint32_t)(((b * p.Hin + sy) * p.Win + sx) * p.x_pix_stride + piece * 8 + c_begin * CK3) * 2u;
-            }
+            if ((unsigned)iy < (unsigned)H && (unsigned)ix < (unsigned)W)
+                acur[i] = (uint32_t)(halo_src_pixel(p, b, iy, ix) * p.x_pix_stride + piece * 8 + c_begin * CK3) * 2u;
         }
         adst[i] = smem_base + (uint32_t)((wv * 3 + i) * 1024);
     }
@@ -111,19 +97,11 @@ __global__ __launch_bounds__(NW * 64, 2) void conv3x3_patch3_kernel(const ConvGe
     const uint32_t w_tap = (uint32_t)(p.Cin * 2), w_chunk = (uint32_t)(CK3 * 2) - 8u * w_tap;      // next tap / tap 8 -> tap 0 of the next chunk
     auto dma_patch = [&](auto buf_c) __attribute__((always_inline)) {
 #pragma unroll
-        for (int i = 0; i < 3; ++i) {
-            asm volatile("s_add_u32 m0, %1, %3\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %2, 0 offen lds"
-                         : : "v"(acur[i]), "s"(adst[i]), "s"(dx), "n"(decltype(buf_c)::value * AB3) : "memory", "scc");
-            acur[i] += (uint32_t)(CK3 * 2);
-        }
+        for (int i = 0; i < 3; ++i) dma16_run<decltype(buf_c)::value * AB3>(dx, adst[i], acur[i], (uint32_t)(CK3 * 2));
     };
     auto dma_w = [&](auto ring_c) __attribute__((always_inline)) {
 #pragma unroll
-        for (int i = 0; i < WPW; ++i) {
-            asm volatile("s_add_u32 m0, %1, %3\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %2, 0 offen lds"
-                         : : "v"(wcur[i]), "s"(wdst[i]), "s"(dw), "n"(decltype(ring_c)::value * WB3) : "memory", "scc");
-            wcur[i] += w_tap;
-        }
+        for (int i = 0; i < WPW; ++i) dma16_run<decltype(ring_c)::value * WB3>(dw, wdst[i], wcur[i], w_tap);
     };
 
     f32x16 acc[5];
@@ -232,11 +210,7 @@ __global__ __launch_bounds__(NW * 64, 2) void conv3x3_patch3_kernel(const ConvGe
         if ((wave >> 1) == wr) {
             const int row_l = (wave & 1) * 32 + cpix;
 #pragma unroll
-            for (int a = 0; a < 5; ++a)
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-                    *reinterpret_cast<float4*>(Cs + row_l * CLD3 + a * 32 + 8 * j + 4 * hi) =
-                        make_float4(acc[a][4 * j], acc[a][4 * j + 1], acc[a][4 * j + 2], acc[a][4 * j + 3]);
+            for (int a = 0; a < 5; ++a) acc_to_lds<CLD3>(Cs, row_l, a * 32, hi, acc[a]);
         }
         __syncthreads();
         if (mine) {
@@ -259,7 +233,7 @@ __global__ __launch_bounds__(NW * 64, 2) void conv3x3_patch3_kernel(const ConvGe
 #pragma unroll
                         for (int e = 0; e < 8; ++e) {
                             if (e < nv) {
-                                const float r = E::tof(E::fromf(v[e]));           // statistics of the STORED tensor
+                                const float r = E::tof(E::fromf(v[e]));           // statistics of the STORED tensor (gemm_common.h)
                                 if (e < st_split) { st[0] += r; st[1] += r * r; } else { st[2] += r; st[3] += r * r; }
                             }
                         }
@@ -269,39 +243,14 @@ __global__ __launch_bounds__(NW * 64, 2) void conv3x3_patch3_kernel(const ConvGe
         }
         if (wr + 1 < NW / 2) __syncthreads();
     }
-    if (want_stats) {
-        __syncthreads();                        // the fp32 tile in LDS is dead: reuse its head for the NT x 4 partials
-        float* red = reinterpret_cast<float*>(smem);
-        *reinterpret_cast<float4*>(red + tid * 4) = make_float4(st[0], st[1], st[2], st[3]);
-        __syncthreads();
-        const int G = p.gn_stats_groups;
-        if (tid < G) {                          // fixed summation order: column chunk, then row lane (deterministic)
-            const int g = tid;
-            float S = 0.f, Q = 0.f;
-            for (int j = 0; j < CPR; ++j) {
-                const int nj = n0 + 8 * j;
-                if (nj >= p.N) break;
-                const int gj = nj / cpg;
-                if (gj == g || gj + 1 == g) {
-                    const int o = (gj == g) ? 0 : 2;
-                    for (int rl = 0; rl < RL; ++rl) { S += red[(j + CPR * rl) * 4 + o]; Q += red[(j + CPR * rl) * 4 + o + 1]; }
-                }
-            }
-            const int nparts = tiles_y * tiles_x * n_tiles;
-            const int part = (ty * tiles_x + tx) * n_tiles + tile_n;
-            float* dst = p.gn_stats_out + (((size_t)b * nparts + part) * G + g) * 2;
-            dst[0] = S; dst[1] = Q;
-        }
-    }
+    if (want_stats)
+        gn_stats_fold_store<CPR, RL>(p, smem, tid, make_float4(st[0], st[1], st[2], st[3]), n0, cpg, b, tl.tiles_y * tl.tiles_x * tl.n_tiles, (tl.ty * tl.tiles_x + tl.tx) * tl.n_tiles + tl.tile_n);
 }
 
 }  // namespace
 
 static bool patch3_geometry(const ConvGemmParams& p, int th) {
-    const bool geom = p.ups ? (p.Hout == 2 * p.Hin && p.Wout == 2 * p.Win) : (p.Hin == p.Hout && p.Win == p.Wout);
-    return p.taps == 9 && p.stride == 1 && !p.pad_br_only && geom && p.Hout >= th && p.Wout >= T3W && (p.Cin % CK3) == 0 &&
-           p.mode == OUT_ROWMAJOR && p.act != ACT_GEGLU && p.gn_a == nullptr && (p.x_pix_stride % 8) == 0 &&
-           p.x_bytes < 0x80000000u && p.w_bytes < 0x80000000u;
+    return halo_geometry(p, th, T3W, CK3) && p.gn_a == nullptr && (p.x_pix_stride % 8) == 0 && p.x_bytes < 0x80000000u && p.w_bytes < 0x80000000u;
 }
 bool imd_conv_patch3_supported(const ConvGemmParams& p) { return patch3_geometry(p, T3<4>::TH); }       // tile config 22
 bool imd_conv_patch4_supported(const ConvGemmParams& p) { return patch3_geometry(p, T3<8>::TH); }       // tile config 23 (16 x 16 pixel tiles)
@@ -313,22 +262,14 @@ static int launch_patch3(const ConvGemmParams& p_in, hipStream_t s, const char* 
     if (!patch3_geometry(p, T3<NW>::TH))
         return imd_set_error("%s: unsupported geometry (needs 3x3 stride 1, H >= %d, W >= 16, Cin %% 32 == 0, row-major output, operands < 2 GiB)", what, T3<NW>::TH);
     const bool h = p.dtype == IMD_DTYPE_F16;
-    typedef void (*kern_t)(const ConvGemmParams);
-    const kern_t kern = h ? conv3x3_patch3_kernel<true, NW> : conv3x3_patch3_kernel<false, NW>;
-    if (int rc_attr = imd_lds_attr(reinterpret_cast<const void*>(kern), T3<NW>::LDS, what)) return rc_attr;
-    const int B = p.M / (p.Hout * p.Wout);
-    const long blocks = (long)B * ((p.Hout + T3<NW>::TH - 1) / T3<NW>::TH) * ((p.Wout + T3W - 1) / T3W) * ((p.N + BN3 - 1) / BN3);
-    hipLaunchKernelGGL(kern, dim3((unsigned)blocks, (unsigned)p.split_k), dim3(NW * 64), T3<NW>::LDS, s, p);
-    return imd_check_launch(what);
+    return halo_launch(h ? conv3x3_patch3_kernel<true, NW> : conv3x3_patch3_kernel<false, NW>, p, halo_blocks(p, T3<NW>::TH, T3W, BN3), p.split_k, NW * 64, T3<NW>::LDS, what, s);
 }
 
 // statistic partials per image written through gn_stats_out by the un-split launch of tile config 22 (nw = 4) / 23 (nw = 8); 0: cannot
 int imd_conv_patch3_stats_parts_of(const ConvGemmParams& p, int nw) {
     const int th = nw == 8 ? T3<8>::TH : T3<4>::TH;
-    if (!patch3_geometry(p, th) || p.split_k > 1 || p.out_f32 || p.gn_stats_groups <= 0 || p.gn_stats_groups > 64 || p.N % p.gn_stats_groups ||
-        (p.N / p.gn_stats_groups) < 8 || (p.N % 8))
-        return 0;
-    return ((p.Hout + th - 1) / th) * ((p.Wout + T3W - 1) / T3W) * ((p.N + BN3 - 1) / BN3);
+    if (!patch3_geometry(p, th) || !halo_stats_ok(p) || (p.N % 8)) return 0;
+    return halo_tiles(p.Hout, p.Wout, p.N, th, T3W, BN3);
 }
 
 int imd_launch_conv_patch3(const ConvGemmParams& p, hipStream_t s) { return launch_patch3<4>(p, s, "conv_patch3"); }

@@ -289,6 +289,45 @@ __device__ __forceinline__ void epilogue8(const ConvGemmParams& p, float* v, int
 }
 
 // ------------------------------------------------------------------------------------------
+// GroupNorm statistics of the output tile from the epilogue (gn_stats_out): conv_gemm.hip, conv_patch.hip, conv_patch3.hip.
+// A thread emits the same 8-channel column chunk for every row it owns (thread count % CPR == 0, or the surplus threads idle), so
+// it accumulates st[4] = (sum, sum of squares) of its final values for the at most two groups those 8 channels belong to (a group
+// has >= 8 channels: the launchers check): channels [0, st_split) of the chunk, st_split = min(8, (n / cpg + 1) * cpg - n), go to
+// the chunk's first group (st[0], st[1]), the rest to the next one (st[2], st[3]).  The statistics are those of the STORED tensor --
+// each value after rounding to 16 bits, E::tof(E::fromf(v)): what the standalone gn_stats_kernel and the reference's GroupNorm see --
+// so they do not depend on which kernel produced the tensor.  (The accumulation loop stays inline in all three kernels: as a helper,
+// in any of three shapes, it changed their register allocation.)
+//
+// The fold: every thread parks its four sums in LDS (the fp32 output tile there is dead: its head takes the threads x 4 partials; both
+// barriers are in here), then thread g < groups sums group g's partials in a FIXED order -- column chunk j, then row lane rl (thread
+// j + CPR * rl) -- so the result is deterministic, and stores (S, Q) as partial `part` of the `nparts` the launch writes per image.
+// CPR = column chunks per tile row, RL = row lanes.  (The sums by value: with `const float (&)[4]` conv_patch.hip compiled differently.)
+// ------------------------------------------------------------------------------------------
+template <int CPR, int RL>
+__device__ __forceinline__ void gn_stats_fold_store(const ConvGemmParams& p, char* smem, int tid, float4 st, int n0, int cpg, int b, int nparts, int part) {
+    __syncthreads();
+    float* red = reinterpret_cast<float*>(smem);
+    *reinterpret_cast<float4*>(red + tid * 4) = st;
+    __syncthreads();
+    const int G = p.gn_stats_groups;
+    if (tid < G) {
+        const int g = tid;
+        float S = 0.f, Q = 0.f;
+        for (int j = 0; j < CPR; ++j) {
+            const int nj = n0 + 8 * j;
+            if (nj >= p.N) break;
+            const int gj = nj / cpg;
+            if (gj == g || gj + 1 == g) {
+                const int o = (gj == g) ? 0 : 2;
+                for (int rl = 0; rl < RL; ++rl) { S += red[(j + CPR * rl) * 4 + o]; Q += red[(j + CPR * rl) * 4 + o + 1]; }
+            }
+        }
+        float* dst = p.gn_stats_out + (((size_t)b * nparts + part) * G + g) * 2;
+        dst[0] = S; dst[1] = Q;
+    }
+}
+
+// ------------------------------------------------------------------------------------------
 // split-K without a second launch.  Every workgroup of a K slice writes its fp32 partial tile to its slab; the LAST workgroup
 // to arrive at the tile's counter sums the slabs of the tile in slice order 0 .. S-1 -- the order the finish kernel uses, so
 // the result is bit-identical whoever arrives last -- and runs the epilogue.

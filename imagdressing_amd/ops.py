@@ -752,7 +752,7 @@ def conv2d_nhwc(x: torch.Tensor, w: torch.Tensor, bias=None, *, taps=9, stride=1
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# Upsample2D (nearest-2x interpolate -> 3x3 conv) as four 2x2 phase convolutions (csrc/conv_patch.hip::conv_ups_phase_kernel;
+# Upsample2D (nearest-2x interpolate -> 3x3 conv) as four 2x2 phase convolutions (csrc/conv_ups_phase.hip::conv_ups_phase_kernel;
 # include/imagdressing_hip.h::imd_conv_ups_phase): after the upsample the four pixels of a 2x2 output block see the same 2x2 source
 # pixels, so the 3x3 taps that fall on one source pixel are summed once per layer and four taps run instead of nine.  A/B switch,
 # default on; IMD_UPS_PHASE=0 restores conv2d_nhwc(ups=True), whose dispatch is untouched.

@@ -528,7 +528,7 @@ int imd_ff_geglu(const imd_ff_params* p, void* stream);
 int imd_text_xattn320(const imd_xattn_params* p, void* stream);
 int imd_text_xattn320_supported(const imd_xattn_params* p);
 
-/* Upsample2D (nearest-2x interpolate -> 3x3 conv) as four 2x2 PHASE convolutions (conv_patch.hip): out[2y + py, 2x + px] = bias +
+/* Upsample2D (nearest-2x interpolate -> 3x3 conv) as four 2x2 PHASE convolutions (conv_ups_phase.hip): out[2y + py, 2x + px] = bias +
  * sum over dy, dx in {0, 1} of W'[py, px][dy, dx] . src[y + py - 1 + dy, x + px - 1 + dx] (out-of-image src = 0) -- 4 taps instead of 9.
  * *p describes the 9-tap problem exactly as imd_conv_gemm takes it (taps = 9, K = 9 Cin, stride = 1, ups = 1, Hout = 2 Hin, Wout = 2 Win),
  * except that p->w holds the PHASE weights [4 phases py * 2 + px][N][4 taps dy * 2 + dx][Cin] in the activation type, the 3x3 taps that

@@ -1,4 +1,4 @@
-"""Nearest-2x upsample + 3x3 conv as four 2x2 phase convolutions (csrc/conv_patch.hip::conv_ups_phase_kernel, ops.conv_ups_phase) against
+"""Nearest-2x upsample + 3x3 conv as four 2x2 phase convolutions (csrc/conv_ups_phase.hip::conv_ups_phase_kernel, ops.conv_ups_phase) against
 F.conv2d(F.interpolate(x, 2, 'nearest'), w, b, padding=1) and against the 9-tap path it replaces (ops.conv2d_nhwc(ups=True), what
 IMD_UPS_PHASE=0 runs).
 

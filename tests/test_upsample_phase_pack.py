@@ -1,5 +1,5 @@
 """ops.pack_upsample_phase: nearest-2x upsample + 3x3 conv == four 2x2 phase convolutions on the SOURCE map with pre-summed weights
-(csrc/conv_patch.hip::conv_ups_phase_kernel).  For output phase (py, px)
+(csrc/conv_ups_phase.hip::conv_ups_phase_kernel).  For output phase (py, px)
 
     out[2y + py, 2x + px] = bias + sum_{dy, dx in {0, 1}} W'[py, px][dy, dx] . src[y + py - 1 + dy, x + px - 1 + dx]        (out-of-image src = 0)
 
