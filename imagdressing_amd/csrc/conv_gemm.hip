@@ -23,12 +23,15 @@
 //   slice writes its fp32 partial tile to a slab; a second tiny kernel sums the slabs in a fixed
 //   order (deterministic) and runs the same epilogue.
 //
+// The blocks this kernel shares with its descendants (gemm_dma*.hip, the halo-patch family) live in tile_common.h; only two are CALLED
+// here -- this kernel's register allocation follows every helper, the rest stays written out.
+//
 // Reference arithmetic this replaces (diffusers==0.24.0, un-vendored; call sites
 // /root/reference/dressing_sd/pipelines/IMAGDressing_v1_pipeline.py:466,499,511):
 // ResnetBlock2D conv1/conv2/conv_shortcut, Down/Upsample2D conv, Transformer2DModel proj_in/
 // proj_out, Attention to_q/to_k/to_v/to_out, GEGLU FeedForward, TimestepEmbedding, and the
 // to_k_ref/to_v_ref garment projections of adapter/attention_processor.py:600-601.
-#include "gemm_common.h"
+#include "tile_common.h"
 
 namespace {
 
@@ -73,9 +76,8 @@ __global__ __launch_bounds__(WAVES_M * WAVES_N * 64, (WAVES_M * WAVES_N == 4) ? 
     // K range of this split (whole BK tiles)
     const int nk_total = (p.K + BK - 1) / BK;
     const int split = blockIdx.y;
-    const int per = (nk_total + p.split_k - 1) / p.split_k;
-    const int kt_begin = split * per;
-    const int kt_end = min(nk_total, kt_begin + per);
+    const int per = k_tiles_per_slice(nk_total, p.split_k);
+    const int kt_begin = split * per, kt_end = min(nk_total, kt_begin + per);
 
     // staging map.  BK = 32 (80-byte LDS rows, 4 vectors per row): 16 consecutive lanes that write rows R .. R+3 put three of
     // their sixteen 16-byte pieces on an occupied bank slot (PMC: 30 % of the LDS cycles of the halo-patch kernel were bank
@@ -186,11 +188,10 @@ __global__ __launch_bounds__(WAVES_M * WAVES_N * 64, (WAVES_M * WAVES_N == 4) ? 
     for (int a = 0; a < TN; ++a)
 #pragma unroll
         for (int b = 0; b < TM; ++b)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.f;
+            zero_frag(acc[a][b]);
 
     const int frag_off = (lane & 31) * STRIDE + (lane >> 5) * 16;
-    auto mma = [&](int buf, int kk) {           // one 16-deep k step of the LDS tile `buf`
+    auto mma = [&](int buf, int kk) {           // one 16-deep k step of the LDS tile `buf` (tile_common.h::mfma_step16 written out: in any of three shapes it moved registers)
         const char* As = smem + buf * BUF;
         const char* Ws = As + BM * STRIDE;
         uint4 wf[TN], xf[TM];
@@ -273,7 +274,7 @@ __global__ __launch_bounds__(WAVES_M * WAVES_N * 64, (WAVES_M * WAVES_N == 4) ? 
 #pragma unroll
                 for (int a = 0; a < TN; ++a)
 #pragma unroll
-                    for (int j = 0; j < 4; ++j) {
+                    for (int j = 0; j < 4; ++j) {          // (tile_common.h::acc_to_lds, and lds_read8 below, written out: up to 190 lines of a kernel's assembly moved)
                         float* dst = Cs + (b * 32 + col) * T::CLD + wn0 + a * 32 + 8 * j + 4 * hi;
                         *reinterpret_cast<float4*>(dst) = make_float4(acc[a][b][4 * j], acc[a][b][4 * j + 1], acc[a][b][4 * j + 2], acc[a][b][4 * j + 3]);
                     }
@@ -349,7 +350,9 @@ __global__ __launch_bounds__(WAVES_M * WAVES_N * 64, (WAVES_M * WAVES_N == 4) ? 
     }
 }
 
-// sum the split-K slabs in a fixed order and run the epilogue (row-major outputs only)
+// sum the split-K slabs in a fixed order and run the epilogue (row-major outputs only).  The slice sum, here and in the statistics form
+// below, uses ORDINARY loads (the kernel boundary has made the slabs visible) in the order of the coherent gemm_common.h::splitk_sum8:
+// same bits.  (Both stay written out: as one helper beside splitk_sum8, in any of four shapes, the finish kernels compiled differently.)
 template <bool F16>
 __global__ __launch_bounds__(256) void splitk_finish_kernel(const ConvGemmParams p) {
     const int HWo = p.Hout * p.Wout;
@@ -554,35 +557,28 @@ int launch_splitk_finish(const ConvGemmParams& p, hipStream_t s, const char* wha
             return imd_set_error("%s: gn_out_* on a problem whose finish launch cannot normalise (ask imd_conv_gemm_gn_out_supported(): K slices with a separate "
                                  "finish, row-major 16-bit output, no residual / activation / scale, 4 | N / groups, H W N / groups <= %d)", what, 4 * FG_THREADS * FG_MAXU);
         const int B = p.M / (p.Hout * p.Wout);
-        if (h) hipLaunchKernelGGL(splitk_finish_gn_kernel<true>, dim3((unsigned)p.gn_out_groups, (unsigned)B), dim3(FG_THREADS), 0, s, p);
-        else hipLaunchKernelGGL(splitk_finish_gn_kernel<false>, dim3((unsigned)p.gn_out_groups, (unsigned)B), dim3(FG_THREADS), 0, s, p);
-        return imd_check_launch(what);
+        return tile_launch(h ? splitk_finish_gn_kernel<true> : splitk_finish_gn_kernel<false>, p, dim3((unsigned)p.gn_out_groups, (unsigned)B), FG_THREADS, 0, what, s);
     }
     if (p.gn_stats_out != nullptr) {
         const int nparts = splitk_stats_parts_of(p);
         if (nparts == 0) return imd_set_error("%s: gn_stats_out on a K-sliced problem that cannot produce the statistics", what);
         const int HW = p.Hout * p.Wout, B = p.M / HW, rpp = fs_rows_per_part(B, HW, p.N);
-        if (h) hipLaunchKernelGGL(splitk_finish_stats_kernel<true>, dim3((unsigned)nparts, (unsigned)B), dim3(FS_THREADS), 0, s, p, rpp, nparts);
-        else hipLaunchKernelGGL(splitk_finish_stats_kernel<false>, dim3((unsigned)nparts, (unsigned)B), dim3(FS_THREADS), 0, s, p, rpp, nparts);
+        // (two more kernel arguments than tile_launch passes; no dynamic LDS)
+        hipLaunchKernelGGL(h ? splitk_finish_stats_kernel<true> : splitk_finish_stats_kernel<false>, dim3((unsigned)nparts, (unsigned)B), dim3(FS_THREADS), 0, s, p, rpp, nparts);
         return imd_check_launch(what);
     }
     const long chunks = (long)p.M * ((p.N + 7) / 8);
     long blocks = (chunks + 255) / 256;
     if (blocks > 2048) blocks = 2048;
-    if (h) hipLaunchKernelGGL(splitk_finish_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, s, p);
-    else hipLaunchKernelGGL(splitk_finish_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, s, p);
-    return imd_check_launch(what);
+    return tile_launch(h ? splitk_finish_kernel<true> : splitk_finish_kernel<false>, p, dim3((unsigned)blocks), 256, 0, what, s);
 }
 
 template <bool F16, int BM, int BN, int BK, int WM, int WN, int DEPTH = 2>
 int launch_cfg(const ConvGemmParams& p, hipStream_t s) {
     static_assert(DEPTH == 2 || DEPTH == 4, "pipeline depth");
     constexpr int lds = TileCfg<BM, BN, BK, WM>::LDS;
-    auto kern = conv_gemm_kernel<F16, BM, BN, BK, WM, WN, DEPTH>;
-    if (int rc_attr = imd_lds_attr(reinterpret_cast<const void*>(kern), lds, "conv_gemm")) return rc_attr;
     const long mt = (p.M + BM - 1) / BM, nt = (p.N + BN - 1) / BN;
-    hipLaunchKernelGGL(kern, dim3((unsigned)(mt * nt), (unsigned)p.split_k), dim3(WM * WN * 64), lds, s, p);
-    return imd_check_launch("conv_gemm");
+    return tile_launch(conv_gemm_kernel<F16, BM, BN, BK, WM, WN, DEPTH>, p, dim3((unsigned)(mt * nt), (unsigned)p.split_k), WM * WN * 64, lds, "conv_gemm", s);
 }
 
 // the register-staged tile kernel (this file) in both element types
@@ -657,12 +653,12 @@ const TileConfig* tile_config(int cfg) {
     return cfg >= 0 && cfg < (int)(sizeof(TILE_CONFIGS) / sizeof(TILE_CONFIGS[0])) ? &TILE_CONFIGS[cfg] : nullptr;
 }
 
-// tile of `cfg` into (bm, bn); 1, (bm, bn) untouched, where the config has no grid of tiles
-int tile_dims(int cfg, int* bm, int* bn) {
+// tile of `cfg`, for the sizing heuristics: 128 x 128 where the config has no grid of tiles (or does not exist)
+struct TileDims { int bm, bn; };
+TileDims tile_dims(int cfg) {
     const TileConfig* t = tile_config(cfg);
-    if (t == nullptr || t->bm == 0) return 1;
-    *bm = t->bm, *bn = t->bn;
-    return 0;
+    if (t == nullptr || t->bm == 0) return TileDims{128, 128};
+    return TileDims{t->bm, t->bn};
 }
 
 }  // namespace
@@ -737,9 +733,8 @@ int imd_conv_gemm_choose_cfg(int M, int N) {
 
 // number of K slices: only for row-major epilogues on problems whose tile grid cannot fill the chip
 int imd_conv_gemm_choose_split(int M, int N, int K, int cfg) {
-    int bm = 128, bn = 128;
-    tile_dims(cfg, &bm, &bn);
-    const long blocks = (long)((M + bm - 1) / bm) * ((N + bn - 1) / bn);
+    const TileDims td = tile_dims(cfg);
+    const long blocks = (long)((M + td.bm - 1) / td.bm) * ((N + td.bn - 1) / td.bn);
     const int ktiles = (K + 63) / 64;
     if (blocks >= 200 || ktiles < 32) return 1;
     long s = (448 + blocks - 1) / blocks;           // aim at ~1.75 blocks per CU
@@ -780,15 +775,14 @@ int imd_launch_conv_gemm(const ConvGemmParams& p_in, int cfg, hipStream_t s) {
         return imd_set_error("conv_gemm: flags = 0x%x on entry is neither 0 nor IMD_TUNING_PER_CALL | bits (an uninitialised parameter block?)", (unsigned)p_in.flags);
     const int gf = (tag == (unsigned)IMD_TUNING_PER_CALL) ? ((p_in.flags & 31) | (g_gemm_flags & ~31)) : g_gemm_flags;
     const TileConfig* t = tile_config(cfg);         // (nullptr: refused below, behind the checks of the problem itself)
+    const TileDims td = tile_dims(cfg);
     p.flags = 0;
     // measured (profiles/r1g_gemm_flags_ab.jsonl): +8..17 % on the 64x64 / 32x32 feature maps, -2..4 % on 16x16 / 8x8
     const bool big_map = p.taps == 9 && p.Wout >= 32;
     if ((gf & 1) && big_map && (p.Cin % (t != nullptr ? t->order_bk : 64)) == 0) p.flags |= 1;
     if ((gf & 2) && big_map) p.flags |= 2;
     if (gf & 4) {
-        int bm = 128, bn = 128;
-        tile_dims(cfg, &bm, &bn);
-        p.flags |= imd_gemm_pick_order(p, (p.N + bn - 1) / bn);
+        p.flags |= imd_gemm_pick_order(p, (p.N + td.bn - 1) / td.bn);
         p.flags |= gf & 16;
     }
 #ifdef IMD_ABLATIONS
@@ -812,10 +806,8 @@ int imd_launch_conv_gemm(const ConvGemmParams& p_in, int cfg, hipStream_t s) {
                              4 * FG_THREADS * FG_MAXU, cfg, p.split_k, p.gn_out_groups, p.N);
     if (p.gn_out_gamma != nullptr) p.splitk_counters = nullptr;
     if (p.splitk_counters != nullptr) {          // one counter per output tile; larger grids keep the two-launch path
-        int bm = 128, bn = 128;
-        tile_dims(cfg, &bm, &bn);
         const long tiles = (t != nullptr && t->stats == ST_PATCH) ? (long)(p.M / (p.Hout * p.Wout)) * ((p.Hout + 7) / 8) * ((p.Wout + 15) / 16) * ((p.N + 127) / 128)   // (8 x 16 pixel patches)
-                                                                  : (long)((p.M + bm - 1) / bm) * ((p.N + bn - 1) / bn);
+                                                                  : (long)((p.M + td.bm - 1) / td.bm) * ((p.N + td.bn - 1) / td.bn);
         if (tiles > IMD_SPLITK_COUNTERS || (size_t)p.M * p.N * 4 >= 0x80000000ull) p.splitk_counters = nullptr;
     }
     if (p.split_k > 1) {

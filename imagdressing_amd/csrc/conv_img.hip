@@ -29,8 +29,7 @@
 // (IMAGDressing_v1_pipeline.py:466,499,511 call the UNets).
 #include <type_traits>
 
-#include "gemm_common.h"
-#include "lds_dma.h"
+#include "tile_common.h"
 
 namespace {
 
@@ -154,8 +153,7 @@ __global__ __launch_bounds__(IMG * 64, 1) void conv3x3_img_kernel(const ConvGemm
     for (int pb = 0; pb < NPB; ++pb)
 #pragma unroll
         for (int nb = 0; nb < 2; ++nb)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[pb][nb][r] = 0.f;
+            zero_frag(acc[pb][nb]);
 
     // unit (chunk on patch buffer buf_c, tap row dy_c) = ring slot 3 buf_c + dy_c: the weights of unit + 5 staged behind it and, at dy = 0,
     // the next chunk's patches (HBM latency is ~2 us under load and a unit multiplies for ~0.4 us: with unit + 2 in flight -- the first

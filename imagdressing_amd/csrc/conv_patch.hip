@@ -149,8 +149,7 @@ __global__ __launch_bounds__(256, CKD == 32 ? 3 : 2) void conv3x3_patch_kernel(c
     for (int a = 0; a < 2; ++a)
 #pragma unroll
         for (int bb = 0; bb < 2; ++bb)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[a][bb][r] = 0.f;
+            zero_frag(acc[a][bb]);
 
     // A-fragment base rows: output pixel q = wm0 + bb*32 + col -> patch row (q/16)*18 + q%16 (+ tap offset)
     int a_frag[2];
@@ -456,7 +455,7 @@ bool imd_conv_patch64_supported(const ConvGemmParams& p) {
 int imd_launch_conv_patch64(const ConvGemmParams& p, hipStream_t s) {
     if (!imd_conv_patch64_supported(p)) return imd_set_error("conv_patch (128-byte rows): unsupported problem (needs 3x3 stride 1, H >= 8, W >= 16, Cin %% 64 == 0, operands < 2 GiB, no fused GroupNorm)");
     const bool h = p.dtype == IMD_DTYPE_F16;
-    return halo_launch(h ? conv3x3_patch_kernel<true, true, 64> : conv3x3_patch_kernel<false, true, 64>, p, halo_blocks(p, TH, TW, BN), p.split_k, 256, PD<64>::LDS,
+    return tile_launch(h ? conv3x3_patch_kernel<true, true, 64> : conv3x3_patch_kernel<false, true, 64>, p, dim3((unsigned)halo_blocks(p, TH, TW, BN), (unsigned)p.split_k), 256, PD<64>::LDS,
                        "conv_patch (128-byte rows)", s);
 }
 
@@ -467,7 +466,7 @@ int imd_launch_conv_patch(const ConvGemmParams& p, hipStream_t s) {
     // bit 9 selects the round-1/2 register-staged form (A/B)
     const bool dma = p.gn_a == nullptr && !(g_gemm_flags & 512) && (p.ups || (p.x_bytes < 0x80000000u && p.w_bytes < 0x80000000u));   // (the DMA loop marks out-of-range pieces with offset 2^31)
     if (p.ups && (p.x_bytes >= 0x80000000u || p.w_bytes >= 0x80000000u)) return imd_set_error("conv_patch: fused upsample needs operands < 2 GiB");
-    const halo_kern_t kern = dma ? (h ? conv3x3_patch_kernel<true, true> : conv3x3_patch_kernel<false, true>)
+    const tile_kern_t kern = dma ? (h ? conv3x3_patch_kernel<true, true> : conv3x3_patch_kernel<false, true>)
                                  : (h ? conv3x3_patch_kernel<true, false> : conv3x3_patch_kernel<false, false>);
-    return halo_launch(kern, p, halo_blocks(p, TH, TW, BN), p.split_k, 256, dma ? PD<32>::LDS : PATCH_LDS, "conv_patch", s);
+    return tile_launch(kern, p, dim3((unsigned)halo_blocks(p, TH, TW, BN), (unsigned)p.split_k), 256, dma ? PD<32>::LDS : PATCH_LDS, "conv_patch", s);
 }

@@ -58,8 +58,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_patch2_kernel(const ConvGemmPa
     for (int a = 0; a < 2; ++a)
 #pragma unroll
         for (int bb = 0; bb < 4; ++bb)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[a][bb][r] = 0.f;
+            zero_frag(acc[a][bb]);
     const bool wave_live = n0 + wn0 < p.N;     // (the last channel tile of N = 320 is half empty)
 
     const int wv = __builtin_amdgcn_readfirstlane(wave);
@@ -205,5 +204,5 @@ int imd_launch_conv_patch2(const ConvGemmParams& p_in, hipStream_t s) {
     ConvGemmParams p = p_in;
     p.gn_stats_out = nullptr;
     const bool h = p.dtype == IMD_DTYPE_F16;
-    return halo_launch(h ? conv3x3_patch2_kernel<true> : conv3x3_patch2_kernel<false>, p, halo_blocks(p, T2H, T2W, BN2), p.split_k, 256, PATCH2_LDS, "conv_patch2", s);
+    return tile_launch(h ? conv3x3_patch2_kernel<true> : conv3x3_patch2_kernel<false>, p, dim3((unsigned)halo_blocks(p, T2H, T2W, BN2), (unsigned)p.split_k), 256, PATCH2_LDS, "conv_patch2", s);
 }

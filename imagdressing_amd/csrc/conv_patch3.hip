@@ -107,8 +107,7 @@ __global__ __launch_bounds__(NW * 64, 2) void conv3x3_patch3_kernel(const ConvGe
     f32x16 acc[5];
 #pragma unroll
     for (int a = 0; a < 5; ++a)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[a][r] = 0.f;
+        zero_frag(acc[a]);
 
     // fragment addresses (bytes inside a ring slot / a patch buffer), loop-invariant; the 16-deep slice kk = 1 is the same address ^ 32.
     // Weight row a * 32 + col has the swizzle term of row col (a * 32 / 4 is a multiple of 4), so block a is a compile-time offset.
@@ -262,7 +261,7 @@ static int launch_patch3(const ConvGemmParams& p_in, hipStream_t s, const char* 
     if (!patch3_geometry(p, T3<NW>::TH))
         return imd_set_error("%s: unsupported geometry (needs 3x3 stride 1, H >= %d, W >= 16, Cin %% 32 == 0, row-major output, operands < 2 GiB)", what, T3<NW>::TH);
     const bool h = p.dtype == IMD_DTYPE_F16;
-    return halo_launch(h ? conv3x3_patch3_kernel<true, NW> : conv3x3_patch3_kernel<false, NW>, p, halo_blocks(p, T3<NW>::TH, T3W, BN3), p.split_k, NW * 64, T3<NW>::LDS, what, s);
+    return tile_launch(h ? conv3x3_patch3_kernel<true, NW> : conv3x3_patch3_kernel<false, NW>, p, dim3((unsigned)halo_blocks(p, T3<NW>::TH, T3W, BN3), (unsigned)p.split_k), NW * 64, T3<NW>::LDS, what, s);
 }
 
 // statistic partials per image written through gn_stats_out by the un-split launch of tile config 22 (nw = 4) / 23 (nw = 8); 0: cannot

@@ -98,8 +98,7 @@ __global__ __launch_bounds__(256, 3) void conv_ups_phase_kernel(const ConvGemmPa
     for (int a = 0; a < 2; ++a)
 #pragma unroll
         for (int bb = 0; bb < 2; ++bb)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[a][bb][r] = 0.f;
+            zero_frag(acc[a][bb]);
 
     const std::integral_constant<int, 0> i0{}; const std::integral_constant<int, 1> i1{}; const std::integral_constant<int, 2> i2{};
     dma_patch(i0);
@@ -247,5 +246,5 @@ int imd_launch_conv_ups_phase(const ConvGemmParams& p_in, hipStream_t s) {
     const bool h = p.dtype == IMD_DTYPE_F16;
     const long blocks = ups_phase_blocks(p);
     if (blocks > 0x7fffffffL) return imd_set_error("conv_ups_phase: grid too large");
-    return halo_launch(h ? conv_ups_phase_kernel<true> : conv_ups_phase_kernel<false>, p, blocks, 1, 256, PD<32>::LDS, "conv_ups_phase", s);
+    return tile_launch(h ? conv_ups_phase_kernel<true> : conv_ups_phase_kernel<false>, p, dim3((unsigned)blocks, (unsigned)1), 256, PD<32>::LDS, "conv_ups_phase", s);
 }

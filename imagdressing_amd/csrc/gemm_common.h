@@ -1,5 +1,6 @@
-// Pieces shared by the implicit-GEMM kernels (conv_gemm.hip, conv_patch.hip): raw buffer loads with
-// out-of-range => 0 semantics and the fused 8-channel epilogue.
+// Pieces shared by every GEMM-like kernel: the tiled family and conv_img.hip (through tile_common.h), the halo-patch family (patch_common.h)
+// and the row-resident family (row_common.h) -- raw buffer loads with out-of-range => 0 semantics, the XCD-aware tile order, the GroupNorm
+// prologue / statistics pieces, the fused 8-channel epilogue and the coherent K-slice sum.
 #pragma once
 #include "common.h"
 #include "imd_kernels.h"
@@ -35,12 +36,16 @@ constexpr uint32_t OOB = 0xffffffffu;   // any offset past num_records reads as 
 //   flags & 8: channel-tile major -> all row tiles of a channel tile share one L2 (weights fetched once: the 8x8 / 16x16
 //                                   levels, where K = 11520..23040 weight rows dominate)
 // The launcher picks the cheaper of the two from the operand sizes (imd_gemm_pick_order).
-__device__ __forceinline__ void xcd_tile_order(int flags, int m_tiles, int n_tiles, int& tile_m, int& tile_n) {
-    unsigned w = blockIdx.x;
+// Two steps (gemm_dma256.hip, whose list is tiles x K slices, splits the slice off between them): xcd_remap, position w of a list of
+// `total` -> its index in XCD-contiguous order; tile_of, index w of the tile list -> (row tile, channel tile).
+__device__ __forceinline__ unsigned xcd_remap(int flags, unsigned w, unsigned total) {
     if (flags & 12) {
-        const unsigned gx = gridDim.x, k = w & 7u, slot = w >> 3, q8 = gx >> 3, r8 = gx & 7u;
-        w = (k < r8 ? k * (q8 + 1) : r8 * (q8 + 1) + (k - r8) * q8) + slot;       // bijective also when gx % 8 != 0
+        const unsigned k = w & 7u, slot = w >> 3, q8 = total >> 3, r8 = total & 7u;
+        w = (k < r8 ? k * (q8 + 1) : r8 * (q8 + 1) + (k - r8) * q8) + slot;       // bijective also when total % 8 != 0
     }
+    return w;
+}
+__device__ __forceinline__ void tile_of(int flags, unsigned w, int m_tiles, int n_tiles, int& tile_m, int& tile_n) {
     if (flags & 8) { tile_n = (int)(w / (unsigned)m_tiles); tile_m = (int)(w - (unsigned)tile_n * m_tiles); }
     else if ((flags & 4) && (flags & 16)) {
         // grouped order inside the XCD's range: 8 row tiles x all channel tiles, row tile fastest -- the workgroups that
@@ -54,6 +59,9 @@ __device__ __forceinline__ void xcd_tile_order(int flags, int m_tiles, int n_til
         tile_m = (int)(g * GM + (r - (unsigned)tile_n * rows));
     }
     else { tile_m = (int)(w / (unsigned)n_tiles); tile_n = (int)(w - (unsigned)tile_m * n_tiles); }
+}
+__device__ __forceinline__ void xcd_tile_order(int flags, int m_tiles, int n_tiles, int& tile_m, int& tile_n) {      // the grid's x dimension is the tile list
+    tile_of(flags, xcd_remap(flags, blockIdx.x, gridDim.x), m_tiles, n_tiles, tile_m, tile_n);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -368,8 +376,8 @@ __device__ __forceinline__ bool splitk_last_arrival(int* counters, int tile_id, 
     return last;
 }
 
-// sum of the K slices of 8 consecutive channels [n, n+8) of row m, in slice order (what splitk_finish_kernel computes), read
-// from the memory side
+// sum of the K slices of 8 consecutive channels [n, n+8) of row m, in slice order, read from the memory side: the COHERENT form, for the
+// last arrival inside the launch that wrote the slabs (conv_gemm.hip's finish launches sum in the same order with ordinary loads)
 __device__ __forceinline__ void splitk_sum8(const ConvGemmParams& p, int m, int n, int nv, float* v) {
     const size_t slab = (size_t)p.M * p.N;
 #pragma unroll

@@ -9,13 +9,13 @@
 //     feeds 4 MFMAs and every weight fragment 2 (0.75 KB of LDS reads per MFMA instead of 1 KB);
 //   * both operand tiles (256 rows x 64 k x 2 B = 32 KB each) go global -> LDS by DMA (buffer_load ... lds) in whole 128-byte
 //     row pieces, double buffered: tile t + 1 is in flight while tile t is multiplied, ONE barrier per 64-deep step; rows
-//     unpadded, piece p of row r stored at p ^ ((r >> 1) & 7) (source-side swizzle) -> conflict-free ds_read_b128;
+//     unpadded and swizzled on the source side (tile_common.h::lds_row_swz);
 //   * out-of-range rows (M / N tails) are out-of-range DMA offsets and arrive as zeros;
-//   * the epilogue is the tiled kernel's: accumulators -> LDS (fp32, 64 rows at a time) -> 8 consecutive channels per thread
-//     through epilogue8 (bias / residual / activations / GEGLU / head-split layouts), XCD-aware tile order.
+//   * the epilogue goes through LDS 64 rows at a time (fp32; tile_common.h::acc_to_lds / lds_read8), then 8 consecutive channels
+//     per thread through gemm_common.h::epilogue8; XCD-aware tile order (gemm_common.h::xcd_tile_order).
 // Same arithmetic as conv_gemm.hip (fp32 accumulation over K in 16-element MFMA steps, ascending), same reference layers.
-#include "gemm_common.h"
-#include "lds_dma.h"
+// The blocks shared with the other tiled kernels live in tile_common.h, each with its explanation.
+#include "tile_common.h"
 
 namespace {
 
@@ -27,7 +27,6 @@ constexpr int GD_CLD = GD_BN + 4, GD_EROWS = 64;         // fp32 epilogue stagin
 
 template <bool F16>
 __global__ __launch_bounds__(512, 1) void gemm_dma_kernel(const ConvGemmParams p) {
-    using E = El<F16>;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -43,14 +42,14 @@ __global__ __launch_bounds__(512, 1) void gemm_dma_kernel(const ConvGemmParams p
 
     // ---- DMA assignments: a stage is 64 pieces of 1 KB (8 rows x 128 B each): pieces 0..31 activations, 32..63 weights ----
     const v4i_t ds_x = raw_rsrc(p.x, p.x_bytes), ds_w = raw_rsrc(p.w, p.w_bytes);
+    // (slot -> row / piece -> offset stays written out in both kernels: as a helper, in two shapes, every kernel of the file compiled differently)
     uint32_t soff[8];        // source byte offset of this lane's 16 bytes of piece (j * 8 + wave) at k tile 0, or OOB
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
         const int id = j * 8 + wave;
         const bool isw = j >= 4;                              // (id >= 32)
         const int q = (id & 31) * 64 + lane;                 // 16-byte slot inside the operand tile
-        const int row = q >> 3, pos = q & 7;
-        const int pc = pos ^ ((row >> 1) & 7);                // source piece stored at this slot
+        const int row = q >> 3, pc = (q & 7) ^ lds_row_swz<GD_ROWB>(row);      // source piece stored at this slot
         if (isw) soff[j] = (n0 + row < p.N) ? (uint32_t)(((size_t)(n0 + row) * p.K + pc * 8) * 2) : OOB;
         else soff[j] = (m0 + row < p.M) ? (uint32_t)(((size_t)(m0 + row) * p.x_pix_stride + pc * 8) * 2) : OOB;
     }
@@ -69,12 +68,11 @@ __global__ __launch_bounds__(512, 1) void gemm_dma_kernel(const ConvGemmParams p
     for (int a = 0; a < 4; ++a)
 #pragma unroll
         for (int b = 0; b < 2; ++b)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.f;
+            zero_frag(acc[a][b]);
 
     // fragment addresses: row (wm0 + b * 32 + col) of the activation tile, row (wn0 + a * 32 + col) of the weight tile;
     // k16 step kk reads piece 2 kk + hi, stored at (2 kk + hi) ^ ((row >> 1) & 7) = (2 kk) ^ (hi ^ f)
-    const uint32_t f16 = (uint32_t)((hi ^ ((col >> 1) & 7)) << 4);       // (row >> 1) & 7 == (col >> 1) & 7: row offsets are multiples of 32
+    const uint32_t f16 = (uint32_t)((hi ^ lds_row_swz<GD_ROWB>(col)) << 4);       // the swizzle term of row (base + col) is col's: row offsets are multiples of 32
     const char* xlane = smem + (wm0 + col) * GD_ROWB;
     const char* wlane = smem + GD_A + (wn0 + col) * GD_ROWB;
 
@@ -89,20 +87,13 @@ __global__ __launch_bounds__(512, 1) void gemm_dma_kernel(const ConvGemmParams p
 #pragma unroll
         for (int kk = 0; kk < GD_BK / 16; ++kk) {
             const uint32_t po = (uint32_t)(kk * 32) ^ f16;
-            uint4 wf[4], xf[2];
-#pragma unroll
-            for (int b = 0; b < 2; ++b) xf[b] = *reinterpret_cast<const uint4*>(Xs + b * 32 * GD_ROWB + po);
-#pragma unroll
-            for (int a = 0; a < 4; ++a) wf[a] = *reinterpret_cast<const uint4*>(Ws + a * 32 * GD_ROWB + po);
-#pragma unroll
-            for (int a = 0; a < 4; ++a)
-#pragma unroll
-                for (int b = 0; b < 2; ++b) acc[a][b] = E::mfma(wf[a], xf[b], acc[a][b]);
+            mfma_step16<F16, false, 32 * GD_ROWB>(Ws, Xs, po, acc);
         }
     }
     __syncthreads();                   // the last tile has been read by everybody: LDS becomes the epilogue staging area
 
-    // ---- epilogue (conv_gemm.hip's): one 64-row wave group at a time through LDS (fp32), 8 consecutive channels per thread ----
+    // ---- epilogue: one 64-row wave group at a time through LDS (fp32), 8 consecutive channels per thread.  (The column addends and the chunk
+    // decode stay written out, here and in gemm_dma128_kernel: as helpers, in four shapes each, they moved registers in every kernel.) ----
     float* Cs = reinterpret_cast<float*>(smem);
     const int HWo = p.Hout * p.Wout;
     constexpr int CPR = GD_BN / 8;                 // 32 chunks per row
@@ -124,12 +115,7 @@ __global__ __launch_bounds__(512, 1) void gemm_dma_kernel(const ConvGemmParams p
 #pragma unroll
             for (int b = 0; b < 2; ++b)
 #pragma unroll
-                for (int a = 0; a < 4; ++a)
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        float* dst = Cs + (b * 32 + col) * GD_CLD + wn0 + a * 32 + 8 * j + 4 * hi;
-                        *reinterpret_cast<float4*>(dst) = make_float4(acc[a][b][4 * j], acc[a][b][4 * j + 1], acc[a][b][4 * j + 2], acc[a][b][4 * j + 3]);
-                    }
+                for (int a = 0; a < 4; ++a) acc_to_lds<GD_CLD>(Cs, b * 32 + col, wn0 + a * 32, hi, acc[a][b]);
         }
         __syncthreads();
         for (int c = tid; c < CHUNKS; c += 512) {
@@ -138,9 +124,8 @@ __global__ __launch_bounds__(512, 1) void gemm_dma_kernel(const ConvGemmParams p
             else { row = c / CPR; cc = (c - row * CPR) * 8; }
             const int m = m0 + wr * GD_EROWS + row, n = n0 + cc;
             if (m >= p.M || n >= p.N) continue;
-            const float4 v0 = *reinterpret_cast<const float4*>(Cs + row * GD_CLD + cc);
-            const float4 v1 = *reinterpret_cast<const float4*>(Cs + row * GD_CLD + cc + 4);
-            float v[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
+            const TileChunk8 t = lds_read8<GD_CLD>(Cs, row, cc);
+            float v[8] = {t.v0.x, t.v0.y, t.v0.z, t.v0.w, t.v1.x, t.v1.y, t.v1.z, t.v1.w};
             epilogue8<F16>(p, v, m, n, (n + 8 <= p.N) ? 8 : 4, HWo, use_col_pre, col_pre0, col_pre1);
         }
         if (wr + 1 < 4) __syncthreads();
@@ -153,8 +138,8 @@ __global__ __launch_bounds__(512, 1) void gemm_dma_kernel(const ConvGemmParams p
 // linears of the UNet it only ties the register-staged tiles.  This shape is the halo-patch conv's recipe (conv_patch.hip)
 // applied to a plain [M, K] x [N, K]^T product: 16 KB stages (128 + 128 rows of 64 bytes), three of them = 48 KB -> three
 // workgroups per CU, tile t + 2 in flight while tile t is multiplied, counted `s_waitcnt vmcnt(4)` (each wave issues exactly
-// four 1-KB pieces per tile), unpadded 64-byte rows with piece c of row r at c ^ ((r >> 2) & 3) (conflict-free ds_read_b128),
-// no staging registers, no VGPR -> LDS stores.  Epilogue = conv_gemm.hip's.
+// four 1-KB pieces per tile), unpadded swizzled 64-byte rows, no staging registers, no VGPR -> LDS stores.  The epilogue is the
+// 256^2 kernel's above, plus the fp32 slabs of K slices.
 // ---------------------------------------------------------------------------------------------------------------------------
 // NST = 4 (tile configs 19 / 20; round 3): a FOUR-stage ring, 64 KB -> two workgroups per CU with three tiles of lead instead of three
 // workgroups with two.  Same bytes in flight per CU, but each workgroup's wait is one tile further behind its issue: -8...-22 % on the
@@ -171,12 +156,10 @@ static_assert(3 * G1_STAGE >= G1_EROWS * G1_CLD * 4, "epilogue tile must fit");
 // kernel cannot tile (8 x 8) and the stride-2 convs.
 // BK = 64 (tile configs 25 / 26 / 27; round 4): 128-BYTE rows.  The L2 hands a CU one 128-byte line per request whatever part of it was asked for
 // (tools/probes/staging_probe.hip: 62 GB/s per CU in 64-byte segments, 113 GB/s in 128-byte segments) -- the 64-byte rows of BK = 32 use half of
-// every line they pull.  Stage = 32 KB (two stages = 64 KB = two workgroups per CU, three = 96 KB = one), eight pieces per wave and tile, piece
-// c of row r at c ^ ((r >> 1) & 7).
+// every line they pull.  Stage = 32 KB (two stages = 64 KB = two workgroups per CU, three = 96 KB = one), eight pieces per wave and tile.
 template <bool F16, bool GATHER, int G1_NST, int BK = 32>
 __global__ __launch_bounds__(256, (G1_NST * (G1_BM + G1_BN) * BK * 2 <= 49152) ? 3 : (G1_NST * (G1_BM + G1_BN) * BK * 2 <= 65536) ? 2 : 1)
 void gemm_dma128_kernel(const ConvGemmParams p) {
-    using E = El<F16>;
     constexpr int ROWB = BK * 2, LPR = ROWB / 16;              // bytes / 16-byte pieces per row
     constexpr int STAGE = (G1_BM + G1_BN) * ROWB;
     constexpr int PPW = G1_BM * ROWB / 1024 / 4;               // pieces per wave and operand tile: 2 | 4
@@ -195,7 +178,7 @@ void gemm_dma128_kernel(const ConvGemmParams p) {
     const int m0 = tile_m * G1_BM, n0 = tile_n * G1_BN;
     // K range of this slice (split-K: blockIdx.y; fp32 slabs + the fixed-order finish launch of conv_gemm.hip)
     const int nk_total = p.K / BK;                 // (GATHER: 9 taps x Cin / BK channel chunks)
-    const int per = (nk_total + p.split_k - 1) / p.split_k;
+    const int per = (nk_total + p.split_k - 1) / p.split_k;    // (tile_common.h::k_tiles_per_slice written out: through it an s_add got its operands swapped)
     const int kt0 = blockIdx.y * per;
     const int nk = max(0, min(nk_total, kt0 + per) - kt0);
 
@@ -210,7 +193,7 @@ void gemm_dma128_kernel(const ConvGemmParams p) {
 #pragma unroll
     for (int j = 0; j < NP; ++j) {
         const int id = (j % PPW) * 4 + wave;                  // piece inside its operand tile
-        const int q = id * 64 + lane, row = q / LPR, pc = (q % LPR) ^ (BK == 32 ? (row >> 2) & 3 : (row >> 1) & 7);
+        const int q = id * 64 + lane, row = q / LPR, pc = (q % LPR) ^ lds_row_swz<ROWB>(row);
         if (j >= PPW) soff[j] = (n0 + row < p.N) ? (uint32_t)(((size_t)(n0 + row) * p.K + pc * 8) * 2) : OOB;
         else if (!GATHER) soff[j] = (m0 + row < p.M) ? (uint32_t)(((size_t)(m0 + row) * p.x_pix_stride + pc * 8) * 2) : OOB;
         else {
@@ -257,13 +240,12 @@ void gemm_dma128_kernel(const ConvGemmParams p) {
     for (int a = 0; a < 2; ++a)
 #pragma unroll
         for (int b = 0; b < 2; ++b)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.f;
+            zero_frag(acc[a][b]);
 
-    // fragment addresses (16-deep slice kk: piece 2 kk + hi): row offsets are multiples of 32, so the swizzle term of row (base + col) is col's
+    // fragment addresses of the 16-deep slices
     int fo[BK / 16];
 #pragma unroll
-    for (int kk = 0; kk < BK / 16; ++kk) fo[kk] = col * ROWB + (((2 * kk + hi) ^ (BK == 32 ? (col >> 2) & 3 : (col >> 1) & 7)) << 4);
+    for (int kk = 0; kk < BK / 16; ++kk) fo[kk] = frag_offset<ROWB>(col, hi, kk);
     const bool wave_live = n0 + wn0 < p.N && m0 + wm0 < p.M;
 
 #pragma unroll
@@ -279,15 +261,7 @@ void gemm_dma128_kernel(const ConvGemmParams p) {
             const char* Ws = smem + slot * STAGE + G1_BM * ROWB + wn0 * ROWB;
 #pragma unroll
             for (int kk = 0; kk < BK / 16; ++kk) {
-                uint4 wf[2], xf[2];
-#pragma unroll
-                for (int a = 0; a < 2; ++a) wf[a] = *reinterpret_cast<const uint4*>(Ws + a * 32 * ROWB + fo[kk]);
-#pragma unroll
-                for (int b = 0; b < 2; ++b) xf[b] = *reinterpret_cast<const uint4*>(Xs + b * 32 * ROWB + fo[kk]);
-#pragma unroll
-                for (int a = 0; a < 2; ++a)
-#pragma unroll
-                    for (int b = 0; b < 2; ++b) acc[a][b] = E::mfma(wf[a], xf[b], acc[a][b]);
+                mfma_step16<F16, true, 32 * ROWB>(Ws, Xs, fo[kk], acc);
             }
         }
         slot = slot == G1_NST - 1 ? 0 : slot + 1;
@@ -319,12 +293,7 @@ void gemm_dma128_kernel(const ConvGemmParams p) {
 #pragma unroll
             for (int b = 0; b < 2; ++b)
 #pragma unroll
-                for (int a = 0; a < 2; ++a)
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        float* dst = Cs + (b * 32 + col) * G1_CLD + wn0 + a * 32 + 8 * j + 4 * hi;
-                        *reinterpret_cast<float4*>(dst) = make_float4(acc[a][b][4 * j], acc[a][b][4 * j + 1], acc[a][b][4 * j + 2], acc[a][b][4 * j + 3]);
-                    }
+                for (int a = 0; a < 2; ++a) acc_to_lds<G1_CLD>(Cs, b * 32 + col, wn0 + a * 32, hi, acc[a][b]);
         }
         __syncthreads();
         for (int c = tid; c < CHUNKS; c += 256) {
@@ -333,12 +302,11 @@ void gemm_dma128_kernel(const ConvGemmParams p) {
             else { row = c / CPR; cc = (c - row * CPR) * 8; }
             const int m = m0 + wr * G1_EROWS + row, n = n0 + cc;
             if (m >= p.M || n >= p.N) continue;
-            const float4 v0 = *reinterpret_cast<const float4*>(Cs + row * G1_CLD + cc);
-            const float4 v1 = *reinterpret_cast<const float4*>(Cs + row * G1_CLD + cc + 4);
+            const TileChunk8 t = lds_read8<G1_CLD>(Cs, row, cc);
             if (slab) {                         // raw fp32 partial tile -> slab [split][M][N]
-                slab_store8(slab, (size_t)m * p.N + n, v0, v1, n + 8 <= p.N, false);
+                slab_store8(slab, (size_t)m * p.N + n, t.v0, t.v1, n + 8 <= p.N, false);
             } else {
-                float v[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
+                float v[8] = {t.v0.x, t.v0.y, t.v0.z, t.v0.w, t.v1.x, t.v1.y, t.v1.z, t.v1.w};
                 epilogue8<F16>(p, v, m, n, (n + 8 <= p.N) ? 8 : 4, HWo, use_col_pre, col_pre0, col_pre1);
             }
         }
@@ -358,12 +326,8 @@ static int launch_dma128(const ConvGemmParams& p, hipStream_t s, const char* wha
     constexpr int LDS = NST * (G1_BM + G1_BN) * BK * 2;        // BK = 32: 49152 (three stages) | 65536 (four); BK = 64: 65536 (two) | 98304 (three)
     static_assert(LDS >= G1_EROWS * G1_CLD * 4, "epilogue tile must fit");
     const bool h = p.dtype == IMD_DTYPE_F16;
-    typedef void (*kern_t)(const ConvGemmParams);
-    const kern_t kern = h ? gemm_dma128_kernel<true, GATHER, NST, BK> : gemm_dma128_kernel<false, GATHER, NST, BK>;
-    if (int rc_attr = imd_lds_attr(reinterpret_cast<const void*>(kern), LDS, what)) return rc_attr;
     const long mt = (p.M + G1_BM - 1) / G1_BM, nt = (p.N + G1_BN - 1) / G1_BN;
-    hipLaunchKernelGGL(kern, dim3((unsigned)(mt * nt), (unsigned)p.split_k), dim3(256), LDS, s, p);
-    return imd_check_launch(what);
+    return tile_launch(h ? gemm_dma128_kernel<true, GATHER, NST, BK> : gemm_dma128_kernel<false, GATHER, NST, BK>, p, dim3((unsigned)(mt * nt), (unsigned)p.split_k), 256, LDS, what, s);
 }
 
 // tile configs 17 / 19 / 25 / 27 (plain linears) and 18 / 20 / 26 / 28 (3x3 convs): a ring of `stages` K chunks of `bk` elements -- three | four of 32 (64-byte rows),
@@ -371,24 +335,22 @@ static int launch_dma128(const ConvGemmParams& p, hipStream_t s, const char* wha
 int imd_launch_gemm_dma128(const ConvGemmParams& p, int stages, int bk, hipStream_t s) {
     if (!((bk == 32 && (stages == 3 || stages == 4)) || (bk == 64 && (stages == 2 || stages == 3))))
         return imd_set_error("gemm_dma128: %d ring stages of %d-element K chunks (3 | 4 of 32, 2 | 3 of 64)", stages, bk);
-    if (bk == 64) {
-        if (p.taps == 9) {
-            if (!imd_conv_dma_supported(p) || (p.Cin % 64)) return imd_set_error("conv_dma (128-byte rows): needs a 3x3 convolution with Cin %% 64 == 0 (got Cin=%d stride=%d)", p.Cin, p.stride);
-            return stages == 2 ? launch_dma128<true, 2, 64>(p, s, "conv_dma128 (BK 64)") : launch_dma128<true, 3, 64>(p, s, "conv_dma128 (BK 64, 3 stages)");
-        }
-        ConvGemmParams p1 = p;
-        p1.split_k = 1;
+    const bool conv = p.taps == 9, wide = bk == 64, deep = stages == (wide ? 3 : 4);      // deep: the ring with one more stage
+    if (conv) {         // (the two wordings differ on purpose: Cin % 64 for the 128-byte rows)
+        if (wide && (!imd_conv_dma_supported(p) || (p.Cin % 64))) return imd_set_error("conv_dma (128-byte rows): needs a 3x3 convolution with Cin %% 64 == 0 (got Cin=%d stride=%d)", p.Cin, p.stride);
+        if (!wide && !imd_conv_dma_supported(p)) return imd_set_error("conv_dma: needs a 3x3 convolution with Cin %% 32 == 0 (got Cin=%d stride=%d)", p.Cin, p.stride);
+    } else {            // (K % 64 == 0 also for the 64-byte rows: imd_gemm_dma_supported is the one predicate of the plain linears)
+        ConvGemmParams p1 = p; p1.split_k = 1;
         if (!imd_gemm_dma_supported(p1)) return imd_set_error("gemm_dma128: needs a plain linear layer with K %% 64 == 0 (got K=%d taps=%d)", p.K, p.taps);
-        return stages == 2 ? launch_dma128<false, 2, 64>(p, s, "gemm_dma128 (BK 64)") : launch_dma128<false, 3, 64>(p, s, "gemm_dma128 (BK 64, 3 stages)");
     }
-    if (p.taps == 9) {
-        if (!imd_conv_dma_supported(p)) return imd_set_error("conv_dma: needs a 3x3 convolution with Cin %% 32 == 0 (got Cin=%d stride=%d)", p.Cin, p.stride);
-        return stages == 3 ? launch_dma128<true, 3>(p, s, "conv_dma128") : launch_dma128<true, 4>(p, s, "conv_dma128 (4 stages)");
-    }
-    ConvGemmParams p1 = p;
-    p1.split_k = 1;
-    if (!imd_gemm_dma_supported(p1)) return imd_set_error("gemm_dma128: needs a plain linear layer with K %% 64 == 0 (got K=%d taps=%d)", p.K, p.taps);
-    return stages == 3 ? launch_dma128<false, 3>(p, s, "gemm_dma128") : launch_dma128<false, 4>(p, s, "gemm_dma128 (4 stages)");
+    // [128-byte | 64-byte rows][3x3 conv | plain linear][shorter | deeper ring]  (in this order the kernels are emitted as they always were)
+    static const struct { int (*launch)(const ConvGemmParams&, hipStream_t, const char*); const char* what; } form[2][2][2] = {
+        {{{launch_dma128<true, 2, 64>, "conv_dma128 (BK 64)"}, {launch_dma128<true, 3, 64>, "conv_dma128 (BK 64, 3 stages)"}},
+         {{launch_dma128<false, 2, 64>, "gemm_dma128 (BK 64)"}, {launch_dma128<false, 3, 64>, "gemm_dma128 (BK 64, 3 stages)"}}},
+        {{{launch_dma128<true, 3>, "conv_dma128"}, {launch_dma128<true, 4>, "conv_dma128 (4 stages)"}},
+         {{launch_dma128<false, 3>, "gemm_dma128"}, {launch_dma128<false, 4>, "gemm_dma128 (4 stages)"}}}};
+    const auto& f = form[!wide][!conv][deep];
+    return f.launch(p, s, f.what);
 }
 
 bool imd_gemm_dma_supported(const ConvGemmParams& p) {
@@ -399,10 +361,6 @@ bool imd_gemm_dma_supported(const ConvGemmParams& p) {
 int imd_launch_gemm_dma(const ConvGemmParams& p, hipStream_t s) {      // p: validated and completed (x_bytes, w_bytes, flags) by imd_launch_conv_gemm
     if (!imd_gemm_dma_supported(p)) return imd_set_error("gemm_dma: needs a plain linear layer with K %% 64 == 0 and no K split (got K=%d taps=%d split=%d)", p.K, p.taps, p.split_k);
     const bool h = p.dtype == IMD_DTYPE_F16;
-    const void* kern = h ? reinterpret_cast<const void*>(gemm_dma_kernel<true>) : reinterpret_cast<const void*>(gemm_dma_kernel<false>);
-    if (int rc_attr = imd_lds_attr(kern, GD_LDS, "gemm_dma")) return rc_attr;
     const long mt = (p.M + GD_BM - 1) / GD_BM, nt = (p.N + GD_BN - 1) / GD_BN;
-    if (h) hipLaunchKernelGGL(gemm_dma_kernel<true>, dim3((unsigned)(mt * nt)), dim3(512), GD_LDS, s, p);
-    else hipLaunchKernelGGL(gemm_dma_kernel<false>, dim3((unsigned)(mt * nt)), dim3(512), GD_LDS, s, p);
-    return imd_check_launch("gemm_dma");
+    return tile_launch(h ? gemm_dma_kernel<true> : gemm_dma_kernel<false>, p, dim3((unsigned)(mt * nt)), 512, GD_LDS, "gemm_dma", s);
 }

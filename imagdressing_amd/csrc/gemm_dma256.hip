@@ -3,8 +3,8 @@
 // 128 x 128 tiles of gemm_dma.hip).  Round 5; tile configs 30 (persistent) / 31 (one item per workgroup).  DESIGN.md section 2.2e has the
 // ablation history that shaped it.  What those shapes pay for on 128 x 128 tiles is not the multiplication (K = 640 is TEN 64-deep steps) but
 // what surrounds it once per tile -- the launch ramp, the first operands' latency, the output stream -- so this kernel is built around those:
-//   * 256 x 128 x 64 tiles, THREE 48 KB stages (144 KB), both operands global -> LDS by DMA in whole 128-byte rows (piece c of row r at
-//     c ^ ((r >> 1) & 7): conflict-free ds_read_b128, whole L2 lines);
+//   * 256 x 128 x 64 tiles, THREE 48 KB stages (144 KB), both operands global -> LDS by DMA in whole 128-byte rows (whole L2 lines;
+//     swizzled: tile_common.h::lds_row_swz);
 //   * WAVE SPECIALISATION: four producer waves issue every LDS-DMA piece and are the only waves that wait on them; eight consumer waves
 //     (4 along M x 2 along N, 64 x 64 each) read fragments, multiply and store.  One workgroup barrier per step is the whole handshake;
 //   * PERSISTENT: one 12-wave workgroup per CU walks a list of (tile, K slice) items, and the producers' ring is ONE software pipeline
@@ -15,8 +15,8 @@
 //     transpose so that 4 lanes store 64 contiguous bytes of a row (16-byte fragments drain at the L2's request rate: 2.5 vs 6.2 TB/s).
 // Same arithmetic as the tiled kernels (fp32 accumulation over K in 16-element MFMA steps, ascending; bit-identical to tile config 25 without
 // K slices), same reference layers (diffusers-0.24 BasicTransformerBlock feed-forward: GEGLU proj + out linear).
-#include "gemm_common.h"
-#include "lds_dma.h"
+// The blocks shared with the other tiled kernels (row swizzle, fragment offsets, the MFMA step, the launch body) live in tile_common.h.
+#include "tile_common.h"
 
 namespace {
 
@@ -24,27 +24,16 @@ constexpr int G2_BK = 64, G2_ROWB = G2_BK * 2;                   // 128-byte row
 
 struct G2Item { int m0, n0, kt0, nk, slice; };
 
-// item w of `items` = tiles x K slices, XCD-aware: consecutive items of one XCD (w mod 8: the dispatcher hands block b to XCD b mod 8,
-// and a persistent block's items stay congruent to its id mod 8 because the grid is a multiple of 8) are neighbours in tile order
+// item w of `items` = tiles x K slices, XCD-aware (gemm_common.h::xcd_remap over the ITEM list, then tile_of inside the slice): consecutive
+// items of one XCD (w mod 8: the dispatcher hands block b to XCD b mod 8, and a persistent block's items stay congruent to its id mod 8
+// because the grid is a multiple of 8) are neighbours in tile order
 __device__ __forceinline__ void g2_decode(const ConvGemmParams& p, unsigned w, unsigned items, int m_tiles, int n_tiles, int bm, int bn, int per, int nk_total,
                                           G2Item& o) {
-    if (p.flags & 12) {
-        const unsigned k = w & 7u, slot = w >> 3, q8 = items >> 3, r8 = items & 7u;
-        w = (k < r8 ? k * (q8 + 1) : r8 * (q8 + 1) + (k - r8) * q8) + slot;
-    }
+    w = xcd_remap(p.flags, w, items);
     const unsigned tiles = (unsigned)(m_tiles * n_tiles);
     const unsigned slice = w / tiles;
-    const unsigned t = w - slice * tiles;
     int tm, tn;
-    if (p.flags & 8) { tn = (int)(t / (unsigned)m_tiles); tm = (int)(t - (unsigned)tn * m_tiles); }
-    else if ((p.flags & 4) && (p.flags & 16)) {
-        constexpr unsigned GM = 8;
-        const unsigned per_group = GM * (unsigned)n_tiles;
-        const unsigned g = t / per_group, r = t - g * per_group;
-        const unsigned rows = min(GM, (unsigned)m_tiles - g * GM);
-        tn = (int)(r / rows);
-        tm = (int)(g * GM + (r - (unsigned)tn * rows));
-    } else { tm = (int)(t / (unsigned)n_tiles); tn = (int)(t - (unsigned)tm * n_tiles); }
+    tile_of(p.flags, w - slice * tiles, m_tiles, n_tiles, tm, tn);
     o.m0 = tm * bm; o.n0 = tn * bn; o.slice = (int)slice;
     o.kt0 = (int)slice * per;
     o.nk = min(nk_total, o.kt0 + per) - o.kt0;
@@ -63,11 +52,21 @@ __device__ __forceinline__ void g2_decode(const ConvGemmParams& p, unsigned w, u
 // stage g, one step of lead is less than the operands' latency.)
 // BM = 192 (round 6, tile config 32): six consumer + four producer waves.  For item counts that leave a third of the chip idle at 256 rows --
 // feed-forward out, 8192 x 640 x 2560: 32 x 5 = 160 tiles on 256 CUs -- 43 x 5 = 215 tiles of three quarters the work run in ONE round as well.
+// Registers 8 t .. 8 t + 3 of a 32 x 32 accumulator block hold channels 16 t + 4 hi + 0..3, registers 8 t + 4 .. 8 t + 7 channels 16 t + 8 + 4 hi + 0..3:
+// swapping the upper lanes' copy of the first group with the lower lanes' copy of the second (one v_permlane32_swap per pair) gives every lane the 8
+// consecutive channels 16 t + 8 hi + 0..7 of its row.  (row_common.h::quads_to_wide is the same exchange on packed 16-bit pairs.)
+__device__ __forceinline__ void gather8(const f32x16& acc, int t, float* v) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(acc[8 * t + e]), __float_as_uint(acc[8 * t + 4 + e]), false, false);
+        v[e] = __uint_as_float(r[0]); v[4 + e] = __uint_as_float(r[1]);
+    }
+}
+
 template <int BM> struct G2Waves { static constexpr int NCW = BM / 32, NPROD = BM == 192 ? 4 : BM / 64; };
 template <bool F16, int BM, int BN, int NST, bool PRE, bool RES>
 __global__ __launch_bounds__((G2Waves<BM>::NCW + G2Waves<BM>::NPROD) * 64, 3) void gemm_dma256_kernel       // (HIP: the second bound is WAVES PER SIMD -- twelve (ten) waves per CU either way)
 (const ConvGemmParams p) {
-    using E = El<F16>;
     constexpr int NCW = G2Waves<BM>::NCW, G2_NPROD = G2Waves<BM>::NPROD;   // consumer waves (BM / 64 along M x 2 along N), producer waves
     constexpr int G2_A = BM * G2_ROWB;                               // activation bytes per stage
     constexpr int APIECES = BM / 8;                                  // 1-KB pieces (8 rows x 128 B) of the activation tile
@@ -87,7 +86,7 @@ __global__ __launch_bounds__((G2Waves<BM>::NCW + G2Waves<BM>::NPROD) * 64, 3) vo
     const int m_tiles = (p.M + BM - 1) / BM, n_tiles = (p.N + BN - 1) / BN;
     const unsigned items = (unsigned)(m_tiles * n_tiles) * (unsigned)p.split_k;
     const int nk_total = p.K / G2_BK;
-    const int per = (nk_total + p.split_k - 1) / p.split_k;
+    const int per = k_tiles_per_slice(nk_total, p.split_k);
     const int HWo = p.Hout * p.Wout;
     // timing ablations with WRONG results (tuning knob 2 bits 5..7, tools/gemm256_bench.py): what is a launch made of.  They exist in
     // -DIMD_ABLATIONS builds only (like the attention kernel's): the product library neither compiles them nor lets knob 2 carry the bits
@@ -116,7 +115,7 @@ __global__ __launch_bounds__((G2Waves<BM>::NCW + G2Waves<BM>::NPROD) * 64, 3) vo
                 const int id = j * G2_NPROD + pw;     // activation pieces first, then weight pieces
                 constexpr int JW = APIECES / G2_NPROD; // (APIECES % NPROD == 0: a piece index j is an activation piece in every producer wave or in none)
                 const bool isw = j >= JW;
-                const int q = (isw ? id - APIECES : id) * 64 + lane, row = q >> 3, pc = (q & 7) ^ ((row >> 1) & 7);
+                const int q = (isw ? id - APIECES : id) * 64 + lane, row = q >> 3, pc = (q & 7) ^ ((row >> 1) & 7);   // (= lds_row_swz<G2_ROWB>(row), written out: through the function, in any of four shapes, all eight kernels compiled differently)
                 if (isw) soff[j] = (pi.n0 + row < p.N) ? (uint32_t)(((size_t)(pi.n0 + row) * p.K + pc * 8) * 2) : OOB;
                 else soff[j] = (pi.m0 + row < p.M) ? (uint32_t)(((size_t)(pi.m0 + row) * p.x_pix_stride + pc * 8) * 2) : OOB;
             }
@@ -170,14 +169,13 @@ __global__ __launch_bounds__((G2Waves<BM>::NCW + G2Waves<BM>::NPROD) * 64, 3) vo
         for (int a = 0; a < NA; ++a)
 #pragma unroll
             for (int b = 0; b < 2; ++b)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.f;
+                zero_frag(acc[a][b]);
     };
     zero_acc();
-    // fragment addresses (16-deep slice kk reads piece 2 kk + hi, stored at (2 kk + hi) ^ ((row >> 1) & 7); row offsets are multiples of 32)
+    // fragment addresses of the 16-deep slices
     int fo[G2_BK / 16];
 #pragma unroll
-    for (int kk = 0; kk < G2_BK / 16; ++kk) fo[kk] = col * G2_ROWB + (((2 * kk + hi) ^ ((col >> 1) & 7)) << 4);
+    for (int kk = 0; kk < G2_BK / 16; ++kk) fo[kk] = frag_offset<G2_ROWB>(col, hi, kk);
 
     __syncthreads();                                  // barrier 0
     int slot = 0;
@@ -194,15 +192,7 @@ __global__ __launch_bounds__((G2Waves<BM>::NCW + G2Waves<BM>::NPROD) * 64, 3) vo
                 const char* Ws = smem + slot * STAGE + G2_A + wn0 * G2_ROWB;
 #pragma unroll
                 for (int kk = 0; kk < G2_BK / 16; ++kk) {
-                    uint4 wf[NA], xf[2];
-#pragma unroll
-                    for (int a = 0; a < NA; ++a) wf[a] = *reinterpret_cast<const uint4*>(Ws + a * 32 * G2_ROWB + fo[kk]);
-#pragma unroll
-                    for (int b = 0; b < 2; ++b) xf[b] = *reinterpret_cast<const uint4*>(Xs + b * 32 * G2_ROWB + fo[kk]);
-#pragma unroll
-                    for (int a = 0; a < NA; ++a)
-#pragma unroll
-                        for (int b = 0; b < 2; ++b) acc[a][b] = E::mfma(wf[a], xf[b], acc[a][b]);
+                    mfma_step16<F16, true, 32 * G2_ROWB>(Ws, Xs, fo[kk], acc);
                 }
             }
             slot = slot == NST - 1 ? 0 : slot + 1;
@@ -276,11 +266,7 @@ __global__ __launch_bounds__((G2Waves<BM>::NCW + G2Waves<BM>::NPROD) * 64, 3) vo
                 uint4 pk0[NA][2];
                 auto finish = [&](int a, int b, int t, const uint4& rr) __attribute__((always_inline)) {
                     float v[8];
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(acc[a][b][8 * t + e]), __float_as_uint(acc[a][b][8 * t + 4 + e]), false, false);
-                        v[e] = __uint_as_float(r[0]); v[4 + e] = __uint_as_float(r[1]);
-                    }
+                    gather8(acc[a][b], t, v);
                     uint4 pk = make_uint4(0, 0, 0, 0);
                     epilogue8<F16>(p, v, ci.m0 + wm0 + b * 32 + col, ci.n0 + wn0 + a * 32 + 16 * t + 8 * hi, 8, HWo, true, make_float4(0, 0, 0, 0), make_float4(0, 0, 0, 0), true, rr, &pk);
                     return pk;
@@ -328,11 +314,7 @@ __global__ __launch_bounds__((G2Waves<BM>::NCW + G2Waves<BM>::NPROD) * 64, 3) vo
                     // chunk (a, t) of this lane: 8 channels -> 16 bytes, or 4 GEGLU outputs -> 8 bytes
                     auto chunk = [&](int a, int t) __attribute__((always_inline)) {
                         float v[8];
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) {
-                            const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(acc[a][b][8 * t + e]), __float_as_uint(acc[a][b][8 * t + 4 + e]), false, false);
-                            v[e] = __uint_as_float(r[0]); v[4 + e] = __uint_as_float(r[1]);
-                        }
+                        gather8(acc[a][b], t, v);
                         const int n = ci.n0 + wn0 + a * 32 + 16 * t + 8 * hi;
                         uint4 pk = make_uint4(0, 0, 0, 0);
                         if (m < p.M) {
@@ -341,6 +323,7 @@ __global__ __launch_bounds__((G2Waves<BM>::NCW + G2Waves<BM>::NPROD) * 64, 3) vo
                         }
                         return pk;
                     };
+                    // (read-back + row store of the two branches differ in the destination column only: as one lambda, in two shapes, every kernel changed)
                     if (geglu) {                      // one pass: 32 rows x 64 bytes (the wave's 32 output channels); 8-byte chunk c of row r at slot c ^ (sw << 1)
 #pragma unroll
                         for (int a = 0; a < NA; ++a)
@@ -379,15 +362,8 @@ __global__ __launch_bounds__((G2Waves<BM>::NCW + G2Waves<BM>::NPROD) * 64, 3) vo
                 for (int a = 0; a < NA; ++a) {
 #pragma unroll
                     for (int t = 0; t < 2; ++t) {
-                        // registers 8 t .. 8 t + 3 hold channels 16 t + 4 hi + 0..3 of the block, 8 t + 4 .. 8 t + 7 channels 16 t + 8 + 4 hi + 0..3:
-                        // swapping the upper lanes' copy of the first group with the lower lanes' copy of the second gives every lane the 8
-                        // consecutive channels 16 t + 8 hi + 0..7 of its row
                         float v[8];
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) {
-                            const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(acc[a][b][8 * t + e]), __float_as_uint(acc[a][b][8 * t + 4 + e]), false, false);
-                            v[e] = __uint_as_float(r[0]); v[4 + e] = __uint_as_float(r[1]);
-                        }
+                        gather8(acc[a][b], t, v);
                         const int n = ci.n0 + wn0 + a * 32 + 16 * t + 8 * hi;
                         if (m < p.M && n < p.N) {
                             const int nv = (n + 8 <= p.N) ? 8 : 4;
@@ -411,18 +387,15 @@ int launch_dma256_v(const ConvGemmParams& p, bool persistent, hipStream_t s, con
     constexpr int WG_PER_CU = BM >= 192 ? 1 : 2;
     static_assert(LDS * WG_PER_CU <= 160 * 1024, "ring + transpose areas must fit the CU's LDS");
     const bool h = p.dtype == IMD_DTYPE_F16;
-    typedef void (*kern_t)(const ConvGemmParams);
-    const kern_t kern = h ? gemm_dma256_kernel<true, BM, BN, NST, PRE, RES> : gemm_dma256_kernel<false, BM, BN, NST, PRE, RES>;
+    const tile_kern_t kern = h ? gemm_dma256_kernel<true, BM, BN, NST, PRE, RES> : gemm_dma256_kernel<false, BM, BN, NST, PRE, RES>;
     // per DEVICE (a process may drive several GPUs): the 160 KB dynamic-LDS attribute and the CU count that sizes the persistent grid
     // (a multiple of 8: a block's items stay on its XCD's share of the tile order)
-    if (int rc_attr = imd_lds_attr(reinterpret_cast<const void*>(kern), LDS, what)) return rc_attr;
     const int n_cu = imd_cu_count8();
     if (n_cu < 0) return imd_set_error("%s: cannot query the device", what);
     const long items = (long)((p.M + BM - 1) / BM) * ((p.N + BN - 1) / BN) * p.split_k;
     const long slots = (long)n_cu * WG_PER_CU;
     const long grid = persistent ? (items < slots ? items : slots) : items;
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3((G2Waves<BM>::NCW + G2Waves<BM>::NPROD) * 64), LDS, s, p);
-    return imd_check_launch(what);
+    return tile_launch(kern, p, dim3((unsigned)grid), (G2Waves<BM>::NCW + G2Waves<BM>::NPROD) * 64, LDS, what, s);
 }
 
 template <int BM, int BN, int NST>
@@ -443,7 +416,7 @@ int imd_launch_gemm_dma256(const ConvGemmParams& p, int form, hipStream_t s) {
     ConvGemmParams p1 = p;
     p1.split_k = 1;
     if (!imd_gemm_dma_supported(p1)) return imd_set_error("gemm_dma256: needs a plain linear layer with K %% 64 == 0 (got K=%d taps=%d)", p.K, p.taps);
-    const int nk_total = p.K / G2_BK, per = (nk_total + p.split_k - 1) / p.split_k;
+    const int nk_total = p.K / G2_BK, per = k_tiles_per_slice(nk_total, p.split_k);
     if (p.split_k > 1 && (long)(p.split_k - 1) * per >= nk_total) return imd_set_error("gemm_dma256: %d K slices over %d K tiles leave a slice empty", p.split_k, nk_total);
     switch (form) {
         case 0: return launch_dma256<256, 128, 3>(p, true, s, "gemm_dma256 (256x128, persistent)");

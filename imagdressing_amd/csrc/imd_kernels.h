@@ -65,8 +65,8 @@ int imd_launch_row_qkv(const ConvGemmParams& p, int ln, float ln_eps, hipStream_
 bool imd_gemm_dma_supported(const ConvGemmParams& p);                                       // gemm_dma.hip
 int imd_launch_gemm_dma(const ConvGemmParams& p, hipStream_t s);
 int imd_launch_gemm_dma128(const ConvGemmParams& p, int stages, int bk, hipStream_t s);      // ring stages x K chunk: 3 | 4 x 32, 2 | 3 x 64
-int imd_launch_gemm_dma256(const ConvGemmParams& p, int form, hipStream_t s);        // gemm_dma256.hip: 0 = 256x128 persistent, 1 = 256x128 one item per workgroup (tile configs 30 / 31)
-bool imd_conv_dma_supported(const ConvGemmParams& p);                         // gemm_dma.hip: 128 x 128 x 32, 3-stage ring (tile config 17)
+int imd_launch_gemm_dma256(const ConvGemmParams& p, int form, hipStream_t s);        // gemm_dma256.hip: 0 = 256x128 persistent, 1 = 256x128 one item per workgroup, 2 = 192x128 persistent (tile configs 30 / 31 / 32)
+bool imd_conv_dma_supported(const ConvGemmParams& p);                         // gemm_dma.hip: the gathering form of the 128 x 128 LDS-DMA tiles (tile configs 18 / 20 / 26 / 28)
 int imd_launch_ff_geglu(const imd_ff_params& p, hipStream_t s);                              // ff_fused.hip
 bool imd_text_xattn320_supported_of(const imd_xattn_params& p);                              // row_xattn.hip
 int imd_launch_text_xattn320(const imd_xattn_params& p, hipStream_t s);
@@ -74,7 +74,7 @@ int imd_launch_attention(const AttnParams& p, hipStream_t s);
 int imd_launch_attention_d40(const AttnParams& p, int variant, hipStream_t s);
 int imd_launch_attention_fp8(const AttnParams& p, int eq, int ek, int ev, hipStream_t s);                       // attention_d40_fp8.hip
 int imd_launch_attn_quantize_fp8(const bf16_t* src, unsigned char* dst, int kind, long rows_or_groups, int LP, int exp2_scale,
-                                 float pad_val, int dtype, hipStream_t s);   // attention_d40.hip: software-pipelined level-0 kernel
+                                 float pad_val, int dtype, hipStream_t s);   // attention_d40_fp8.hip: the quantiser of its operands
 extern int g_attn_qw40;
 extern int g_attn_xcd;
 #ifdef IMD_ATTN_SWEEP

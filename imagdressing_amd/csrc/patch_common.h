@@ -3,7 +3,8 @@
 // channel chunk in LDS once and lets the taps read their MFMA operand fragments from it at constant row offsets, while the weight
 // tile of a tap streams through a ring in LDS.  What is specific to a member -- its tile, its schedule (main loop and waits), what
 // its epilogue adds -- is told at the head of its file; the blocks every member repeats live here, each with its explanation.  The
-// staging piece itself is lds_dma.h::dma16_run, the GroupNorm-statistics epilogue gemm_common.h::gn_stats_fold_store.
+// staging piece itself is lds_dma.h::dma16_run, the GroupNorm-statistics epilogue gemm_common.h::gn_stats_fold_store; row swizzle,
+// accumulators -> LDS tile and the launch body are the tiled GEMMs' (tile_common.h).
 //
 // RULE: these helpers only move text.  A kernel uses one only if it compiles to the same instructions as
 // with the block written out (compare the device assembly); where it does not, the kernel keeps the block inline and says so in one
@@ -11,8 +12,7 @@
 #pragma once
 #include <type_traits>
 
-#include "gemm_common.h"
-#include "lds_dma.h"
+#include "tile_common.h"
 
 namespace {
 
@@ -66,15 +66,6 @@ __device__ __forceinline__ int halo_src_pixel(const ConvGemmParams& p, int b, in
     return (b * p.Hin + sy) * p.Win + sx;
 }
 
-// ---- epilogue: one 32 x 32 accumulator fragment -> the fp32 tile in LDS (row stride CLD_ floats).  The lane owns tile row `row`
-// (its MFMA column, through kColPix), register quad j the 4 consecutive channels c0 + 8 j + 4 hi ----
-template <int CLD_>
-__device__ __forceinline__ void acc_to_lds(float* Cs, int row, int c0, int hi, const f32x16& acc) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-        *reinterpret_cast<float4*>(Cs + row * CLD_ + c0 + 8 * j + 4 * hi) = make_float4(acc[4 * j], acc[4 * j + 1], acc[4 * j + 2], acc[4 * j + 3]);
-}
-
 // ---- the 8 x 16 pixel x 128 channel tile of conv_patch.hip and conv_ups_phase.hip ----
 constexpr int TH = 8, TW = 16;                 // output pixels per workgroup: 8 rows x 16 columns
 constexpr int PW = TW + 2, PH = TH + 2;        // halo patch
@@ -86,8 +77,8 @@ constexpr int EROWS = 64;
 constexpr int EPI_LDS = EROWS * CLD * 4;       // 33,792
 // LDS-DMA geometry at CKD channels per chunk.  Both operands are written lane-linear, i.e. as unpadded rows of RB bytes: the halo
 // patch of a chunk (180 pixel rows) and the weight tile of a tap (128 rows), in one-KB pieces.  Fragment reads stay conflict-free
-// through a SOURCE-side swizzle -- piece c of row r sits at position c ^ swz(r), so the 16 rows of a ds_read_b128 lane group (any
-// 8 + 8 consecutive rows of the patch, or aligned row groups of the weight tile) fall on 16 distinct 16-byte bank slots.
+// through the SOURCE-side swizzle of tile_common.h::lds_row_swz -- piece c of row r sits at position c ^ swz(r) -- for any 8 + 8
+// consecutive rows of the patch as for aligned row groups of the weight tile.
 //   CKD = 32: 64-byte rows, 12 patch pieces, 8 weight pieces, three-slot weight ring, 48 KB.
 //   CKD = 64 (tile config 29): 128-byte rows -- the L2 hands a CU whole 128-byte lines (tools/probes/staging_probe.hip: 62 GB/s per CU
 //   in 64-byte segments, 113 in 128-byte ones) -- 23 patch pieces (six per wave with one empty), 16 weight pieces, two-slot ring, 80 KB.
@@ -101,7 +92,7 @@ template <int CKD> struct PD {
     static constexpr int NWR = CKD == 32 ? 3 : 2;
     static constexpr int LDS = 2 * AB + NWR * WB;                           // 49,152 | 81,920
     static_assert(LDS >= EPI_LDS, "the epilogue tile must fit the main-loop LDS");
-    static __device__ __forceinline__ int swz(int r) { return CKD == 32 ? (r >> 2) & 3 : (r >> 1) & 7; }
+    static __device__ __forceinline__ int swz(int r) { return lds_row_swz<RB>(r); }
 };
 
 // ---- host side ----
@@ -122,13 +113,6 @@ static long halo_blocks(const ConvGemmParams& p, int th, int tw, int bn) {
 // thread per group)
 static bool halo_stats_ok(const ConvGemmParams& p) {
     return !(p.split_k > 1 || p.out_f32 || p.gn_stats_groups <= 0 || p.gn_stats_groups > 64 || p.N % p.gn_stats_groups || (p.N / p.gn_stats_groups) < 8);
-}
-// the launch itself: dynamic-LDS attribute, `blocks` x `slices` workgroups of `threads`
-typedef void (*halo_kern_t)(const ConvGemmParams);
-static int halo_launch(halo_kern_t kern, const ConvGemmParams& p, long blocks, int slices, int threads, int lds, const char* what, hipStream_t s) {
-    if (int rc_attr = imd_lds_attr(reinterpret_cast<const void*>(kern), lds, what)) return rc_attr;
-    hipLaunchKernelGGL(kern, dim3((unsigned)blocks, (unsigned)slices), dim3(threads), lds, s, p);
-    return imd_check_launch(what);
 }
 
 }  // namespace
