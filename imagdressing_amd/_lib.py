@@ -189,6 +189,8 @@ SYMBOLS = {
     "imd_ddim_cfg_step_rows": (C.c_int, [C.POINTER(DdimParams), C.c_void_p, C.c_void_p]),
     "imd_sampler_step": (C.c_int, [C.POINTER(SamplerParams), C.c_void_p]),
     "imd_sampler_step_rows": (C.c_int, [C.POINTER(SamplerParams), C.c_void_p, C.c_void_p]),
+    "imd_sampler_step_rows_at": (C.c_int, [C.POINTER(SamplerParams), C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "imd_session_input_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "imd_image_resample": (C.c_int, [C.POINTER(ImageResampleParams), C.c_void_p]),
     "imd_image_resample_form": (C.c_int, [C.POINTER(ImageResampleParams)]),
     "imd_image_pack_u8": (C.c_int, [C.POINTER(ImagePackParams), C.c_void_p]),

@@ -70,6 +70,13 @@ __global__ __launch_bounds__(256) void ddim_cfg_step_kernel(const DdimParams p, 
     }
 }
 
+// the next UNet input of one pixel: 16-bit(in_scale z), channels padded 4 -> 8 (one expression for the step kernels and the session's
+// input launch, so that the two agree bit for bit)
+template <bool F16>
+__device__ __forceinline__ uint4 session_input_pack(float in_scale, const float (&zz)[4]) {
+    return make_uint4(El<F16>::pack2(in_scale * zz[0], in_scale * zz[1]), El<F16>::pack2(in_scale * zz[2], in_scale * zz[3]), 0u, 0u);
+}
+
 // sampler_step: the same fused launch for every sampler whose update is affine in the latent, the guided epsilon, a short history
 // and noise (DPM-Solver++ 1 / 2M, Euler, Euler-ancestral, PNDM/PLMS -- imd_sampler_params):
 //   m  = m_x z + m_e eps;   z' = z_x z + z_m m + sum_k z_h[k] H[k] + z_n noise;   blend;   H[store] = m;   x_next = 16-bit(in_scale z')
@@ -138,7 +145,7 @@ __global__ __launch_bounds__(256) void sampler_step_kernel(const SamplerParams p
         reinterpret_cast<float4*>(p.z)[i] = make_float4(zz[0], zz[1], zz[2], zz[3]);
         if (store >= 0) reinterpret_cast<float4*>(p.hist)[(long)store * total + i] = make_float4(mm[0], mm[1], mm[2], mm[3]);
         if (p.x_next) {
-            const uint4 o = make_uint4(El<F16>::pack2(in_scale * zz[0], in_scale * zz[1]), El<F16>::pack2(in_scale * zz[2], in_scale * zz[3]), 0u, 0u);
+            const uint4 o = session_input_pack<F16>(in_scale, zz);
             reinterpret_cast<uint4*>(p.x_next)[i] = o;
             reinterpret_cast<uint4*>(p.x_next)[i + total] = o;
         }
@@ -151,11 +158,35 @@ __global__ __launch_bounds__(256) void sampler_step_kernel(const SamplerParams p
 // bytes.  The per-pixel arithmetic is sampler_step_kernel's, statement for statement (same expression trees, same contraction): with
 // every row equal and active the two launches are bit-identical.  The row of a pixel is i / HW, so a block that spans several rows
 // (HW < 256) reads several blocks; at the real geometries (HW >= 64) the four loads are wave-uniform and hit one cache line.
-template <bool F16>
-__global__ __launch_bounds__(256) void sampler_step_rows_kernel(const SamplerParams p, const float* __restrict__ coef_rows) {
+//
+// sampler_step_rows_at (a COMPACTING session, whose forward runs p.B <= slots batch rows) is the same kernel with ONE trailing SlotMap
+// argument -- the instantiation with the empty pack keeps the two-argument signature, hence the kernarg layout and instruction stream it
+// had before the variant existed (the ddim_cfg_step_kernel idiom).  Two address spaces are then apart: `i` / `total` index what the
+// forward produced and consumes (eps, x_next, the coefficient block, the guidance scale: batch ROWS), `si` / `stotal` what belongs to
+// the request (z, the history with plane k at hist + k slots HW, noise, the blend operands: SLOTS).  Row r is the request living in
+// slot row_slot[r]; a row whose slot is outside [0, slots) is idle and skipped like an inactive one BEFORE anything is addressed
+// through it, so whatever the device map holds the kernel stays inside its buffers; slots no row names keep their bytes.  (Two rows
+// naming one slot would race: the session's plan gives every running slot exactly one row.)  The map load is one dword per pixel,
+// wave-uniform at HW >= 64 like the coefficients.
+struct SlotMap {
+    const int* row_slot;                                   // DEVICE [B]: the slot of every batch row
+    int slots;
+};
+
+template <bool F16, typename... Map>
+__global__ __launch_bounds__(256) void sampler_step_rows_kernel(const SamplerParams p, const float* __restrict__ coef_rows, const Map... map) {
+    static_assert(sizeof...(Map) <= 1, "row == slot (no map) or one SlotMap");
     const long total = (long)p.B * p.HW;                   // one thread per pixel (4 channels = 16 B)
+    long stotal = total;
+    if constexpr (sizeof...(Map) == 1) stotal = (((long)map.slots * p.HW), ...);
     for (long i = blockIdx.x * 256L + threadIdx.x; i < total; i += (long)gridDim.x * 256L) {
         const long b = i / p.HW;                           // the latent row of this pixel
+        long si = i;                                       // ... and the pixel in its slot
+        if constexpr (sizeof...(Map) == 1) {
+            const int slot = (map.row_slot[b], ...);
+            if (slot < 0 || slot >= (map.slots, ...)) continue;          // idle row
+            si = (long)slot * p.HW + (i - b * p.HW);
+        }
         const float4* row = reinterpret_cast<const float4*>(coef_rows) + b * (IMD_SAMPLER_ROW_FLOATS / 4);
         const float4 r3 = row[3];
         if (r3.y == 0.f) continue;                         // inactive: neither read nor written
@@ -165,7 +196,7 @@ __global__ __launch_bounds__(256) void sampler_step_rows_kernel(const SamplerPar
         const float z_n = r2.x, b_img = r2.y, b_noise = r2.z, in_scale = r2.w;
         int store = (int)r3.x;
         if (store >= p.K) store = -1;                      // (device coefficients are not seen by the launcher: never past the buffer)
-        const float4 z = reinterpret_cast<const float4*>(p.z)[i];
+        const float4 z = reinterpret_cast<const float4*>(p.z)[si];
         const float4 ec = reinterpret_cast<const float4*>(p.eps)[i];
         const float4 eu = reinterpret_cast<const float4*>(p.eps)[i + total];
         float zz[4] = {z.x, z.y, z.z, z.w};
@@ -176,19 +207,19 @@ __global__ __launch_bounds__(256) void sampler_step_rows_kernel(const SamplerPar
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             float4 h = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (k < p.K && zh[k] != 0.f) h = reinterpret_cast<const float4*>(p.hist)[(long)k * total + i];
+            if (k < p.K && zh[k] != 0.f) h = reinterpret_cast<const float4*>(p.hist)[(long)k * stotal + si];
             hs[k][0] = h.x; hs[k][1] = h.y; hs[k][2] = h.z; hs[k][3] = h.w;
         }
         float mk = 1.f;
         float zi[4] = {0, 0, 0, 0}, nz[4] = {0, 0, 0, 0}, vn[4] = {0, 0, 0, 0};
         if (p.noise) {
-            const float4 n = reinterpret_cast<const float4*>(p.noise)[i];
+            const float4 n = reinterpret_cast<const float4*>(p.noise)[si];
             vn[0] = z_n * n.x; vn[1] = z_n * n.y; vn[2] = z_n * n.z; vn[3] = z_n * n.w;
         }
         if (p.mask) {
-            mk = p.mask[i];
-            const float4 a = reinterpret_cast<const float4*>(p.z_img)[i];
-            const float4 n = reinterpret_cast<const float4*>(p.blend_noise)[i];
+            mk = p.mask[si];
+            const float4 a = reinterpret_cast<const float4*>(p.z_img)[si];
+            const float4 n = reinterpret_cast<const float4*>(p.blend_noise)[si];
             zi[0] = a.x; zi[1] = a.y; zi[2] = a.z; zi[3] = a.w;
             nz[0] = n.x; nz[1] = n.y; nz[2] = n.z; nz[3] = n.w;
         }
@@ -207,13 +238,33 @@ __global__ __launch_bounds__(256) void sampler_step_rows_kernel(const SamplerPar
             }
             zz[e] = zn;
         }
-        reinterpret_cast<float4*>(p.z)[i] = make_float4(zz[0], zz[1], zz[2], zz[3]);
-        if (store >= 0) reinterpret_cast<float4*>(p.hist)[(long)store * total + i] = make_float4(mm[0], mm[1], mm[2], mm[3]);
+        reinterpret_cast<float4*>(p.z)[si] = make_float4(zz[0], zz[1], zz[2], zz[3]);
+        if (store >= 0) reinterpret_cast<float4*>(p.hist)[(long)store * stotal + si] = make_float4(mm[0], mm[1], mm[2], mm[3]);
         if (p.x_next) {
-            const uint4 o = make_uint4(El<F16>::pack2(in_scale * zz[0], in_scale * zz[1]), El<F16>::pack2(in_scale * zz[2], in_scale * zz[3]), 0u, 0u);
+            const uint4 o = session_input_pack<F16>(in_scale, zz);
             reinterpret_cast<uint4*>(p.x_next)[i] = o;
             reinterpret_cast<uint4*>(p.x_next)[i + total] = o;
         }
+    }
+}
+
+// session_input_rows: x_in[r] = x_in[B + r] = 16-bit(in_scale[r] z[row_slot[r]]), channels 4..7 zero -- the UNet input of a request
+// written from its fp32 latent with the step's own pack expression (admission, and the re-layout of every row at a repack: it reads
+// z and writes x_in, never what it wrote).  Rows with a slot outside [0, slots) are skipped.
+template <bool F16>
+__global__ __launch_bounds__(256) void session_input_rows_kernel(const float* __restrict__ z, const int* __restrict__ row_slot,
+                                                                 const float* __restrict__ in_scale_rows, bf16_t* __restrict__ x_in,
+                                                                 int B, int slots, int HW) {
+    const long total = (long)B * HW;
+    for (long i = blockIdx.x * 256L + threadIdx.x; i < total; i += (long)gridDim.x * 256L) {
+        const long r = i / HW;
+        const int slot = row_slot[r];
+        if (slot < 0 || slot >= slots) continue;
+        const float4 v = reinterpret_cast<const float4*>(z)[(long)slot * HW + (i - r * HW)];
+        const float zz[4] = {v.x, v.y, v.z, v.w};
+        const uint4 o = session_input_pack<F16>(in_scale_rows[r], zz);
+        reinterpret_cast<uint4*>(x_in)[i] = o;
+        reinterpret_cast<uint4*>(x_in)[i + total] = o;
     }
 }
 
@@ -411,6 +462,36 @@ int imd_launch_sampler_step_rows(const SamplerParams& p, const float* coef_rows,
     if (p.dtype == IMD_DTYPE_F16) hipLaunchKernelGGL(sampler_step_rows_kernel<true>, dim3(grid_for((long)p.B * p.HW)), dim3(256), 0, s, p, coef_rows);
     else hipLaunchKernelGGL(sampler_step_rows_kernel<false>, dim3(grid_for((long)p.B * p.HW)), dim3(256), 0, s, p, coef_rows);
     return imd_check_launch("sampler_step_rows");
+}
+
+int imd_launch_sampler_step_rows_at(const SamplerParams& p, const float* coef_rows, const int* row_slot, int slots, hipStream_t s) {
+    if (!coef_rows) return imd_set_error("sampler_step_rows_at: null coef_rows");
+    if (reinterpret_cast<uintptr_t>(coef_rows) & 15) return imd_set_error("sampler_step_rows_at: coef_rows must be 16-byte aligned (four float4 per batch row)");
+    if (!row_slot) return imd_set_error("sampler_step_rows_at: null row_slot");
+    if (reinterpret_cast<uintptr_t>(row_slot) & 3) return imd_set_error("sampler_step_rows_at: row_slot must be 4-byte aligned");
+    if (slots < 1) return imd_set_error("sampler_step_rows_at: slots (%d) must be >= 1", slots);
+    if (sampler_step_refusal(p, "sampler_step_rows_at", true)) return 1;
+    if (p.B > slots) return imd_set_error("sampler_step_rows_at: B (%d batch rows) exceeds slots (%d)", p.B, slots);
+    const SlotMap map = {row_slot, slots};
+    if (p.dtype == IMD_DTYPE_F16) hipLaunchKernelGGL((sampler_step_rows_kernel<true, SlotMap>), dim3(grid_for((long)p.B * p.HW)), dim3(256), 0, s, p, coef_rows, map);
+    else hipLaunchKernelGGL((sampler_step_rows_kernel<false, SlotMap>), dim3(grid_for((long)p.B * p.HW)), dim3(256), 0, s, p, coef_rows, map);
+    return imd_check_launch("sampler_step_rows_at");
+}
+
+int imd_launch_session_input_rows(const float* z, const int* row_slot, const float* in_scale_rows, bf16_t* x_in, int B, int slots, int HW,
+                                  int dtype, hipStream_t s) {
+    if (!z || !row_slot || !in_scale_rows || !x_in) return imd_set_error("session_input_rows: null pointer");
+    if (B <= 0 || HW <= 0) return imd_set_error("session_input_rows: empty input");
+    if (slots < 1) return imd_set_error("session_input_rows: slots (%d) must be >= 1", slots);
+    if (B > slots) return imd_set_error("session_input_rows: B (%d batch rows) exceeds slots (%d)", B, slots);
+    if ((reinterpret_cast<uintptr_t>(z) & 15) || (reinterpret_cast<uintptr_t>(x_in) & 15))
+        return imd_set_error("session_input_rows: z and x_in must be 16-byte aligned");
+    if ((reinterpret_cast<uintptr_t>(row_slot) & 3) || (reinterpret_cast<uintptr_t>(in_scale_rows) & 3))
+        return imd_set_error("session_input_rows: row_slot and in_scale_rows must be 4-byte aligned");
+    if (dtype == IMD_DTYPE_F16) hipLaunchKernelGGL(session_input_rows_kernel<true>, dim3(grid_for((long)B * HW)), dim3(256), 0, s, z, row_slot, in_scale_rows, x_in, B, slots, HW);
+    else if (dtype == IMD_DTYPE_BF16) hipLaunchKernelGGL(session_input_rows_kernel<false>, dim3(grid_for((long)B * HW)), dim3(256), 0, s, z, row_slot, in_scale_rows, x_in, B, slots, HW);
+    else return imd_set_error("session_input_rows: unknown dtype %d", dtype);
+    return imd_check_launch("session_input_rows");
 }
 
 int imd_launch_timestep_embedding(const float* t, float* out, int B, int dim, hipStream_t s) {

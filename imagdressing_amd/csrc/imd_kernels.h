@@ -94,6 +94,9 @@ int imd_launch_ddim_cfg_step(const DdimParams& p, hipStream_t s);
 int imd_launch_ddim_cfg_step_rows(const DdimParams& p, const float* guidance, hipStream_t s);
 int imd_launch_sampler_step(const SamplerParams& p, hipStream_t s);
 int imd_launch_sampler_step_rows(const SamplerParams& p, const float* coef_rows, hipStream_t s);
+int imd_launch_sampler_step_rows_at(const SamplerParams& p, const float* coef_rows, const int* row_slot, int slots, hipStream_t s);
+int imd_launch_session_input_rows(const float* z, const int* row_slot, const float* in_scale_rows, bf16_t* x_in, int B, int slots, int HW,
+                                  int dtype, hipStream_t s);
 int imd_launch_image_resample(const ImageResampleParams& p, hipStream_t s);          // image.hip
 int imd_image_resample_form_of(const ImageResampleParams& p);                        // launches it would make: 1 | 2, 0 = refused
 int imd_launch_image_pack_u8(const ImagePackParams& p, hipStream_t s);

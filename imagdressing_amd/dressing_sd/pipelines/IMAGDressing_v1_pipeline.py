@@ -21,10 +21,11 @@ class IMAGDressing_v1(PipelineBase):
     def set_scale(self, scale):                                            # :342-345
         set_scale_by_type(self.unet, RefSAttnProcessor2_0, scale=scale)
 
-    def open_session(self, slots: int, width: int, height: int, controlnet_conditioning_scale: float = 1.0):
+    def open_session(self, slots: int, width: int, height: int, controlnet_conditioning_scale: float = 1.0, compact: bool = False, widths=None):
         """In-flight batching: a :class:`imagdressing_amd.session.DenoiseSession` with ``slots`` slots at ``width`` x ``height``
-        (``controlnet_conditioning_scale`` is accepted for a uniform surface; this pipeline has no ControlNet)."""
-        return self._open_session(slots, width, height)
+        (``controlnet_conditioning_scale`` is accepted for a uniform surface; this pipeline has no ControlNet).  ``compact`` / ``widths``:
+        run only as many batch rows as requests are running (``_open_session``)."""
+        return self._open_session(slots, width, height, compact=compact, widths=widths)
 
     @torch.no_grad()
     def __call__(self, prompt, null_prompt, negative_prompt, ref_image, width, height, num_inference_steps, guidance_scale,

@@ -31,11 +31,13 @@ class IMAGDressing_v1(PipelineBase):
                     negative_prompt_embeds=negative_prompt_embeds, scale=float(first(scale)),
                     keep=controlnet_keep(num_inference_steps, float(first(start)), float(first(end))))
 
-    def open_session(self, slots: int, width: int, height: int, controlnet_conditioning_scale: float = 1.0):
+    def open_session(self, slots: int, width: int, height: int, controlnet_conditioning_scale: float = 1.0, compact: bool = False, widths=None):
         """In-flight batching: a :class:`imagdressing_amd.session.DenoiseSession` with ``slots`` slots at ``width`` x ``height``; every
         request brings its own pose image, ``controlnet_conditioning_scale`` holds for the whole session (the gate is one scalar per
-        launch).  A pipeline built without a ControlNet opens the session of the base pipeline."""
-        return self._open_session(slots, width, height, controlnet_conditioning_scale, with_controlnet=self.controlnet is not None)
+        launch).  A pipeline built without a ControlNet opens the session of the base pipeline.  ``compact`` / ``widths``: run only as
+        many batch rows as requests are running (``_open_session``)."""
+        return self._open_session(slots, width, height, controlnet_conditioning_scale, with_controlnet=self.controlnet is not None,
+                                  compact=compact, widths=widths)
 
     @torch.no_grad()
     def __call__(self, prompt, null_prompt, negative_prompt, ref_image, width, height, num_inference_steps, guidance_scale,

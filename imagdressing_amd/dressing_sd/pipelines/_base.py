@@ -516,12 +516,17 @@ class PipelineBase:
                 dc.clear()          # the stored feature dies with the call, an exception included
 
     # ---- in-flight batching (imagdressing_amd/session.py) ----
-    def _open_session(self, slots: int, width: int, height: int, controlnet_conditioning_scale: float = 1.0, with_controlnet: bool = False):
+    def _open_session(self, slots: int, width: int, height: int, controlnet_conditioning_scale: float = 1.0, with_controlnet: bool = False,
+                      compact: bool = False, widths=None):
         """A denoising session of ``slots`` latent rows at one geometry: requests are submitted at any time, enter a free slot at the
         start of any step, run their own number of steps and leave when done (``session.DenoiseSession``).  DPM-Solver++, Euler, PNDM
-        and DDIM (eta = 0); refused with UniPC, Euler-ancestral and while ``enable_deepcache`` is on; ``enable_step_graph`` is ignored."""
+        and DDIM (eta = 0); refused with UniPC, Euler-ancestral and while ``enable_deepcache`` is on; ``enable_step_graph`` is ignored.
+        ``compact=True``: every step runs a batch only as wide as the running requests need -- the smallest entry of ``widths`` (None:
+        every width 1..slots; else a strictly increasing tuple that ends at ``slots``) -- and a request's bits then depend on the
+        widths it ran under."""
         from ...session import DenoiseSession
-        return DenoiseSession(self, slots, width, height, controlnet_conditioning_scale, with_controlnet=with_controlnet)
+        return DenoiseSession(self, slots, width, height, controlnet_conditioning_scale, with_controlnet=with_controlnet, compact=compact,
+                              widths=widths)
 
     # ---- request-batched calls (RequestLayout) ----
     def _request_count(self, args: Dict[str, Any], per_call: Dict[str, Any], shard_over_ranks: bool) -> int:

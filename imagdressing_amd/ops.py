@@ -1205,19 +1205,23 @@ def sampler_coefs(m_x=0.0, m_e=1.0, z_x=1.0, z_m=0.0, z_h=(), z_n=0.0, b_img=1.0
     return [float(m_x), float(m_e), float(z_x), float(z_m)] + zh + [float(z_n), float(b_img), float(b_noise), float(in_scale), float(int(store))]
 
 
-def _sampler_params(what, z, eps, x_next, guidance, hist, noise, mask, z_img, blend_noise):
-    """the tensor fields of ``imd_sampler_params`` (everything but the coefficients), checked: shared by the two entry points"""
+def _sampler_params(what, z, eps, x_next, guidance, hist, noise, mask, z_img, blend_noise, rows=None):
+    """the tensor fields of ``imd_sampler_params`` (everything but the coefficients), checked: shared by the entry points.  ``rows``:
+    the batch width B of ``imd_sampler_step_rows_at``, whose z / hist / noise / blend operands have ``z.shape[0]`` = slots rows while
+    eps, x_next and the guidance array have B; None: one row count for everything."""
     ensure_device(z.device)
-    B, HW = z.shape[0], z.shape[1]
-    n = B * HW * 4
+    S, HW = z.shape[0], z.shape[1]
+    B = S if rows is None else int(rows)
+    n, nr = S * HW * 4, B * HW * 4
     p = L.SamplerParams()
     p.z, p.eps = _dev(z, torch.float32, "z"), _dev(eps, torch.float32, "eps")
-    if z.numel() != n or eps.numel() != 2 * n:
-        raise L.ImdError(f"{what}: z {tuple(z.shape)} / eps {tuple(eps.shape)}: expected [B, HW, 4] and [2B, HW, 4]")
+    if z.numel() != n or eps.numel() != 2 * nr:
+        raise L.ImdError(f"{what}: z {tuple(z.shape)} / eps {tuple(eps.shape)}: expected [B, HW, 4] and [2B, HW, 4]" if rows is None else
+                         f"{what}: z {tuple(z.shape)} / eps {tuple(eps.shape)}: expected [slots, HW, 4] and [2 x {B}, HW, 4]")
     p.dtype = 0 if x_next is None else _code(x_next, "x_next")
     p.x_next = None if x_next is None else _dev(x_next, x_next.dtype, "x_next")
-    if x_next is not None and x_next.numel() != 4 * n:
-        raise L.ImdError(f"{what}: x_next has {x_next.numel()} elements, expected {4 * n}")
+    if x_next is not None and x_next.numel() != 4 * nr:
+        raise L.ImdError(f"{what}: x_next has {x_next.numel()} elements, expected {4 * nr}")
     p.B, p.HW = B, HW
     if isinstance(guidance, torch.Tensor):
         if guidance.dtype != torch.float32 or guidance.numel() != B or not guidance.is_contiguous():
@@ -1234,8 +1238,8 @@ def _sampler_params(what, z, eps, x_next, guidance, hist, noise, mask, z_img, bl
     for name, t in (("noise", noise), ("z_img", z_img), ("blend_noise", blend_noise)):
         if t is not None and t.numel() != n:
             raise L.ImdError(f"{what}: {name} has {t.numel()} elements, expected {n}")
-    if mask is not None and mask.numel() != B * HW:
-        raise L.ImdError(f"{what}: mask has {mask.numel()} elements, expected {B * HW}")
+    if mask is not None and mask.numel() != S * HW:
+        raise L.ImdError(f"{what}: mask has {mask.numel()} elements, expected {S * HW}")
     p.noise = _opt(noise, torch.float32, "noise")
     p.mask, p.z_img, p.blend_noise = _opt(mask, torch.float32, "mask"), _opt(z_img, torch.float32, "z_img"), _opt(blend_noise, torch.float32, "blend_noise")
     p.coefs, p.store = None, -1
@@ -1290,6 +1294,58 @@ def sampler_step_rows(z, eps, x_next, *, guidance, coef_rows, hist=None, noise=N
                          f"{tuple(getattr(coef_rows, 'shape', ()))}")
     L.check(L.load().imd_sampler_step_rows(C.byref(p), _dev(coef_rows, torch.float32, "coef_rows"), _stream()))
     return z
+
+
+def _coef_rows_ptr(what, coef_rows, B):
+    if (not isinstance(coef_rows, torch.Tensor) or coef_rows.dtype != torch.float32 or coef_rows.numel() != B * SAMPLER_ROW_FLOATS
+            or not coef_rows.is_contiguous()):
+        raise L.ImdError(f"{what}: coef_rows must be a contiguous device fp32 tensor [{B}, {SAMPLER_ROW_FLOATS}] "
+                         f"(ops.sampler_coef_row per row), got {getattr(coef_rows, 'dtype', type(coef_rows))} "
+                         f"{tuple(getattr(coef_rows, 'shape', ()))}")
+    return _dev(coef_rows, torch.float32, "coef_rows")
+
+
+def _row_slot_ptr(what, row_slot, slots):
+    """the device int32 map row -> slot of a compacting session; its length is the batch width B <= slots"""
+    if (not isinstance(row_slot, torch.Tensor) or row_slot.dtype != torch.int32 or row_slot.dim() != 1 or not row_slot.is_contiguous()
+            or not 1 <= row_slot.numel() <= slots):
+        raise L.ImdError(f"{what}: row_slot must be a contiguous device int32 tensor [B] with 1 <= B <= slots = {slots}, got "
+                         f"{getattr(row_slot, 'dtype', type(row_slot))} {tuple(getattr(row_slot, 'shape', ()))}")
+    return _dev(row_slot, torch.int32, "row_slot")
+
+
+def sampler_step_rows_at(z, eps, x_next, *, guidance, coef_rows, row_slot, hist=None, noise=None, mask=None, z_img=None, blend_noise=None):
+    """:func:`sampler_step_rows` through a row -> slot map (``imd_sampler_step_rows_at``; the compacting denoising session).
+    ``row_slot`` [B] int32 on the device: batch row r carries the request of slot ``row_slot[r]`` (-1, or anything outside
+    0..slots-1: an idle row, skipped whole).  By ROW: ``eps`` [2B,HW,4], ``x_next`` [2B,HW,8], ``coef_rows`` [B,16], a ``guidance``
+    tensor [B].  By SLOT: ``z`` [slots,HW,4] (in place), ``hist`` [K,slots,HW,4], ``noise``, ``mask`` / ``z_img`` / ``blend_noise``."""
+    slots = z.shape[0]
+    rs = _row_slot_ptr("sampler_step_rows_at", row_slot, slots)
+    B = row_slot.numel()
+    p = _sampler_params("sampler_step_rows_at", z, eps, x_next, guidance, hist, noise, mask, z_img, blend_noise, rows=B)
+    L.check(L.load().imd_sampler_step_rows_at(C.byref(p), _coef_rows_ptr("sampler_step_rows_at", coef_rows, B), rs, slots, _stream()))
+    return z
+
+
+def session_input_rows(z, row_slot, in_scale_rows, x_in):
+    """``x_in[r] = x_in[B + r] = 16-bit(in_scale_rows[r] * z[row_slot[r]])``, channels 4..7 zero (``imd_session_input_rows``): the
+    UNet input of a session's batch rows from the fp32 latents, with the pack expression of the step's ``x_next``.  z [slots,HW,4]
+    fp32; ``row_slot`` [B] int32 and ``in_scale_rows`` [B] fp32 on the device; ``x_in`` [2B,HW,8] 16-bit.  Rows whose slot is outside
+    0..slots-1 keep their bytes."""
+    ensure_device(z.device)
+    if z.dim() != 3 or z.shape[2] != 4:
+        raise L.ImdError(f"session_input_rows: z {tuple(z.shape)}: expected [slots, HW, 4]")
+    slots, HW = z.shape[0], z.shape[1]
+    zp = _dev(z, torch.float32, "z")
+    rs = _row_slot_ptr("session_input_rows", row_slot, slots)
+    B = row_slot.numel()
+    if not isinstance(in_scale_rows, torch.Tensor) or in_scale_rows.numel() != B:
+        raise L.ImdError(f"session_input_rows: in_scale_rows must be a device fp32 tensor of {B} values")
+    if not isinstance(x_in, torch.Tensor) or x_in.numel() != 2 * B * HW * 8:
+        raise L.ImdError(f"session_input_rows: x_in has {getattr(x_in, 'numel', lambda: 0)()} elements, expected {2 * B * HW * 8} ([2 x {B}, {HW}, 8])")
+    L.check(L.load().imd_session_input_rows(zp, rs, _dev(in_scale_rows, torch.float32, "in_scale_rows"), _dev(x_in, x_in.dtype, "x_in"),
+                                            B, slots, HW, _code(x_in, "x_in"), _stream()))
+    return x_in
 
 
 # ---------------------------------------------------------------------------------------------

@@ -6,15 +6,23 @@ runs its own schedule (its own step count, its own position in it) and leaves wh
 UNet forward (plus ControlNet) over all 2 x slots rows of the CFG batch and one fused step launch (``imd_sampler_step_rows``) that
 gives every latent row its own coefficients, its own history slots and its own "this row is not running" flag.
 
+Two kinds of index.  A SLOT is the home of a request's per-latent state -- the fp32 latent ``z[S, HW, 4]`` and the history
+``hist[K, S, HW, 4]``; slots are taken lowest free index first and these buffers never move.  A ROW is a position in the batch the
+forward runs: at width B the batch is [cond rows 0..B-1 ; uncond rows B..2B-1].  By default the width is always ``slots`` and row =
+slot: an under-full session pays for its idle rows (tools/session_bench.py measures how much).  With ``compact=True`` the width is
+the smallest entry of the ``widths`` ladder that holds the running requests; when it changes the step REPACKS (the running slots take
+rows 0, 1, ... in ascending slot order and their rows of every batch buffer are rewritten from what the request keeps, the UNet input
+from the fp32 latent by ``imd_session_input_rows``), otherwise rows stay where they are.  The step launch then goes through the device
+map row -> slot (``imd_sampler_step_rows_at``).  A forward at another batch width may be dispatched to other tile configurations, so
+with ``compact=True`` a request's bits depend on the sequence of widths it ran under; the default session is unchanged bit for bit.
+
 Two layers, so that the logic is testable without a GPU:
 
 * :class:`SessionPlan` -- pure Python: slot allocation (lowest free index first), the FIFO queue, one scheduler instance /
-  :class:`~imagdressing_amd.scheduler.SamplerHistory` / position per request, and per step one 16-float coefficient row and one
-  timestep per slot.
-* :class:`DenoiseSession` -- the device state: fixed-address buffers for every slot, admission (prompt encoding, the garment UNet at
-  batch 1, in-place writes of the slot's rows), the step, tickets.
-
-The session always runs all slots: an under-full session pays for its idle rows (tools/session_bench.py measures how much).
+  :class:`~imagdressing_amd.scheduler.SamplerHistory` / position per request, the width and the row of every slot, and per step one
+  16-float coefficient row and one timestep per slot and per row.
+* :class:`DenoiseSession` -- the device state: fixed-address buffers for every slot and, at capacity, for every row (one view object
+  per width and buffer), admission (prompt encoding, the garment UNet at batch 1, in-place writes of the row), the step, tickets.
 """
 from __future__ import annotations
 
@@ -77,7 +85,7 @@ def check_request(*, size, width=None, height=None, num_inference_steps, guidanc
 # ---- the plan ----
 class PlanRun:
     """One latent row's run: its own scheduler instance (``set_timesteps(n)``), history bookkeeping and position."""
-    __slots__ = ("scheduler", "ring", "timesteps", "steps", "i", "slot", "payload")
+    __slots__ = ("scheduler", "ring", "timesteps", "steps", "i", "slot", "row", "in_scale", "ready", "payload")
 
     def __init__(self, scheduler, num_inference_steps: int, payload=None):
         sch = copy.copy(scheduler)          # the class and configuration of the pipeline's scheduler; set_timesteps rebinds, never mutates
@@ -93,6 +101,9 @@ class PlanRun:
             self.ring = SamplerHistory(0)
         self.i = 0
         self.slot: Optional[int] = None
+        self.row: Optional[int] = None          # its position in the batch the forward runs (== slot unless the plan compacts)
+        self.in_scale = self.first_input_scale()          # what its current UNet input was scaled with: coefficient [11] of its last step
+        self.ready = False          # for the plan's caller: what an admission has to set up (device state) is in place
         self.payload = payload
 
     @property
@@ -111,29 +122,74 @@ class PlanRun:
     def next_coefs(self) -> List[float]:
         """the 13 coefficients of step ``i`` -- and the history bookkeeping advances"""
         row = self.scheduler.plan(self.i) if self.affine else ddim_row(self.scheduler, self.timesteps[self.i])
-        return self.ring.coefs(row)
+        coefs = self.ring.coefs(row)
+        self.in_scale = coefs[11]
+        return coefs
 
 
 class PlanStep:
     """What one step launches: ``rows`` [slots][16] floats, ``timesteps`` [slots] (None for a free slot), ``running`` = (slot, run,
-    position) of every row that takes this step, ``finished`` = the runs for which it is the last."""
-    __slots__ = ("rows", "timesteps", "running", "finished")
+    position) of every row that takes this step, ``finished`` = the runs for which it is the last.  And the same step seen by batch
+    ROW: ``width`` rows ran, row r carried slot ``row_slot[r]`` (-1: idle) with the coefficient row ``coef_rows[r]`` and the timestep
+    ``row_timesteps[r]``; ``repack`` = the rows were laid out anew before this step.  A plan that does not compact has width =
+    slots, row r = slot r and never repacks."""
+    __slots__ = ("rows", "timesteps", "running", "finished", "width", "row_slot", "repack", "coef_rows", "row_timesteps")
 
-    def __init__(self, rows, timesteps, running, finished):
+    def __init__(self, rows, timesteps, running, finished, width=None, row_slot=None, repack=False, coef_rows=None, row_timesteps=None):
         self.rows, self.timesteps, self.running, self.finished = rows, timesteps, running, finished
+        self.width = len(rows) if width is None else width
+        self.row_slot = list(range(len(rows))) if row_slot is None else row_slot
+        self.repack = repack
+        self.coef_rows = rows if coef_rows is None else coef_rows
+        self.row_timesteps = timesteps if row_timesteps is None else row_timesteps
+
+
+class PlanLayout:
+    """The batch of the coming step: ``width`` rows, ``rows`` [width] = the run of each row or None, ``repack`` = every running
+    request was given a new row (ascending slot order), ``placed`` = the runs that entered a row without one (none at a repack)."""
+    __slots__ = ("width", "rows", "repack", "placed")
+
+    def __init__(self, width, rows, repack, placed):
+        self.width, self.rows, self.repack, self.placed = width, rows, repack, placed
+
+
+def check_widths(slots: int, widths) -> tuple:
+    """the ladder of batch widths of a compacting plan: None = every width 1..slots, else strictly increasing ints in 1..slots
+    that end at slots"""
+    S = int(slots)
+    if widths is None:
+        return tuple(range(1, S + 1))
+    try:
+        w = tuple(widths)
+    except TypeError:
+        raise ValueError(f"widths must be None or a tuple of ints, got {widths!r}") from None
+    if not w or any(isinstance(v, bool) or not isinstance(v, int) for v in w):
+        raise ValueError(f"widths must be a non-empty tuple of ints, got {widths!r}")
+    if any(not 1 <= v <= S for v in w) or any(a >= b for a, b in zip(w, w[1:])) or w[-1] != S:
+        raise ValueError(f"widths must be strictly increasing, within 1..{S} and end at slots = {S}, got {widths!r}")
+    return w
 
 
 class SessionPlan:
-    def __init__(self, slots: int, scheduler):
+    def __init__(self, slots: int, scheduler, compact: bool = False, widths=None):
         if int(slots) < 1:
             raise ValueError(f"slots must be >= 1, got {slots}")
         check_scheduler(scheduler)
         self.S = int(slots)
+        self.compact = bool(compact)
+        if widths is not None and not self.compact:
+            raise ValueError("widths is the ladder of a compacting session: pass compact=True with it")
+        self.widths = check_widths(self.S, widths) if self.compact else (self.S,)
         self.scheduler = scheduler
         self.K = int(getattr(scheduler, "history", 0)) if hasattr(scheduler, "plan") else 0          # history slots of the device buffer
         self._slots: List[Optional[PlanRun]] = [None] * self.S
         self.queue = deque()
         self.idle_row = ops.sampler_coef_row(ops.sampler_coefs(), active=False)
+        # the batch: width 0 until the first step lays it out (nothing to move: that is no repack)
+        self.width = 0 if self.compact else self.S
+        self._rows: List[Optional[PlanRun]] = [] if self.compact else [None] * self.S
+        self._laid: Optional[PlanLayout] = None
+        self.repacks = 0
 
     def submit(self, num_inference_steps: int, payload=None) -> PlanRun:
         run = PlanRun(self.scheduler, num_inference_steps, payload)
@@ -154,15 +210,59 @@ class SessionPlan:
         return taken
 
     def cancel(self, run: PlanRun) -> None:
-        """drop a run that has not finished (a failed admission): its slot is free again"""
+        """drop a run that has not finished (a failed admission): its slot is free again (and its row, had it one).  Call it
+        before ``layout()`` of the step, which counts the running slots."""
         if run in self.queue:
             self.queue.remove(run)
         if run.slot is not None and self._slots[run.slot] is run:
             self._slots[run.slot] = None
+        if run.row is not None and run.row < len(self._rows) and self._rows[run.row] is run:
+            self._rows[run.row] = None
+        run.row = None
+
+    def required_width(self) -> int:
+        """the smallest entry of the ladder that holds every running slot"""
+        n = self.running
+        return next(w for w in self.widths if w >= n)
+
+    def layout(self) -> PlanLayout:
+        """Give every running slot its batch row for the coming step (after ``admit``; ``next_rows`` calls it if the caller did
+        not).  The width is the smallest ladder entry >= the running slots.  If it differs from the current width the step REPACKS:
+        the running slots take rows 0, 1, ... in ascending slot order, the rest of the width idles.  Otherwise every row stays where
+        it is and each slot without a row (just admitted) takes the lowest idle one.  A plan that does not compact keeps row = slot."""
+        if self._laid is not None:
+            return self._laid
+        live = [r for r in self._slots if r is not None]
+        if not self.compact:
+            placed = [r for r in live if r.row is None]
+            for r in placed:
+                r.row = r.slot
+                self._rows[r.slot] = r
+            self._laid = PlanLayout(self.S, list(self._rows), False, placed)
+            return self._laid
+        need = self.required_width()
+        repack = need != self.width and self.width != 0
+        if need != self.width:
+            self.width = need
+            self._rows = [None] * need
+            if repack:
+                self.repacks += 1
+                for r in live:
+                    r.row = None
+        placed = []
+        for r in live:                                   # ascending slot order
+            if r.row is None:
+                r.row = self._rows.index(None)
+                self._rows[r.row] = r
+                placed.append(r)
+        self._laid = PlanLayout(need, list(self._rows), repack, [] if repack else placed)
+        return self._laid
 
     def next_rows(self) -> PlanStep:
         """The coming step: one coefficient row and one timestep per slot (inactive rows for free slots).  Every running request
-        advances; one that takes its last step is reported finished and its slot is free from the next step on."""
+        advances; one that takes its last step is reported finished and its slot (and batch row) is free from the next step on."""
+        lay = self.layout()
+        self._laid = None
         rows, ts, running, finished = [], [], [], []
         for s, run in enumerate(self._slots):
             if run is None:
@@ -176,10 +276,20 @@ class SessionPlan:
             if run.done:
                 finished.append(run)
                 self._slots[s] = None
-        return PlanStep(rows, ts, running, finished)
+                self._rows[run.row] = None
+        if not self.compact:
+            return PlanStep(rows, ts, running, finished)
+        row_slot = [-1 if r is None else r.slot for r in lay.rows]
+        return PlanStep(rows, ts, running, finished, width=lay.width, row_slot=row_slot, repack=lay.repack,
+                        coef_rows=[list(self.idle_row) if s < 0 else rows[s] for s in row_slot],
+                        row_timesteps=[None if s < 0 else ts[s] for s in row_slot])
 
     def slot_runs(self) -> List[Optional[PlanRun]]:
         return list(self._slots)
+
+    def row_runs(self) -> List[Optional[PlanRun]]:
+        """the run of every batch row (the rows of the last layout, minus the requests that have finished since)"""
+        return list(self._rows)
 
     @property
     def running(self) -> int:
@@ -242,18 +352,46 @@ class _Request:
 
 
 # ---- the device state ----
-class DenoiseSession:
-    """``pipe.open_session(slots=S, width=W, height=H)``; a context manager.  See the module docstring."""
+class _WidthViews:
+    """The first 2B (or B) rows of every batch buffer, as ONE object per buffer for the life of the session: the processors' K / V
+    caches and the ControlNet's conditioning cache are keyed on the identity, address and version of the tensors they are handed
+    (adapter/attention_processor.py::_TensorCache), a fresh view per step would miss them every step."""
 
-    def __init__(self, pipe, slots: int, width: int, height: int, controlnet_conditioning_scale: float = 1.0, with_controlnet: bool = False):
+    def __init__(self, ses: "DenoiseSession", B: int):
+        self.B = B
+        self.x_in = ses.x_in[:2 * B]
+        self.x_flat = self.x_in.view(2 * B, ses.HW, 8)
+        self.mask_rows = ses.mask_rows[:2 * B]
+        self.temb = [t[:2 * B] for t in ses.temb]
+        self.temb_pairs = [t.view(2, B, -1) for t in self.temb]
+        self.ctrl_img = ses.ctrl_img[:2 * B] if ses.ctrl_img is not None else None
+        self.coef_rows = ses.coef_rows[:B]
+        self.guidance_rows = ses.guidance_rows[:B] if ses.guidance_rows is not None else None
+        self.row_slot = ses.row_slot[:B]
+        self.ehs = self.garment = self.cak = None          # with the context buffers, at the first admission
+
+    def bind_context(self, ses: "DenoiseSession"):
+        B = self.B
+        self.ehs = ses.ehs[:2 * B]
+        self.garment = {k: v[:B] for k, v in ses.garment.items()}
+        # sa_pair_layout: garment on for the cond rows [0, B) (weight = the row's image_scale), off for the uncond rows [B, 2B)
+        self.cak = {"sa_hidden_states": self.garment, "sa_batch_mask": self.mask_rows, "sa_pair_layout": True}
+
+
+class DenoiseSession:
+    """``pipe.open_session(slots=S, width=W, height=H, compact=False, widths=None)``; a context manager.  See the module docstring."""
+
+    def __init__(self, pipe, slots: int, width: int, height: int, controlnet_conditioning_scale: float = 1.0, with_controlnet: bool = False,
+                 compact: bool = False, widths=None):
         check_pipeline(pipe)
-        self.plan = SessionPlan(slots, pipe.scheduler)
+        self.plan = SessionPlan(slots, pipe.scheduler, compact=compact, widths=widths)
         self.pipe = pipe
+        self.compact = self.plan.compact
         vsf = pipe.vae_scale_factor
         if int(width) % vsf or int(height) % vsf:
             raise ValueError(f"width x height {width} x {height} must be multiples of {vsf}")
-        self.S, self.width, self.height = int(slots), int(width), int(height)
-        self.h, self.w = self.height // vsf, self.width // vsf
+        self.S, self.image_width, self.image_height = int(slots), int(width), int(height)
+        self.h, self.w = self.image_height // vsf, self.image_width // vsf
         self.HW = self.h * self.w
         self.controlnet = pipe.controlnet if with_controlnet else None
         if with_controlnet and self.controlnet is None:
@@ -262,24 +400,53 @@ class DenoiseSession:
         dev, dt, S = pipe.device, pipe.unet.dtype, self.S
         self.device, self.dtype = dev, dt
         ops.ensure_device(dev)
-        # fixed-address buffers, one row (or CFG pair of rows) per slot.  Zero-filled: the rows of a free slot stay finite
+        # fixed-address buffers.  Per SLOT (the home of a request's state, never moved): z, hist, guidance.  Per batch ROW, allocated
+        # at capacity (width B uses the first 2B or B rows): everything the forward reads.  Zero-filled: idle rows stay finite
         self.z = torch.zeros(S, self.HW, 4, dtype=torch.float32, device=dev)
         self.x_in = torch.zeros(2 * S, self.h, self.w, 8, dtype=dt, device=dev)
         self.hist = torch.zeros(self.plan.K, S, self.HW, 4, dtype=torch.float32, device=dev) if self.plan.K else None
         self.mask_rows = torch.zeros(2 * S, dtype=torch.float32, device=dev)          # [image_scale of the cond rows; 0 for the uncond rows]
         self.guidance = torch.ones(S, dtype=torch.float32, device=dev)
+        self.guidance_rows = torch.ones(S, dtype=torch.float32, device=dev) if self.compact else None
         self.coef_rows = torch.zeros(S, ops.SAMPLER_ROW_FLOATS, dtype=torch.float32, device=dev)
+        self.row_slot = torch.arange(S, dtype=torch.int32, device=dev)
+        self._row_slot_host = list(range(S))
         self.encoders = [m for m in [pipe.unet] + ([self.controlnet] if self.controlnet is not None else []) if hasattr(m, "use_time_embedding")]
         if len(self.encoders) != (2 if self.controlnet is not None else 1):
             raise TypeError("open_session needs the engine UNet / ControlNet (imagdressing_amd.unet): per-row time embeddings")
         self.temb = [torch.zeros(2 * S, e.temb_proj.weight.shape[0], dtype=torch.float32, device=dev) for e in self.encoders]
-        self.ctrl_img = torch.zeros(2 * S, self.height, self.width, 8, dtype=dt, device=dev) if self.controlnet is not None else None
+        self.ctrl_img = torch.zeros(2 * S, self.image_height, self.image_width, 8, dtype=dt, device=dev) if self.controlnet is not None else None
         self.ehs = None                                   # [2S, T, C] text context, [cond; uncond]: allocated at the first admission
         self.garment: Optional[Dict[str, torch.Tensor]] = None          # name -> [S, M_l, C_l]
-        self.cak = None
+        self._views: Dict[int, _WidthViews] = {}          # one per width of the ladder, made at its first use
         self.closed = False
         self.steps_run = 0
+        self.steps_at_width: Dict[int, int] = {}          # width -> steps run at it (at most one entry per ladder width)
+        self._last_width = 0
         self._tickets: List[SessionTicket] = []
+
+    # ---- introspection ----
+    @property
+    def width(self) -> int:
+        """rows of the last step's batch (0 before the first; always ``slots`` unless the session compacts)"""
+        return self._last_width
+
+    @property
+    def rows(self) -> List[Optional[int]]:
+        """slot of every batch row, None for an idle row (the last layout, minus the requests that have finished since)"""
+        self._check_open()
+        return [None if r is None else r.slot for r in self.plan.row_runs()]
+
+    @property
+    def repacks(self) -> int:
+        self._check_open()
+        return self.plan.repacks
+
+    @property
+    def cak(self):
+        """the UNet's cross-attention kwargs at full width (None before the first admission)"""
+        v = self._views.get(self.S) if self._views is not None else None
+        return None if v is None else v.cak
 
     # ---- context manager ----
     def __enter__(self):
@@ -301,7 +468,8 @@ class DenoiseSession:
                 t.error = RuntimeError("the session was closed")
         self._tickets = []
         self.plan = None
-        for name in ("z", "x_in", "hist", "mask_rows", "guidance", "coef_rows", "temb", "ctrl_img", "ehs", "garment", "cak"):
+        for name in ("z", "x_in", "hist", "mask_rows", "guidance", "guidance_rows", "coef_rows", "row_slot", "temb", "ctrl_img", "ehs",
+                     "garment", "_views"):
             setattr(self, name, None)
 
     def _check_open(self):
@@ -319,7 +487,7 @@ class DenoiseSession:
         and ``image_scale`` per request) and return its ticket.  Never blocks and launches nothing: the request is admitted at the
         start of the first ``step()`` in which a slot is free.  ``num_images_per_prompt`` = n takes n slots."""
         self._check_open()
-        check_request(size=(self.width, self.height), width=width, height=height, num_inference_steps=num_inference_steps,
+        check_request(size=(self.image_width, self.image_height), width=width, height=height, num_inference_steps=num_inference_steps,
                       guidance_scale=guidance_scale, image_scale=image_scale, eta=eta, shard_over_ranks=shard_over_ranks,
                       control_guidance_start=control_guidance_start, control_guidance_end=control_guidance_end,
                       num_images_per_prompt=num_images_per_prompt, slots=self.S)
@@ -330,7 +498,7 @@ class DenoiseSession:
             raise ValueError("pose_image: this session was opened on the pipeline without a ControlNet")
         if latents is not None and tuple(latents.shape) != (n, 4, self.h, self.w):
             raise ValueError(f"latents {tuple(latents.shape)}: this session's requests have latents {(n, 4, self.h, self.w)} "
-                             f"({self.width} x {self.height}, one geometry per session)")
+                             f"({self.image_width} x {self.image_height}, one geometry per session)")
         req = _Request(prompt=prompt, null_prompt=null_prompt, negative_prompt=negative_prompt, ref_image=ref_image, ref_clip_image=ref_clip_image,
                        pose_image=pose_image, guidance_scale=float(guidance_scale), image_scale=float(image_scale), n=n, generator=generator,
                        output_type=output_type, clip_skip=clip_skip, prompt_embeds=prompt_embeds, negative_prompt_embeds=negative_prompt_embeds,
@@ -358,10 +526,11 @@ class DenoiseSession:
         req.features = {k: v.clone() for k, v in pipe._garment_features(ref_lat, cloth_tokens).items()}
         req.pose = None
         if self.controlnet is not None:
-            img, hw = pipe._image_tensor(as_batch(req.pose_image, "pose_image"), dev, normalize=False, size=(self.height, self.width),
+            img, hw = pipe._image_tensor(as_batch(req.pose_image, "pose_image"), dev, normalize=False, size=(self.image_height, self.image_width),
                                          multiple=pipe.vae_scale_factor, layout="nhwc8")
-            if tuple(hw) != (self.height, self.width) or img.shape[0] != 1:
-                raise ValueError(f"pose_image gives {img.shape[0]} image(s) of {tuple(hw)}: a session request has one of {(self.height, self.width)}")
+            if tuple(hw) != (self.image_height, self.image_width) or img.shape[0] != 1:
+                raise ValueError(f"pose_image gives {img.shape[0]} image(s) of {tuple(hw)}: a session request has one of "
+                                 f"{(self.image_height, self.image_width)}")
             req.pose = img if (img.dim() == 4 and img.shape[-1] == 8 and img.dtype == dt) else nchw_to_nhwc8(img.to(dev), dt)
         lat = req.latents
         if lat is None:
@@ -373,15 +542,22 @@ class DenoiseSession:
         S, dev, dt = self.S, self.device, self.dtype
         self.ehs = torch.zeros(2 * S, req.pe.shape[1], req.pe.shape[2], dtype=dt, device=dev)
         self.garment = {k: torch.zeros(S, v.shape[1], v.shape[2], dtype=v.dtype, device=dev) for k, v in req.features.items()}
-        # sa_pair_layout: garment on for the cond rows [0, S) (weight = the slot's image_scale), off for the uncond rows [S, 2S)
-        self.cak = {"sa_hidden_states": self.garment, "sa_batch_mask": self.mask_rows, "sa_pair_layout": True}
+        for v in self._views.values():
+            v.bind_context(self)
+
+    def _view(self, B: int) -> _WidthViews:
+        v = self._views.get(B)
+        if v is None:
+            v = self._views[B] = _WidthViews(self, B)
+            if self.ehs is not None:
+                v.bind_context(self)
+        return v
 
     def _admit(self, run: PlanRun):
-        """Write the slot's rows of every buffer in place (nothing outside the slot is touched).  The writes bump the tensors'
-        versions, so the processors' step-invariant K / V caches and the ControlNet's conditioning embedding refresh for ALL slots
-        on the next forward."""
+        """What an admission does before the run has a batch row: prepare the request (once), check that it fits the session's
+        context buffers, write the SLOT's latent and compute the time-embedding table of its schedule."""
         ticket, j = run.payload
-        req, s, S = ticket._request, run.slot, self.S
+        req, s = ticket._request, run.slot
         if not req.prepared:
             self._prepare(req, run)
         if self.ehs is None:
@@ -391,39 +567,54 @@ class DenoiseSession:
         for k, v in req.features.items():
             if k not in self.garment or tuple(v.shape[1:]) != tuple(self.garment[k].shape[1:]):
                 raise ValueError(f"garment features of layer {k}: {tuple(v.shape)} does not fit this session's {tuple(self.garment.get(k, v).shape)}")
-        z0 = req.z0[j]
-        self.z[s].copy_(z0)
-        scale = run.first_input_scale()
-        zin = (z0 if scale == 1.0 else z0 * scale).view(self.h, self.w, 4)
-        self.x_in[s, ..., :4] = zin
-        self.x_in[S + s, ..., :4] = zin
-        self.ehs[s].copy_(req.pe[0])
-        self.ehs[S + s].copy_(req.ne[0])
-        for k, v in req.features.items():
-            self.garment[k][s].copy_(v[0])
-        self.mask_rows[s] = req.image_scale
+        self.z[s].copy_(req.z0[j])
         self.guidance[s] = req.guidance_scale
-        if self.ctrl_img is not None:
-            self.ctrl_img[s].copy_(req.pose[0])
-            self.ctrl_img[S + s].copy_(req.pose[0])
         ts = torch.tensor([float(t) for t in run.timesteps], dtype=torch.float32).to(self.device)
         req.temb[j] = [e._time_embed_rows(ts) for e in self.encoders]          # the request's whole schedule, once
+
+    def _write_row(self, v: _WidthViews, run: PlanRun):
+        """Write batch row ``run.row`` (and its uncond twin B + row) of every buffer the forward reads, in place, from what the request
+        keeps while it runs; nothing outside the row is touched.  The writes bump the tensors' versions, so the processors'
+        step-invariant K / V caches and the ControlNet's conditioning embedding refresh for ALL rows on the next forward."""
+        req, r, B = run.payload[0]._request, run.row, v.B
+        v.ehs[r].copy_(req.pe[0])
+        v.ehs[B + r].copy_(req.ne[0])
+        for k, f in req.features.items():
+            v.garment[k][r].copy_(f[0])
+        v.mask_rows[r] = req.image_scale
+        if self.compact:
+            v.guidance_rows[r] = req.guidance_scale
+        if v.ctrl_img is not None:
+            v.ctrl_img[r].copy_(req.pose[0])
+            v.ctrl_img[B + r].copy_(req.pose[0])
+
+    def _write_inputs(self, v: _WidthViews, runs: List[PlanRun]):
+        """the UNet input of the rows of ``runs`` from their slots' fp32 latents, both CFG halves (``imd_session_input_rows``; the
+        other rows keep their bytes): for a fresh request in_scale is its first step's, for a moved one its last step's"""
+        rs, sc = [-1] * v.B, [1.0] * v.B
+        for run in runs:
+            rs[run.row], sc[run.row] = run.slot, run.in_scale
+        ops.session_input_rows(self.z, torch.tensor(rs, dtype=torch.int32).to(self.device), torch.tensor(sc, dtype=torch.float32).to(self.device),
+                               v.x_flat)
 
     # ---- the step ----
     @torch.no_grad()
     def step(self) -> List[SessionTicket]:
-        """Admit from the queue, run ONE UNet (+ ControlNet) forward over all slots and ONE fused step launch; returns the tickets
-        that finished, decoded for their own ``output_type``."""
+        """Admit from the queue, run ONE UNet (+ ControlNet) forward over the batch -- all slots, or with ``compact=True`` as many rows
+        as the width ladder needs for the running ones -- and ONE fused step launch; returns the tickets that finished, decoded for
+        their own ``output_type``."""
         self._check_open()
         check_pipeline(self.pipe)
         with ops.tuning_scope(**(getattr(self.pipe, "_tuning", None) or {})):
             return self._step()
 
     def _step(self) -> List[SessionTicket]:
-        pipe, S = self.pipe, self.S
-        for run in self.plan.admit():
+        pipe = self.pipe
+        self.plan.admit()
+        for run in [r for r in self.plan.slot_runs() if r is not None and not r.ready]:          # (also what a failed step left waiting)
             try:
                 self._admit(run)
+                run.ready = True
             except BaseException as e:
                 ticket = run.payload[0]
                 ticket.error = e
@@ -433,25 +624,43 @@ class DenoiseSession:
                 raise
         if not self.plan.running:
             return []
+        lay = self.plan.layout()
+        B = lay.width
+        v = self._view(B)
+        moved = [r for r in lay.rows if r is not None] if lay.repack else lay.placed
+        if lay.repack:
+            v.mask_rows.zero_()
+        for run in moved:
+            self._write_row(v, run)
+        if moved:
+            self._write_inputs(v, moved)
         st = self.plan.next_rows()
-        for s, run, i in st.running:          # each slot's time-embedding row, the same in both CFG halves
+        for s, run, i in st.running:          # each row's time-embedding row, the same in both CFG halves
             ticket, j = run.payload
-            for buf, table in zip(self.temb, ticket._request.temb[j]):
-                buf.view(2, S, -1)[:, s].copy_(table[i])
-        self.coef_rows.copy_(torch.tensor(st.rows, dtype=torch.float32))
-        pipe.set_scale(1.0)                   # the slots' image scales ride in the sa_batch_mask rows
+            for pair, table in zip(v.temb_pairs, ticket._request.temb[j]):
+                pair[:, run.row].copy_(table[i])
+        v.coef_rows.copy_(torch.tensor(st.coef_rows, dtype=torch.float32))
+        if self.compact and st.row_slot != self._row_slot_host[:B]:
+            v.row_slot.copy_(torch.tensor(st.row_slot, dtype=torch.int32))
+            self._row_slot_host[:B] = st.row_slot
+        pipe.set_scale(1.0)                   # the rows' image scales ride in the sa_batch_mask rows
         try:
-            for e, buf in zip(self.encoders, self.temb):
+            for e, buf in zip(self.encoders, v.temb):
                 e.use_time_embedding(buf)
             down = mid = None
             if self.controlnet is not None:
-                down, mid = self.controlnet.forward_nhwc(self.x_in, 0, self.ehs, self.ctrl_img, self.control_scale)
-            eps = pipe.unet.forward_nhwc(self.x_in, 0, self.ehs, self.cak, down, mid, cfg_pair=True)
+                down, mid = self.controlnet.forward_nhwc(v.x_in, 0, v.ehs, v.ctrl_img, self.control_scale)
+            eps = pipe.unet.forward_nhwc(v.x_in, 0, v.ehs, v.cak, down, mid, cfg_pair=True)
         finally:
             for e in self.encoders:
                 e.clear_time_embeddings()
-        ops.sampler_step_rows(self.z, eps, self.x_in.view(2 * S, self.HW, 8), guidance=self.guidance, coef_rows=self.coef_rows, hist=self.hist)
+        if self.compact:
+            ops.sampler_step_rows_at(self.z, eps, v.x_flat, guidance=v.guidance_rows, coef_rows=v.coef_rows, row_slot=v.row_slot, hist=self.hist)
+        else:
+            ops.sampler_step_rows(self.z, eps, v.x_flat, guidance=self.guidance, coef_rows=v.coef_rows, hist=self.hist)
         self.steps_run += 1
+        self._last_width = B
+        self.steps_at_width[B] = self.steps_at_width.get(B, 0) + 1
         finished = []
         for run in st.finished:
             ticket, j = run.payload
@@ -477,4 +686,4 @@ class DenoiseSession:
         return self.plan.free_slots
 
 
-__all__ = ["SessionPlan", "PlanRun", "PlanStep", "DenoiseSession", "SessionTicket", "check_scheduler", "check_pipeline", "check_request"]
+__all__ = ["SessionPlan", "PlanRun", "PlanStep", "PlanLayout", "check_widths", "DenoiseSession", "SessionTicket", "check_scheduler", "check_pipeline", "check_request"]

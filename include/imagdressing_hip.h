@@ -576,6 +576,23 @@ int imd_sampler_step(const imd_sampler_params* p, void* stream);
 #define IMD_SAMPLER_ROW_FLOATS 16   /* per latent row: [0..12] the coefficient block in imd_sampler_params.coefs order,
                                        [13] active (0: the row is skipped), [14..15] reserved, 0 */
 int imd_sampler_step_rows(const imd_sampler_params* p, const float* coef_rows /* DEVICE [B][16] fp32 */, void* stream);
+/* imd_sampler_step_rows of a COMPACTING session: the forward ran p->B <= slots batch rows, and batch row r carries the request that lives
+ * in slot row_slot[r].  Addressed by ROW (p->B of them): eps [2B, HW, 4], x_next [2B, HW, 8] (rows r and B + r), coef_rows and
+ * p->guidance_rows [B].  Addressed by SLOT (`slots` of them): z, hist (history plane k starts at hist + k slots HW), noise, mask, z_img
+ * and blend_noise.  A row whose coefficient block is inactive, or whose slot is outside [0, slots) (-1 marks an idle row), is skipped
+ * whole -- no load, no store -- so the kernel stays inside its buffers whatever the device map holds; slots that no row names keep
+ * their bytes.  Two rows must not name one slot.  The per-pixel arithmetic is the one copy imd_sampler_step_rows uses: with row_slot the
+ * identity and slots == B the two launches are bit-identical.  Errors without launching: those of imd_sampler_step_rows, row_slot
+ * NULL or not 4-byte aligned, slots < 1, B > slots. */
+int imd_sampler_step_rows_at(const imd_sampler_params* p, const float* coef_rows /* DEVICE [B][16] fp32 */,
+                             const int* row_slot /* DEVICE [B] */, int slots, void* stream);
+/* The UNet input of a session's batch rows from the fp32 latents: x_in[r] = x_in[B + r] = 16-bit(in_scale_rows[r] z[row_slot[r]]),
+ * channels 4..7 zero, with the pack expression of the step's x_next -- given the in_scale of a request's last step (coefficient [11])
+ * it reproduces that step's x_next bit for bit.  z [slots, HW, 4] fp32, x_in [2B, HW, 8] 16-bit, row_slot and in_scale_rows DEVICE [B].
+ * Rows with a slot outside [0, slots) are skipped.  Errors without launching: a null pointer, B or HW < 1, slots < 1, B > slots, z or
+ * x_in not 16-byte aligned, row_slot or in_scale_rows not 4-byte aligned, an unknown dtype. */
+int imd_session_input_rows(const float* z, const int* row_slot, const float* in_scale_rows, void* x_in, int B, int slots, int HW,
+                           int dtype_code, void* stream);
 
 /* Pillow-exact resize (+ crop, normalise, layout) of uint8 images on the device; see imd_image_resample_params.  Errors without
  * launching: a foreign struct size, null src / out, C outside {1, 3}, an incomplete table or a skipped axis whose size changes, a

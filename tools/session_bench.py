@@ -2,6 +2,7 @@
 weights, fp16 and bf16.  Prints one JSON line and, with --out, writes it to a file (profiles/session_bench.json).
 
     python tools/session_bench.py [--reps 5] [--trace-reps 5] [--dtypes fp16,bf16] [--out profiles/session_bench.json]
+    python tools/session_bench.py --compact [--ladder 1,2,4] [--out profiles/session_compact_bench.json]      (see the end of this text)
 
 Steady state, INTERLEAVED repeats (one run of every arm per round, the order rotating), median [min - max]:
   * ``batched_call_step``: ms per step of the request-batched call of four requests -- THE BAR (a step callback synchronises and reads
@@ -14,7 +15,14 @@ Arrival trace: 24 requests with seeded exponential inter-arrival times at 0.5x a
 median solo call); a request becomes visible when the wall clock passes its arrival time.  Served (a) by solo calls, FIFO, (b) by
 request-batched calls of whatever has arrived (up to 4) each time the GPU is free, (c) by one session with 4 slots (steps are launched
 one ahead of the GPU, so the host work of a step overlaps the kernels of the previous one like it does inside a pipeline call).  Per
-arm: images/s from the first arrival to the last result, mean and worst latency from arrival to latents."""
+arm: images/s from the first arrival to the last result, mean and worst latency from arrival to latents.
+
+``--compact`` measures the compacting session (``open_session(..., compact=True)``) beside all of the above in ONE run, the arms interleaved
+the same way: ms per step with 1, 2, 3, 4 of 4 slots running for the default session, the compacting one and the compacting one on the
+``--ladder`` widths; a ``slots=1`` default session (what a width-1 step should cost) and the request-batched call of 1, 2, 3, 4 requests
+(what a width-n step should cost); a step that repacks 2 -> 1 against the plain width-1 steps behind it; and the two arrival traces served
+by solo calls / batched calls / the default session / the compacting session / the compacting session on the ladder.  The figures of
+profiles/session_bench.json for the arms that file has are copied beside the new ones (``parent_commit``)."""
 import argparse
 import json
 import os
@@ -82,10 +90,10 @@ def batched_call_steps(pipe, inp):
     return [marks[i] - marks[i - 1] for i in range(1, len(marks))]
 
 
-def session_steps(pipe, inp, running):
+def session_steps(pipe, inp, running, slots=4, **open_kw):
     """plain steps of a 4-slot session with ``running`` requests of STEPS steps (the admitting step left out)"""
     out = []
-    with pipe.open_session(slots=4, width=inp.width, height=inp.height) as ses:
+    with pipe.open_session(slots=slots, width=inp.width, height=inp.height, **open_kw) as ses:
         for k in range(running):
             ses.submit(**inp.submit_kwargs(k))
         ses.step()
@@ -94,6 +102,36 @@ def session_steps(pipe, inp, running):
             ses.step()
             out.append(sync_clock() - t0)
     return out
+
+
+def batched_call_steps_of(pipe, inp, R):
+    marks = []
+
+    def cb(i, t, z):
+        marks.append(sync_clock())
+    pipe(callback=cb, **inp.call_kwargs(range(R)))
+    return [marks[i] - marks[i - 1] for i in range(1, len(marks))]
+
+
+def repack_step(pipe, inp, **open_kw):
+    """-> (seconds of the step that repacks 2 -> 1 -- the survivor's rows re-laid, the step-invariant caches refreshed --, median plain
+    width-1 step behind it) in a compacting 4-slot session: two requests of STEPS and STEPS / 2 steps"""
+    with pipe.open_session(slots=4, width=inp.width, height=inp.height, compact=True, **open_kw) as ses:
+        ses.submit(**inp.submit_kwargs(0))
+        ses.submit(**inp.submit_kwargs(1, steps=STEPS // 2))
+        for _ in range(STEPS // 2):
+            ses.step()
+        assert ses.width == 2 and ses.rows == [0, None]
+        t0 = sync_clock()
+        ses.step()
+        t = sync_clock() - t0
+        assert ses.width == 1 and ses.repacks == 1
+        plain = []
+        for _ in range(STEPS // 2 - 2):
+            t0 = sync_clock()
+            ses.step()
+            plain.append(sync_clock() - t0)
+        return t, statistics.median(plain)
 
 
 def admission(pipe, inp):
@@ -157,9 +195,9 @@ def serve_batched(pipe, inp, arr):
     return summary(arr, fin)
 
 
-def serve_session(pipe, inp, arr):
+def serve_session(pipe, inp, arr, **open_kw):
     fin, k, tickets = [None] * len(arr), 0, {}
-    with pipe.open_session(slots=4, width=inp.width, height=inp.height) as ses:
+    with pipe.open_session(slots=4, width=inp.width, height=inp.height, **open_kw) as ses:
         t0, prev = time.perf_counter(), None
         while any(f is None for f in fin):
             if not tickets and k < len(arr):
@@ -181,6 +219,102 @@ def serve_session(pipe, inp, arr):
     return summary(arr, fin)
 
 
+def rotate(items, rep):
+    k = rep % len(items)
+    return items[k:] + items[:k]
+
+
+def compact_results(pipe, inp, args, ladder):
+    """the --compact measurement of one element type -> dict(steady_state_ms=, arrival_trace=)"""
+    for R in (1, 2, 3, 4):                                      # warm-up: kernel selection and workspaces of every batch width
+        pipe(**inp.call_kwargs(range(R)))
+        session_steps(pipe, inp, R, compact=True)
+    session_steps(pipe, inp, 4)
+    session_steps(pipe, inp, 1, slots=1)
+    arms = {"slots1_session_step": lambda: session_steps(pipe, inp, 1, slots=1)}
+    for n in (1, 2, 3, 4):
+        arms[f"session_step_{n}of4"] = lambda n=n: session_steps(pipe, inp, n)
+        arms[f"compact_step_{n}of4"] = lambda n=n: session_steps(pipe, inp, n, compact=True)
+        arms[f"batched_call_step_{n}"] = lambda n=n: batched_call_steps_of(pipe, inp, n)
+    arms["ladder_step_3of4"] = lambda: session_steps(pipe, inp, 3, compact=True, widths=ladder)
+    names = list(arms) + ["repack"]
+    per_run = {a: [] for a in arms}
+    rep_t, rep_extra, solo_t = [], [], []
+    for rep in range(args.reps):
+        for a in rotate(names, rep):
+            if a == "repack":
+                t, plain = repack_step(pipe, inp)
+                rep_t.append(t)
+                rep_extra.append(t - plain)
+            else:
+                per_run[a].append(statistics.median(arms[a]()))
+        t0 = sync_clock()
+        pipe(**inp.call_kwargs([rep]))
+        solo_t.append(sync_clock() - t0)
+    steady = {a: spread(v) for a, v in per_run.items()}
+    steady["repacking_step_2to1"] = spread(rep_t)
+    steady["repack_over_plain_step"] = spread(rep_extra)
+    steady["solo_call"] = spread(solo_t)
+    steady["ratio_compact_1of4_vs_slots1"] = round(steady["compact_step_1of4"]["median"] / steady["slots1_session_step"]["median"], 4)
+    for n in (1, 2, 3, 4):
+        steady[f"ratio_compact_{n}of4_vs_batched_call_{n}"] = round(steady[f"compact_step_{n}of4"]["median"] / steady[f"batched_call_step_{n}"]["median"], 4)
+    print("# steady: " + json.dumps(steady), file=sys.stderr, flush=True)
+    solo = statistics.median(solo_t)
+    traces = {}
+    servers = [("solo_fifo", serve_solo), ("batched_calls", serve_batched), ("session_4_slots", serve_session),
+               ("compact_session_4_slots", lambda p, i, a: serve_session(p, i, a, compact=True)),
+               ("compact_session_ladder", lambda p, i, a: serve_session(p, i, a, compact=True, widths=ladder))]
+    for load in (0.5, 0.9):
+        runs = {n: [] for n, _ in servers}
+        for rep in range(args.trace_reps):
+            arr = arrivals(args.requests, solo / load, seed=1000 + rep)          # the same trace for every server of a repeat
+            for n, fn in rotate(servers, rep):
+                runs[n].append(fn(pipe, inp, arr))
+        block = {}
+        for n, rs in runs.items():
+            block[n] = dict(images_per_s=spread([r["images_per_s"] for r in rs], 1.0), mean_latency_ms=spread([r["mean_latency_ms"] for r in rs], 1.0),
+                            worst_latency_ms=spread([r["worst_latency_ms"] for r in rs], 1.0))
+        traces[f"load_{load}"] = dict(mean_inter_arrival_ms=round(1e3 * solo / load, 3), **block)
+        print(f"# load {load}: " + json.dumps(block), file=sys.stderr, flush=True)
+    return dict(steady_state_ms=steady, arrival_trace=traces)
+
+
+def parent_figures(dname):
+    """the arms profiles/session_bench.json has in common with the --compact run (measured before sessions could compact)"""
+    try:
+        with open(os.path.join(ROOT, "profiles", "session_bench.json")) as f:
+            old = json.load(f)["results"][dname]
+    except (OSError, KeyError, ValueError):
+        return None
+    keep = ("session_step_4of4", "session_step_1of4", "batched_call_step", "solo_call")
+    return dict(steady_state_ms={k: old["steady_state_ms"][k] for k in keep if k in old["steady_state_ms"]},
+                arrival_trace={load: {n: v[n]["mean_latency_ms"] for n in ("solo_fifo", "batched_calls", "session_4_slots") if n in v}
+                               for load, v in old["arrival_trace"].items()})
+
+
+def main_compact(args):
+    import bench
+    from imagdressing_amd import ops
+    dev = torch.device("cuda", 0)
+    ladder = tuple(int(w) for w in args.ladder.split(","))
+    res = dict(tool="session_bench --compact", width=args.width, height=args.height, sampler=f"dpmpp_2m_{STEPS}", reps=args.reps,
+               trace_reps=args.trace_reps, trace_requests=args.requests, ladder=list(ladder), device=torch.cuda.get_device_name(dev),
+               note="synthetic weights; every arm of a repeat in one process, interleaved, the order rotating; median [min - max]", results={})
+    for dname in args.dtypes.split(","):
+        dtype = torch.float16 if dname == "fp16" else torch.bfloat16
+        pipe = bench.build_pipeline(dev, dtype, 0)
+        pipe.scheduler = scheduler()
+        inp = Inputs(args.width, args.height, dev, dtype)
+        res["results"][dname] = dict(compact_results(pipe, inp, args, ladder), parent_commit=parent_figures(dname))
+        del pipe
+        ops.clear_workspaces()
+        torch.cuda.empty_cache()
+    print(json.dumps(res), flush=True)
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write(json.dumps(res, indent=1) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--width", type=int, default=512)
@@ -190,7 +324,11 @@ def main():
     ap.add_argument("--requests", type=int, default=24)
     ap.add_argument("--dtypes", default="fp16,bf16")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--compact", action="store_true", help="measure the compacting session beside the other arms (a different result file)")
+    ap.add_argument("--ladder", default="1,2,4", help="--compact: the width ladder of the laddered arms")
     args = ap.parse_args()
+    if args.compact:
+        return main_compact(args)
     import bench
     from imagdressing_amd import ops
     dev = torch.device("cuda", 0)
