@@ -521,6 +521,7 @@ int imd_launch_attention(const AttnParams& p_in, hipStream_t s) {
     if (p.dtype != IMD_DTYPE_BF16 && p.dtype != IMD_DTYPE_F16) return imd_set_error("attention: unknown dtype %d", p.dtype);
     if (p.causal && (p.k2 != nullptr || p.L1 != p.N)) return imd_set_error("attention: the causal mask needs a single key set with L1 == N");
     const bool h = p.dtype == IMD_DTYPE_F16;
+    if (p.D == 512) return imd_launch_attention_d512(p, s);      // (attention_d512.hip refuses, by name, every optional form below)
     if ((p.phase2_rows != 0) != (p.phase2_out != nullptr)) return imd_set_error("attention: phase2_rows and phase2_out go together");
     if (p.phase2_rows != 0) {           // phase-split launch (ABI v9): the generic kernel only
         if (!imd_attention_phase_split_supported(p.D) || p.k2 == nullptr || p.scale2 == nullptr || p.causal || p.proj_w != nullptr || p.out_dup != nullptr ||
@@ -584,6 +585,6 @@ int imd_launch_attention(const AttnParams& p_in, hipStream_t s) {
             }
 #endif
             return h ? launch_attn<true, 160, 1, 1, 2, false, 2>(p, s) : launch_attn<false, 160, 1, 1, 2, false, 2>(p, s);
-        default: return imd_set_error("attention: unsupported head dim %d (supported: 40, 64, 80, 160)", p.D);
+        default: return imd_set_error("attention: unsupported head dim %d (supported: 40, 64, 80, 160, and 512 with one key set and no causal / proj_w / out_dup / phase2_out / k_pad_one)", p.D);
     }
 }

@@ -72,6 +72,7 @@ bool imd_text_xattn320_supported_of(const imd_xattn_params& p);                 
 int imd_launch_text_xattn320(const imd_xattn_params& p, hipStream_t s);
 int imd_launch_attention(const AttnParams& p, hipStream_t s);
 int imd_launch_attention_d40(const AttnParams& p, int variant, hipStream_t s);
+int imd_launch_attention_d512(const AttnParams& p, hipStream_t s);                               // attention_d512.hip: one key set, no mask / fused forms
 int imd_launch_attention_fp8(const AttnParams& p, int eq, int ek, int ev, hipStream_t s);                       // attention_d40_fp8.hip
 int imd_launch_attn_quantize_fp8(const bf16_t* src, unsigned char* dst, int kind, long rows_or_groups, int LP, int exp2_scale,
                                  float pad_val, int dtype, hipStream_t s);   // attention_d40_fp8.hip: the quantiser of its operands

@@ -13,10 +13,13 @@ Everything runs through the hot path's own kernels: NHWC 16-bit activations, `im
 fused nearest-2x upsample, bottom/right-only padding for the encoder's stride-2 convs, bias / residual epilogues),
 `imd_groupnorm` (+SiLU).  The mid block's single-head d = 512 attention is two GEMMs around `imd_softmax_rows`
 (fp32 scores, the reference's upcast softmax): S = Q K^T / sqrt(C), P = softmax(S), O = P V with V^T written by the
-projection's head-split epilogue.  No fallback: CPU tensors raise.
+projection's head-split epilogue -- or, past the 16384 tokens `imd_softmax_rows` takes and wherever
+`enable_flash_attention()` asks for it, ONE `imd_attention` launch at head dim 512 for the whole batch with no N x N
+workspace (`mid_attention_route`).  No fallback: CPU tensors raise.
 """
 from __future__ import annotations
 
+import math
 import types
 from typing import Dict, Optional
 
@@ -102,8 +105,22 @@ class _Resnet:
         return self.conv2(h, res=x if self.shortcut is None else self.shortcut(x))
 
 
+SOFTMAX_ROWS_MAX_TOKENS = 16384       # imd_softmax_rows: at most 256 x 64 columns
+FLASH_CHANNELS = 512                  # the head dim attention_d512.hip is written for (the SD1.5 mid block)
+
+
+def mid_attention_route(tokens: int, channels: int, flash: bool) -> str:
+    """How the mid block's attention over `tokens` latent positions of `channels` channels runs: "flash" (one imd_attention launch at head
+    dim 512, no N x N workspace) or "gemm" (per image S = Q K^T, imd_softmax_rows, O = P V: the default, limited to 16384 tokens).
+    "flash" iff the width is 512 and (the switch is on or the three launches cannot take the size)."""
+    if channels == FLASH_CHANNELS and (flash or tokens > SOFTMAX_ROWS_MAX_TOKENS):
+        return "flash"
+    return "gemm"
+
+
 class _MidAttention:
     """Single head, d = C: GroupNorm -> q / k / v projections (biased) -> softmax(q k^T / sqrt(C)) v -> out proj + residual."""
+    flash = False          # AutoencoderKL.enable_flash_attention()
 
     def __init__(self, sd, p, ch, groups, device, dtype):
         self.norm = NormParams(sd, f"{p}.group_norm", device)
@@ -118,6 +135,8 @@ class _MidAttention:
         N = H * W
         dt = x.dtype
         h = ops.group_norm(x, self.norm.weight, self.norm.bias, groups=self.groups, eps=1e-6, silu=False).view(B * N, Cc)
+        if mid_attention_route(N, Cc, self.flash) == "flash":
+            return self._flash(x, h, B, N, Cc).view(B, H, W, Cc)
         q = self.to_q(h)
         k = self.to_k(h)
         NP = ops.pad64(N)
@@ -134,6 +153,21 @@ class _MidAttention:
             ops.softmax_rows(scores, out=probs)
             ops.conv_gemm(probs, vt[b, 0], M=N, N=Cc, Cin=NP, out=o[b * N:(b + 1) * N])                   # O = P V
         return self.to_out(o, res=x.view(B * N, Cc)).view(B, H, W, Cc)
+
+    def _flash(self, x, h, B, N, Cc):
+        """One launch for the batch: with a single head, [B * N, C] row-major IS the kernel's Q [B, 1, N, C] / K [B, 1, N, C] layout, so the
+        projections are handed over as they are; Q carries the softmax scale and log2(e) (the kernel runs on exp2)."""
+        dt = x.dtype
+        q = ops.conv_gemm(h, self.to_q.weight, M=B * N, N=Cc, Cin=Cc, bias=self.to_q.bias, out_scale=Cc ** -0.5 * math.log2(math.e))
+        k = self.to_k(h)
+        NP = ops.pad64(N)
+        vt = torch.zeros((B, 1, Cc, NP), dtype=dt, device=x.device) if NP != N else torch.empty((B, 1, Cc, NP), dtype=dt, device=x.device)
+        # V^T [B, 1, C, NP] straight from the projection's epilogue, as on the three-launch route
+        ops.conv_gemm(h, self.to_v.weight, M=B * N, N=Cc, Cin=Cc, Hout=N, Wout=1, Hin=N, Win=1, bias=self.to_v.bias,
+                      heads=dict(C=Cc, H=1, D=Cc, dests=[(vt, 1, Cc, NP, 1.0)]))
+        o = torch.empty((B * N, Cc), dtype=dt, device=x.device)
+        ops.attention(q, k, vt, o, B=B, H=1, N=N, D=Cc, L1=N, L1P=NP)          # no N x N workspace, no loop over the batch
+        return self.to_out(o, res=x.view(B * N, Cc))
 
 
 class _Mid:
@@ -164,6 +198,7 @@ class DiagonalGaussian:
 
 class AutoencoderKL(PretrainedMixin):
     _config_keys = ("block_out_channels", "layers_per_block", "latent_channels", "norm_num_groups", "scaling_factor")
+    use_flash_attention = False
 
     def __init__(self, state_dict: Dict[str, torch.Tensor], config: Optional[dict] = None, device="cuda", dtype=bf16):
         device = torch.device(device)
@@ -235,6 +270,15 @@ class AutoencoderKL(PretrainedMixin):
 
     def disable_slicing(self):
         self.use_slicing = False
+
+    def enable_flash_attention(self, flag: bool = True):
+        """Run the mid blocks' attention (encoder and decoder) as one flash launch at every size (512-channel mid blocks only; off by default:
+        the three-launch route and its bits stay the default up to 16384 latent tokens, sizes beyond take the flash launch either way)."""
+        self.use_flash_attention = bool(flag)
+        self.e_mid.attn.flash = self.d_mid.attn.flash = self.use_flash_attention
+
+    def disable_flash_attention(self):
+        self.enable_flash_attention(False)
 
     # ---- compute ------------------------------------------------------------------------------------------------
     def encode_nhwc(self, x8: torch.Tensor) -> torch.Tensor:

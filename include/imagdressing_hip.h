@@ -136,6 +136,10 @@ typedef struct imd_conv_gemm_params {
 } imd_conv_gemm_params;
 #define IMD_SPLITK_COUNTERS 16384
 
+/* Head dims of imd_attention: 40, 64, 80, 160 (attention.hip / attention_d40.hip: every field below) and 512 (attention_d512.hip, the VAE mid
+ * block's single-head attention as one flash launch: DPK = DPV = 512, any B / H / N / L1, kv1_bdiv >= 1, out_ld >= H * 512, bf16 and fp16).
+ * At head dim 512 the optional forms are REFUSED by name, without a launch: a second key set (k2 / v2t / scale2), causal, proj_w, out_dup,
+ * phase2_out / phase2_rows and k_pad_one must all be NULL / 0. */
 typedef struct imd_attn_params {
     uint32_t struct_bytes; /* sizeof(imd_attn_params) in the caller's view (ABI v8); checked on entry */
     const uint16_t* q;   /* [B, H, N, DPK], pre-scaled by D^-1/2 * log2(e) */
