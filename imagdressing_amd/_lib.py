@@ -206,6 +206,9 @@ SYMBOLS = {
     "imd_concat2_gn_stats": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
                                        C.c_void_p, C.c_int, C.c_void_p]),
     "imd_groupnorm_parts": (C.c_int, [C.c_int, C.c_int, C.c_int]),
+    "imd_concat2_freeu": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                    C.c_void_p, C.c_float, C.c_float, C.c_int, C.c_void_p]),
+    "imd_concat2_freeu_parts": (C.c_int, [C.c_int] * 6),
     "imd_f32_to_16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_long, C.c_int, C.c_void_p]),
 }
 

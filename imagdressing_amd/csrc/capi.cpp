@@ -371,6 +371,13 @@ int imd_concat2(const uint16_t* a, int Ca, const uint16_t* b, int Cb, const uint
 
 int imd_groupnorm_parts(int B, int HW, int C) { return imd_groupnorm_parts_of(B, HW, C); }
 
+int imd_concat2_freeu(const uint16_t* a, int Ca, const uint16_t* b, int Cb, const uint16_t* b_add, uint16_t* out, int B, int H, int W, int b_batch, int G,
+                      float* part, float backbone_scale, float skip_scale, int dtype, void* stream) {
+    return imd_launch_concat2_freeu(a, Ca, b, Cb, b_add, out, B, H, W, b_batch, G, part, backbone_scale, skip_scale, dtype, (hipStream_t)stream);
+}
+
+int imd_concat2_freeu_parts(int B, int H, int W, int Ca, int Cb, int G) { return imd_concat2_freeu_parts_of(B, H, W, Ca, Cb, G); }
+
 int imd_concat2_gn_stats(const uint16_t* a, int Ca, const uint16_t* b, int Cb, const uint16_t* b_add, uint16_t* out, int B, int HW, int b_B, int G,
                          float* partial, int dtype, void* stream) {
     IMD_REQUIRE(a && b && out && partial, "concat2 + statistics: null pointer");

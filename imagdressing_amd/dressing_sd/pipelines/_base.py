@@ -157,6 +157,24 @@ class PipelineBase:
         self._deepcache = None
         return self
 
+    def enable_freeu(self, s1: float, s2: float, b1: float, b2: float):
+        """Opt in to FreeU (Si et al., CVPR 2024; diffusers' ``pipe.enable_freeu(s1, s2, b1, b2)``) on the denoising UNet
+        (``UNet2DConditionModel.enable_freeu``): the backbone's lower channel half is scaled by ``b1`` / ``b2`` and the skips are
+        low-pass re-weighted by ``s1`` / ``s2`` at the first two up blocks, inside the launch that concatenates them.  No extra steps,
+        no weights; the garment UNet and the ControlNet are untouched.  The result CHANGES (that is the point); what it does to image
+        quality with real checkpoints is unmeasured, hence off by default.  All four values must be finite and > 0.  Composes with
+        ``enable_step_graph`` (every call captures its own step), DeepCache, sessions and request batches."""
+        if self.unet is None:
+            raise ValueError("enable_freeu: this pipeline has no unet")
+        self.unet.enable_freeu(s1, s2, b1, b2)
+        return self
+
+    def disable_freeu(self):
+        if self.unet is None:
+            raise ValueError("disable_freeu: this pipeline has no unet")
+        self.unet.disable_freeu()
+        return self
+
     def enable_device_image_io(self, flag: bool = True):
         """Opt in to image input and output on the GPU (``imagdressing_amd.image.DeviceImageProcessor``): PIL / uint8 pose, control,
         inpainting and mask images are resized (Pillow's Lanczos filter, bit for bit), scaled and laid out by ``imd_image_resample``

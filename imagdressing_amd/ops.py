@@ -1547,6 +1547,41 @@ def concat_channels(a: torch.Tensor, b: torch.Tensor, b_add: Optional[torch.Tens
     return out
 
 
+FREEU_COUNTER = {"launches": 0}          # imd_concat2_freeu launches of this process (tests count the full / shallow forwards of DeepCache with it)
+
+
+def concat_channels_freeu(a: torch.Tensor, b: torch.Tensor, b_add: Optional[torch.Tensor], H: int, W: int, backbone_scale: float,
+                          skip_scale: float, gn_stats_groups: int = 0) -> torch.Tensor:
+    """:func:`concat_channels` with FreeU (diffusers 0.24 ``apply_freeu``) applied to its operands, in the same single launch
+    (``imd_concat2_freeu``): ``a`` [B, H, W, Ca] has its lower channel half multiplied by ``backbone_scale``; the skip ``b (+ b_add)``
+    [B, H, W, Cb] goes through ``fourier_filter(threshold=1, scale=skip_scale)`` per (image, channel) map, computed in fp32 in its closed
+    form (seven sums per map, no FFT).  ``gn_stats_groups`` = G: the GroupNorm(G) statistics of the stored tensor ride on the result
+    (``_imd_gn_stats``) under the conditions of :func:`concat_channels`; elsewhere the launch writes none and :func:`group_norm` runs its
+    own pass.  Both scales 1.0 store :func:`concat_channels`' bits."""
+    ensure_device(a.device)
+    dt = a.dtype
+    H, W = int(H), int(W)
+    if a.dim() != 4 or b.dim() != 4 or tuple(a.shape[:3]) != tuple(b.shape[:3]) or tuple(a.shape[1:3]) != (H, W):
+        raise L.ImdError(f"concat_channels_freeu: operands must be [B, {H}, {W}, C] with one B (the skip holds every image), got {tuple(a.shape)} and {tuple(b.shape)}")
+    if b_add is not None and tuple(b_add.shape) != tuple(b.shape):
+        raise L.ImdError(f"concat_channels_freeu: b_add {tuple(b_add.shape)} must have the skip's shape {tuple(b.shape)}")
+    B, Ca, Cb = int(a.shape[0]), int(a.shape[-1]), int(b.shape[-1])
+    out = torch.empty((B, H, W, Ca + Cb), dtype=dt, device=a.device)
+    lib = L.load()
+    G = int(gn_stats_groups)
+    part, nparts = None, 0
+    if G and FUSED_CONCAT_STATS and FUSED_GN_STATS and (Ca + Cb) % G == 0:
+        nparts = lib.imd_concat2_freeu_parts(B, H, W, Ca, Cb, G)
+        if nparts > 0:
+            part = torch.empty((B, nparts, G, 2), dtype=torch.float32, device=a.device)
+    L.check(lib.imd_concat2_freeu(_dev(a, dt, "a"), Ca, _dev(b, dt, "b"), Cb, _opt(b_add, dt, "b_add"), out.data_ptr(), B, H, W, B, G if part is not None else 0,
+                                  None if part is None else part.data_ptr(), float(backbone_scale), float(skip_scale), _code(a, "a"), _stream()))
+    FREEU_COUNTER["launches"] += 1
+    if part is not None:
+        out._imd_gn_stats = (part, nparts, G)
+    return out
+
+
 def repeat_batch(x: torch.Tensor, times: int = 2) -> torch.Tensor:
     """cat([x] * times, dim=0) for a contiguous NHWC tensor (strided 2-D copies)."""
     ensure_device(x.device)

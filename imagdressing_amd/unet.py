@@ -654,6 +654,26 @@ class UNet2DConditionModel(_Encoder):
         return cls(random_state_dict(unet_param_shapes(cfg), seed, device=device), cfg, device, dtype)
 
     # ------------------------------------------------------------------------------------
+    def enable_freeu(self, s1: float, s2: float, b1: float, b2: float):
+        """FreeU (Si et al., CVPR 2024; the surface of diffusers 0.24 ``UNet2DConditionModel.enable_freeu``): before the skip concatenation
+        of every resnet of ``up_blocks[0]`` the lower channel half of the backbone is multiplied by ``b1`` and the skip goes through
+        ``fourier_filter(threshold=1, scale=s1)``; ``up_blocks[1]`` takes ``(b2, s2)``.  Both run inside the concatenation's launch
+        (``ops.concat_channels_freeu``); every other concatenation, and everything while the switch is off, is unchanged bit for bit.
+        Two stated differences to diffusers: all four values must be finite and > 0 (diffusers silently treats a 0 as "off"), and the
+        filter is always computed in fp32 (diffusers runs the FFT in half precision on power-of-two maps).  Needs at least three up blocks."""
+        vals = dict(s1=s1, s2=s2, b1=b1, b2=b2)
+        for k, v in vals.items():
+            if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v) or v <= 0:
+                raise ValueError(f"enable_freeu: {k} must be a finite number > 0, got {v!r}")
+        if len(self.up_blocks) < 3:
+            raise ValueError(f"enable_freeu: FreeU acts on up_blocks[0] and up_blocks[1]; this UNet has {len(self.up_blocks)} up blocks")
+        self._freeu = ((float(b1), float(s1)), (float(b2), float(s2)))
+        return self
+
+    def disable_freeu(self):
+        self._freeu = None
+        return self
+
     def forward_nhwc(self, x: torch.Tensor, timestep, encoder_hidden_states: torch.Tensor,
                      cross_attention_kwargs: Optional[dict] = None,
                      down_block_additional_residuals: Optional[List[torch.Tensor]] = None,
@@ -706,6 +726,7 @@ class UNet2DConditionModel(_Encoder):
             # the skips are s0 .. s(depth - 1): layers cut .. L of the last up block pop exactly those, around the stored F_d
             h = feat
             up_blocks = self.up_blocks[-1:]
+        freeu = getattr(self, "_freeu", None)          # ((b1, s1), (b2, s2)) while enable_freeu is on
         for blk in up_blocks:
             for j, r in enumerate(blk.resnets):
                 if cut is not None and blk is self.up_blocks[-1]:
@@ -715,7 +736,13 @@ class UNet2DConditionModel(_Encoder):
                         deepcache.store(h, x)          # a copy: the activation itself is reused by later launches
                 s = skips.pop()
                 c = None if ctrl is None else ctrl[len(skips)]
-                h = ops.concat_channels(h, s, c, gn_stats_groups=r.groups)          # cat([x, skip (+ ControlNet residual)]) + the statistics of the resnet's norm1
+                fu = None
+                if freeu is not None and (blk is self.up_blocks[0] or blk is self.up_blocks[1]):
+                    fu = freeu[0] if blk is self.up_blocks[0] else freeu[1]          # (backbone scale, skip scale) of this block
+                if fu is None:
+                    h = ops.concat_channels(h, s, c, gn_stats_groups=r.groups)          # cat([x, skip (+ ControlNet residual)]) + the statistics of the resnet's norm1
+                else:                                                                   # ... with FreeU's two operations on the operands, same launch count
+                    h = ops.concat_channels_freeu(h, s, c, h.shape[1], h.shape[2], fu[0], fu[1], gn_stats_groups=r.groups)
                 h = r(h, temb_all)
                 if blk.attentions:
                     h = blk.attentions[j](h, ehs, cak)

@@ -642,6 +642,22 @@ int imd_concat2_gn_stats(const uint16_t* a, int Ca, const uint16_t* b, int Cb, c
                          float* partial, int dtype, void* stream);
 /* number of per-image statistic partials imd_groupnorm's own statistics launch (and imd_concat2_gn_stats) writes for this tensor; 0 if C % 8 */
 int imd_groupnorm_parts(int B, int HW, int C);
+/* FreeU (Si et al., CVPR 2024; diffusers 0.24 apply_freeu / fourier_filter) inside the skip concatenation of an up block, one launch:
+ *   out[.., c]      = round16(a[.., c] * backbone_scale)                 c < Ca / 2        (one product, one rounding)
+ *   out[.., c]      = a[.., c]                                           Ca / 2 <= c < Ca
+ *   out[.., Ca + c] = round16(filter(v)[.., c]),  v = round16(b + b_add) (imd_concat2's sum; v = b when b_add is NULL)
+ * for NHWC tensors a [B, H, W, Ca], b and b_add [B, H, W, Cb].  filter = fourier_filter(threshold 1, scale skip_scale) per (image, channel)
+ * map in its closed form -- y = v + (skip_scale - 1) / (H W) * sum over the waves (mean; row 2 pi n / H when H > 1; column 2 pi m / W when
+ * W > 1; the diagonal 2 pi (n / H + m / W) when both) of A cos(phi) + B sin(phi), A = sum v cos(phi), B = sum v sin(phi) -- in fp32, no FFT.
+ * part non-NULL: also the GroupNorm(G) (sum, sum of squares) partials of the ROUNDED values stored, as
+ * part[B][imd_concat2_freeu_parts(B, H, W, Ca, Cb, G)][G][2] fp32, the layout imd_groupnorm_params.nparts takes; every float is written.
+ * Refused without a launch: a null a, b or out; Ca % 16 or Cb % 8; B, H or W < 1; H or W > 256 (the twiddle table); B > 65535; b_batch != B
+ * (every image filters its own skip); (Ca + Cb) % G, G > 64 or 5 .. 7 channels per group with part given; an unknown dtype; a, b, b_add or out
+ * not 16-byte aligned (part: 4-byte); a scale that is not finite or <= 0.  skip_scale = 1 and backbone_scale = 1 store imd_concat2's bits. */
+int imd_concat2_freeu(const uint16_t* a, int Ca, const uint16_t* b, int Cb, const uint16_t* b_add, uint16_t* out, int B, int H, int W, int b_batch, int G,
+                      float* part, float backbone_scale, float skip_scale, int dtype, void* stream);
+/* pure query: statistic partials per (image, group) imd_concat2_freeu writes for this tensor; 0 = it cannot produce the statistics (pass part = NULL) */
+int imd_concat2_freeu_parts(int B, int H, int W, int Ca, int Cb, int G);
 /* fp32 -> 16-bit element cast (round to nearest even). */
 int imd_f32_to_16(const float* a, uint16_t* out, long n, int dtype, void* stream);
 
