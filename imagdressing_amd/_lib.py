@@ -119,6 +119,22 @@ class SamplerParams(_Sized):
     ]
 
 
+class UnipcParams(_Sized):
+    _fields_ = [("struct_bytes", C.c_uint32),
+        ("z", C.c_void_p), ("eps", C.c_void_p), ("x_next", C.c_void_p), ("hist", C.c_void_p),
+        ("B", C.c_int), ("HW", C.c_int), ("K", C.c_int), ("dtype", C.c_int),
+        ("guidance", C.c_float), ("guidance_rows", C.c_void_p),
+        ("m_x", C.c_float), ("m_e", C.c_float), ("s_x", C.c_float), ("s_m", C.c_float),
+        ("s_h", C.c_float * 4),
+        ("z_s", C.c_float), ("z_m", C.c_float),
+        ("z_h", C.c_float * 4),
+        ("b_img", C.c_float), ("b_noise", C.c_float), ("in_scale", C.c_float),
+        ("store_m", C.c_int), ("store_s", C.c_int),
+        ("mask", C.c_void_p), ("z_img", C.c_void_p), ("blend_noise", C.c_void_p),
+        ("coefs", C.c_void_p),
+    ]
+
+
 class ImageResampleParams(_Sized):
     _fields_ = [("struct_bytes", C.c_uint32),
         ("src", C.c_void_p), ("src_row_stride", C.c_int64), ("src_img_stride", C.c_int64), ("out", C.c_void_p), ("tmp", C.c_void_p),
@@ -190,6 +206,9 @@ SYMBOLS = {
     "imd_sampler_step": (C.c_int, [C.POINTER(SamplerParams), C.c_void_p]),
     "imd_sampler_step_rows": (C.c_int, [C.POINTER(SamplerParams), C.c_void_p, C.c_void_p]),
     "imd_sampler_step_rows_at": (C.c_int, [C.POINTER(SamplerParams), C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "imd_unipc_step": (C.c_int, [C.POINTER(UnipcParams), C.c_void_p]),
+    "imd_unipc_step_rows": (C.c_int, [C.POINTER(UnipcParams), C.c_void_p, C.c_void_p]),
+    "imd_unipc_step_rows_at": (C.c_int, [C.POINTER(UnipcParams), C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "imd_session_input_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "imd_image_resample": (C.c_int, [C.POINTER(ImageResampleParams), C.c_void_p]),
     "imd_image_resample_form": (C.c_int, [C.POINTER(ImageResampleParams)]),

@@ -307,6 +307,27 @@ int imd_sampler_step_rows_at(const imd_sampler_params* p, const float* coef_rows
     return imd_launch_sampler_step_rows_at(*p, coef_rows, row_slot, slots, (hipStream_t)stream);
 }
 
+int imd_unipc_step(const imd_unipc_params* p, void* stream) {
+    IMD_REQUIRE(p != nullptr, "unipc_step: null params");
+    IMD_REQUIRE_SIZE(p, "unipc_step");
+    IMD_REQUIRE(p->z && p->eps, "unipc_step: null pointer");
+    return imd_launch_unipc_step(*p, (hipStream_t)stream);
+}
+
+int imd_unipc_step_rows(const imd_unipc_params* p, const float* coef_rows, void* stream) {
+    IMD_REQUIRE(p != nullptr, "unipc_step_rows: null params");
+    IMD_REQUIRE_SIZE(p, "unipc_step_rows");
+    IMD_REQUIRE(p->z && p->eps, "unipc_step_rows: null pointer");
+    return imd_launch_unipc_step_rows(*p, coef_rows, (hipStream_t)stream);
+}
+
+int imd_unipc_step_rows_at(const imd_unipc_params* p, const float* coef_rows, const int* row_slot, int slots, void* stream) {
+    IMD_REQUIRE(p != nullptr, "unipc_step_rows_at: null params");
+    IMD_REQUIRE_SIZE(p, "unipc_step_rows_at");
+    IMD_REQUIRE(p->z && p->eps, "unipc_step_rows_at: null pointer");
+    return imd_launch_unipc_step_rows_at(*p, coef_rows, row_slot, slots, (hipStream_t)stream);
+}
+
 int imd_session_input_rows(const float* z, const int* row_slot, const float* in_scale_rows, void* x_in, int B, int slots, int HW,
                            int dtype_code, void* stream) {
     return imd_launch_session_input_rows(z, row_slot, in_scale_rows, (bf16_t*)x_in, B, slots, HW, dtype_code, (hipStream_t)stream);

@@ -14,6 +14,7 @@ typedef imd_groupnorm_params GroupNormParams;
 typedef imd_layernorm_params LayerNormParams;
 typedef imd_ddim_params DdimParams;
 typedef imd_sampler_params SamplerParams;
+typedef imd_unipc_params UnipcParams;
 typedef imd_image_resample_params ImageResampleParams;
 typedef imd_image_pack_params ImagePackParams;
 typedef imd_image_overlay_params ImageOverlayParams;
@@ -99,6 +100,9 @@ int imd_launch_ddim_cfg_step_rows(const DdimParams& p, const float* guidance, hi
 int imd_launch_sampler_step(const SamplerParams& p, hipStream_t s);
 int imd_launch_sampler_step_rows(const SamplerParams& p, const float* coef_rows, hipStream_t s);
 int imd_launch_sampler_step_rows_at(const SamplerParams& p, const float* coef_rows, const int* row_slot, int slots, hipStream_t s);
+int imd_launch_unipc_step(const UnipcParams& p, hipStream_t s);                                      // unipc_step.hip
+int imd_launch_unipc_step_rows(const UnipcParams& p, const float* coef_rows, hipStream_t s);
+int imd_launch_unipc_step_rows_at(const UnipcParams& p, const float* coef_rows, const int* row_slot, int slots, hipStream_t s);
 int imd_launch_session_input_rows(const float* z, const int* row_slot, const float* in_scale_rows, bf16_t* x_in, int B, int slots, int HW,
                                   int dtype, hipStream_t s);
 int imd_launch_image_resample(const ImageResampleParams& p, hipStream_t s);          // image.hip

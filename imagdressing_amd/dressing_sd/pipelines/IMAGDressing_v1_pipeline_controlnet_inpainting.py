@@ -8,7 +8,7 @@ import torch
 
 from ...unet import nchw_to_nhwc8
 from ._base import (PipelineBase, RefSAttnProcessor2_0, RequestLayout, StableDiffusionPipelineOutput, as_batch, controlnet_keep, first,
-                    min_guidance, per_call_value, randn_tensor, set_scale_by_type, to_image_tensor)
+                    min_guidance, per_call_value, randn_tensor, set_scale_by_type, to_image_tensor, unipc_fused)
 
 
 def _pil_images(value, name: str, mode: Optional[str]) -> list:
@@ -281,7 +281,8 @@ class IMAGDressing_v1(PipelineBase):
         if latents is not None or float(strength) == 1.0:
             lat = (noise if latents is None else latents).to(device=device, dtype=torch.float32) * self.scheduler.init_noise_sigma
         else:
-            t0 = self.scheduler.timesteps[t_start * getattr(self.scheduler, "order", 1)]          # (unrounded: Euler's may be fractional)
+            # (unrounded: Euler's may be fractional; the fused UniPC step makes one UNet call per entry whatever its solver order)
+            t0 = self.scheduler.timesteps[t_start * (1 if unipc_fused(self.scheduler) else getattr(self.scheduler, "order", 1))]
             il = image_latents.to(device=device, dtype=torch.float32)
             if il.shape[0] != B:                                              # one person image shared, or one per request (request-major rows)
                 il = il.expand(B, -1, -1, -1) if il.shape[0] == 1 else RequestLayout(R, num_images_per_prompt).expand(il, "image / image_latents")

@@ -30,6 +30,7 @@ import torch
 from ... import ops
 from ...adapter.attention_processor import (IPAttnProcessor2_0, LoRAIPAttnProcessor2_0, LoraRefSAttnProcessor2_0,
                                             RefSAttnProcessor2_0)
+from ...scheduler import unipc_fused
 from ...unet import DeepCache, nchw_to_nhwc8
 
 bf16 = torch.bfloat16
@@ -114,7 +115,8 @@ class PipelineBase:
     def enable_step_graph(self, flag: bool = True):
         """Opt in to HIP-graph replay of the denoising step (see ``denoise``) -- DDIM and the deterministic samplers of the fused
         sampler step (DPM-Solver++, Euler, PNDM): same kernels, same arithmetic, one graph launch per step instead of ~500 kernel
-        launches.  Worth it where the loop is host-bound (small batches); ignored for UniPC, Euler-ancestral, step callbacks, traces,
+        launches.  Worth it where the loop is host-bound (small batches); ignored for UniPC (unless ``scheduler.enable_fused_step()``:
+        its one-launch step replays like the others), Euler-ancestral, step callbacks, traces,
         per-step ControlNet gating and while ``enable_deepcache`` is on."""
         self._step_graph = bool(flag)
         if not flag:
@@ -316,7 +318,9 @@ class PipelineBase:
 
         The scheduler decides the step: DDIM (``imd_ddim_cfg_step``), a scheduler with a ``plan`` method -- DPM-Solver++, Euler,
         Euler-ancestral, PNDM (scheduler.py) -- one ``imd_sampler_step`` per step with the same guidance / blend / graph-replay
-        features (Euler-ancestral draws its per-step noise like ``eta`` > 0 below and runs eagerly), or UniPC (``step_guided``).
+        features (Euler-ancestral draws its per-step noise like ``eta`` > 0 below and runs eagerly), or UniPC: ``step_guided`` (three
+        ``imd_lincomb`` launches, one guidance scale, no blend, no replay) unless ``scheduler.enable_fused_step()``, which gives it
+        one ``imd_unipc_step`` per step and every feature of the ``plan`` samplers.
         ``eta`` > 0 (DDIM only; other schedulers ignore it, like ``prepare_extra_step_kwargs``, IMAGDressing_v1_pipeline.py:102-119):
         the stochastic step, noise per step = ``variance_noise[i]`` [B, 4, h, w] or a draw of that shape in the UNet's element type
         from ``generator`` (what ``DDIMScheduler.step`` does with the reference's ``noise_pred``).
@@ -334,8 +338,9 @@ class PipelineBase:
         if lay.requests < 1 or lay.rows != B:
             raise ValueError(f"{B} latent rows cannot be split into {requests} requests")
         gs = per_request_floats("guidance_scale", guidance_scale, lay.requests)
-        multistep = hasattr(self.scheduler, "step_guided")        # UniPC: latent updates are host-computed linear combinations
-        fused = not multistep and hasattr(self.scheduler, "plan")  # DPM-Solver++ / Euler / Euler-ancestral / PNDM: one imd_sampler_step per step
+        unipc = unipc_fused(self.scheduler)                       # UniPC with enable_fused_step(): one imd_unipc_step per step
+        multistep = hasattr(self.scheduler, "step_guided") and not unipc      # UniPC: latent updates are host-computed linear combinations
+        fused = (not multistep and hasattr(self.scheduler, "plan")) or unipc  # DPM-Solver++ / Euler / Euler-ancestral / PNDM: one imd_sampler_step per step
         if len(set(gs)) > 1 and multistep:
             raise ValueError("guidance_scale differs between the requests: the per-request guidance step is the fused DDIM step; "
                              "UniPC takes one guidance scale per call")
@@ -410,13 +415,14 @@ class PipelineBase:
         if fused:
             # the history buffer [K][B HW 4] lives for the whole call at one address; which slot a step reads and writes is part of its
             # coefficient row (scheduler.SamplerHistory), so the rows of the whole run are known before the first launch
-            from ...scheduler import SamplerHistory
+            from ...scheduler import SamplerHistory, UniPCHistory
             hist = torch.zeros(sch.history, B, HW, Cl, dtype=torch.float32, device=dev) if sch.history else None
-            ring = SamplerHistory(sch.history)
-            sampler_rows = [ring.coefs(sch.plan(i, int(t_start), blend=inp is not None)) for i in range(len(timesteps))]
+            ring = UniPCHistory(sch.history) if unipc else SamplerHistory(sch.history)
+            plan = sch.plan_fused if unipc else sch.plan          # (UniPC: 19 values per step, two store slots)
+            sampler_rows = [ring.coefs(plan(i, int(t_start), blend=inp is not None)) for i in range(len(timesteps))]
 
         def sampler_step(t, i=None, coefs=None):
-            """ControlNet + UNet + ONE imd_sampler_step (CFG / update / history / noise / blend / next UNet input); ``t``, ``coefs`` as
+            """ControlNet + UNet + ONE imd_sampler_step -- imd_unipc_step for UniPC -- (CFG / update / history / noise / blend / next UNet input); ``t``, ``coefs`` as
             for ``ddim_step`` (graph replay: the coefficient row, history slot included, is read from device memory)."""
             down = mid = None
             mode = {} if i is None else dc_kw(i)          # (i is None: the captured step of a graph replay, which never runs with the cache)
@@ -428,7 +434,7 @@ class PipelineBase:
                 kw = dict(mask=inp["mask"], z_img=inp["z_img"], blend_noise=inp["noise"])
             if noisy:
                 kw["noise"] = step_noise(i)
-            ops.sampler_step(z, eps, x_in.view(2 * B, HW, 8), guidance=g_arg, coefs=sampler_rows[i] if coefs is None else coefs, hist=hist, **kw)
+            (ops.unipc_step if unipc else ops.sampler_step)(z, eps, x_in.view(2 * B, HW, 8), guidance=g_arg, coefs=sampler_rows[i] if coefs is None else coefs, hist=hist, **kw)
 
         def ddim_step(t, i=None, coefs=None):
             """ControlNet + UNet + CFG / DDIM / blend / next UNet input for one timestep; ``t`` a Python int (eager) or a device
@@ -472,7 +478,7 @@ class PipelineBase:
                 # replayed for steps 1 .. S-1: ~500 kernel launches per step become one hipGraphLaunch (the loop is host-bound at batch 1).
                 steps_n = len(timesteps)
                 t_table = torch.tensor(timesteps, dtype=torch.float32).to(dev)
-                rows = sampler_rows if fused else []          # (fused samplers: 13 values per step, history slots included)
+                rows = sampler_rows if fused else []          # (fused samplers: 13 values per step -- UniPC: 19 --, history slots included)
                 if not fused:
                     for i, t in enumerate(timesteps):
                         a_next = (sch.alpha(timesteps[i + 1]) if i < steps_n - 1 else None) if inp is not None else None
@@ -538,7 +544,7 @@ class PipelineBase:
                       compact: bool = False, widths=None):
         """A denoising session of ``slots`` latent rows at one geometry: requests are submitted at any time, enter a free slot at the
         start of any step, run their own number of steps and leave when done (``session.DenoiseSession``).  DPM-Solver++, Euler, PNDM
-        and DDIM (eta = 0); refused with UniPC, Euler-ancestral and while ``enable_deepcache`` is on; ``enable_step_graph`` is ignored.
+        and DDIM (eta = 0), UniPC after ``scheduler.enable_fused_step()``; refused with UniPC otherwise, Euler-ancestral and while ``enable_deepcache`` is on; ``enable_step_graph`` is ignored.
         ``compact=True``: every step runs a batch only as wide as the running requests need -- the smallest entry of ``widths`` (None:
         every width 1..slots; else a strictly increasing tuple that ends at ``slots``) -- and a request's bits then depend on the
         widths it ran under."""
@@ -762,7 +768,7 @@ def request_count(args: Dict[str, Any], per_call: Optional[Dict[str, Any]] = Non
     g = args.get("guidance_scale")
     if g is not None and _is_seq(g):
         gs = per_request_floats("guidance_scale", g, R)
-        if scheduler is not None and hasattr(scheduler, "step_guided") and len(set(gs)) > 1:
+        if scheduler is not None and hasattr(scheduler, "step_guided") and not unipc_fused(scheduler) and len(set(gs)) > 1:
             raise ValueError("guidance_scale differs between the requests: UniPC takes one guidance scale per call (the per-request "
                              "guidance step is the fused DDIM step)")
     if "image_scale" in args and _is_seq(args["image_scale"]):
@@ -833,6 +839,6 @@ def set_scale_by_type(unet, cls, **attrs):
                 setattr(proc, k, v)
 
 
-__all__ = ["deepcache_plan", "RequestLayout", "request_count", "request_rows", "per_request_floats", "per_call_value", "as_batch", "min_guidance", "entries",
+__all__ = ["deepcache_plan", "RequestLayout", "request_count", "request_rows", "unipc_fused", "per_request_floats", "per_call_value", "as_batch", "min_guidance", "entries",
            "controlnet_keep", "first", "to_image_tensor", "PipelineBase", "StableDiffusionPipelineOutput", "randn_tensor", "set_scale_by_type",
            "RefSAttnProcessor2_0", "LoraRefSAttnProcessor2_0", "LoRAIPAttnProcessor2_0", "IPAttnProcessor2_0"]

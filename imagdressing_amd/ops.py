@@ -1205,15 +1205,16 @@ def sampler_coefs(m_x=0.0, m_e=1.0, z_x=1.0, z_m=0.0, z_h=(), z_n=0.0, b_img=1.0
     return [float(m_x), float(m_e), float(z_x), float(z_m)] + zh + [float(z_n), float(b_img), float(b_noise), float(in_scale), float(int(store))]
 
 
-def _sampler_params(what, z, eps, x_next, guidance, hist, noise, mask, z_img, blend_noise, rows=None):
+def _sampler_params(what, z, eps, x_next, guidance, hist, noise, mask, z_img, blend_noise, rows=None, unipc=False):
     """the tensor fields of ``imd_sampler_params`` (everything but the coefficients), checked: shared by the entry points.  ``rows``:
     the batch width B of ``imd_sampler_step_rows_at``, whose z / hist / noise / blend operands have ``z.shape[0]`` = slots rows while
-    eps, x_next and the guidance array have B; None: one row count for everything."""
+    eps, x_next and the guidance array have B; None: one row count for everything.  ``unipc``: the same fields of
+    ``imd_unipc_params`` (which has no ``noise``)."""
     ensure_device(z.device)
     S, HW = z.shape[0], z.shape[1]
     B = S if rows is None else int(rows)
     n, nr = S * HW * 4, B * HW * 4
-    p = L.SamplerParams()
+    p = L.UnipcParams() if unipc else L.SamplerParams()
     p.z, p.eps = _dev(z, torch.float32, "z"), _dev(eps, torch.float32, "eps")
     if z.numel() != n or eps.numel() != 2 * nr:
         raise L.ImdError(f"{what}: z {tuple(z.shape)} / eps {tuple(eps.shape)}: expected [B, HW, 4] and [2B, HW, 4]" if rows is None else
@@ -1240,9 +1241,12 @@ def _sampler_params(what, z, eps, x_next, guidance, hist, noise, mask, z_img, bl
             raise L.ImdError(f"{what}: {name} has {t.numel()} elements, expected {n}")
     if mask is not None and mask.numel() != S * HW:
         raise L.ImdError(f"{what}: mask has {mask.numel()} elements, expected {S * HW}")
-    p.noise = _opt(noise, torch.float32, "noise")
     p.mask, p.z_img, p.blend_noise = _opt(mask, torch.float32, "mask"), _opt(z_img, torch.float32, "z_img"), _opt(blend_noise, torch.float32, "blend_noise")
-    p.coefs, p.store = None, -1
+    p.coefs = None
+    if unipc:
+        p.store_m = p.store_s = -1
+    else:
+        p.noise, p.store = _opt(noise, torch.float32, "noise"), -1
     return p
 
 
@@ -1346,6 +1350,91 @@ def session_input_rows(z, row_slot, in_scale_rows, x_in):
     L.check(L.load().imd_session_input_rows(zp, rs, _dev(in_scale_rows, torch.float32, "in_scale_rows"), _dev(x_in, x_in.dtype, "x_in"),
                                             B, slots, HW, _code(x_in, "x_in"), _stream()))
     return x_in
+
+
+# ---- UniPC on one fused step launch (csrc/unipc_step.hip; the coefficients come from scheduler.UniPCMultistepScheduler.plan_fused) ----
+UNIPC_COEFS = 19
+UNIPC_ROW_FLOATS = 24
+UNIPC_IN_SCALE = 16          # index of in_scale in the block (what ``session_input_rows`` needs of a request's last step)
+
+
+def unipc_coefs(m_x=0.0, m_e=1.0, s_x=1.0, s_m=0.0, s_h=(), z_s=1.0, z_m=0.0, z_h=(), b_img=1.0, b_noise=0.0, in_scale=1.0,
+                store_m=-1, store_s=-1):
+    """The coefficient block of one ``imd_unipc_step`` in the order ``imd_unipc_params.coefs`` reads it (19 floats; ``s_h`` / ``z_h`` by
+    PHYSICAL history slot, padded with zeros; ``store_m`` / ``store_s`` = the slots that receive m and s', -1 for none, carried as
+    floats)."""
+    sh, zh = [float(c) for c in s_h], [float(c) for c in z_h]
+    if len(sh) > SAMPLER_MAX_HISTORY or len(zh) > SAMPLER_MAX_HISTORY:
+        raise L.ImdError(f"unipc_coefs: {max(len(sh), len(zh))} history coefficients (at most {SAMPLER_MAX_HISTORY})")
+    sh += [0.0] * (SAMPLER_MAX_HISTORY - len(sh))
+    zh += [0.0] * (SAMPLER_MAX_HISTORY - len(zh))
+    return ([float(m_x), float(m_e), float(s_x), float(s_m)] + sh + [float(z_s), float(z_m)] + zh
+            + [float(b_img), float(b_noise), float(in_scale), float(int(store_m)), float(int(store_s))])
+
+
+def unipc_step(z, eps, x_next, *, guidance, coefs, hist=None, mask=None, z_img=None, blend_noise=None):
+    """One fused UniPC step (``imd_unipc_step``): x0 prediction with CFG, corrector, predictor, both history stores, the inpainting
+    blend and the next UNet input.  z [B,HW,4] fp32 (in place); eps [2B,HW,4] fp32; x_next [2B,HW,8] 16-bit or None; ``hist``
+    [K, B, HW, 4] fp32 (one contiguous buffer, K = solver_order + 1 <= 4) or None; ``mask`` [B,HW] + ``z_img`` + ``blend_noise``
+    [B,HW,4]: the inpainting blend.  ``coefs``: the 19 values of :func:`unipc_coefs` as a Python sequence (passed in the parameter
+    block) or as a device fp32 tensor (read by the kernel: HIP-graph replay of a step).  ``guidance``: a float, or a device fp32
+    tensor [B]."""
+    p = _sampler_params("unipc_step", z, eps, x_next, guidance, hist, None, mask, z_img, blend_noise, unipc=True)
+    if isinstance(coefs, torch.Tensor):
+        if coefs.numel() < UNIPC_COEFS:
+            raise L.ImdError(f"unipc_step: coefs needs {UNIPC_COEFS} fp32 values")
+        p.coefs = _dev(coefs, torch.float32, "coefs")
+    else:
+        c = [float(v) for v in coefs]
+        if len(c) != UNIPC_COEFS:
+            raise L.ImdError(f"unipc_step: coefs needs {UNIPC_COEFS} values (ops.unipc_coefs), got {len(c)}")
+        p.m_x, p.m_e, p.s_x, p.s_m = c[0:4]
+        p.s_h = (C.c_float * 4)(*c[4:8])
+        p.z_s, p.z_m = c[8:10]
+        p.z_h = (C.c_float * 4)(*c[10:14])
+        p.b_img, p.b_noise, p.in_scale = c[14:17]
+        p.store_m, p.store_s = int(c[17]), int(c[18])
+    L.check(L.load().imd_unipc_step(C.byref(p), _stream()))
+    return z
+
+
+def unipc_coef_row(coefs19, active=True):
+    """One latent row of ``imd_unipc_step_rows``: the 19 values of :func:`unipc_coefs`, the ``active`` flag (0: the row is skipped,
+    nothing of it is read or written) and four reserved zeros -- 24 floats."""
+    c = [float(v) for v in coefs19]
+    if len(c) != UNIPC_COEFS:
+        raise L.ImdError(f"unipc_coef_row: needs the {UNIPC_COEFS} values of ops.unipc_coefs, got {len(c)}")
+    return c + [1.0 if active else 0.0, 0.0, 0.0, 0.0, 0.0]
+
+
+def _unipc_rows_ptr(what, coef_rows, B):
+    if (not isinstance(coef_rows, torch.Tensor) or coef_rows.dtype != torch.float32 or coef_rows.numel() != B * UNIPC_ROW_FLOATS
+            or not coef_rows.is_contiguous()):
+        raise L.ImdError(f"{what}: coef_rows must be a contiguous device fp32 tensor [{B}, {UNIPC_ROW_FLOATS}] "
+                         f"(ops.unipc_coef_row per row), got {getattr(coef_rows, 'dtype', type(coef_rows))} "
+                         f"{tuple(getattr(coef_rows, 'shape', ()))}")
+    return _dev(coef_rows, torch.float32, "coef_rows")
+
+
+def unipc_step_rows(z, eps, x_next, *, guidance, coef_rows, hist=None, mask=None, z_img=None, blend_noise=None):
+    """:func:`unipc_step` with one coefficient block PER LATENT ROW (``imd_unipc_step_rows``): ``coef_rows`` is a device fp32 tensor
+    [B, 24] of :func:`unipc_coef_row` rows -- every row at its own step of its own schedule, with its own history slots; an inactive
+    row keeps every byte of its z, history and x_next.  The other arguments as for :func:`unipc_step`."""
+    p = _sampler_params("unipc_step_rows", z, eps, x_next, guidance, hist, None, mask, z_img, blend_noise, unipc=True)
+    L.check(L.load().imd_unipc_step_rows(C.byref(p), _unipc_rows_ptr("unipc_step_rows", coef_rows, p.B), _stream()))
+    return z
+
+
+def unipc_step_rows_at(z, eps, x_next, *, guidance, coef_rows, row_slot, hist=None, mask=None, z_img=None, blend_noise=None):
+    """:func:`unipc_step_rows` through a row -> slot map (``imd_unipc_step_rows_at``; the compacting denoising session), with the
+    semantics of :func:`sampler_step_rows_at`.  By ROW: ``eps`` [2B,HW,4], ``x_next`` [2B,HW,8], ``coef_rows`` [B,24], a ``guidance``
+    tensor [B].  By SLOT: ``z`` [slots,HW,4] (in place), ``hist`` [K,slots,HW,4], ``mask`` / ``z_img`` / ``blend_noise``."""
+    slots = z.shape[0]
+    rs = _row_slot_ptr("unipc_step_rows_at", row_slot, slots)
+    B = row_slot.numel()
+    p = _sampler_params("unipc_step_rows_at", z, eps, x_next, guidance, hist, None, mask, z_img, blend_noise, rows=B, unipc=True)
+    L.check(L.load().imd_unipc_step_rows_at(C.byref(p), _unipc_rows_ptr("unipc_step_rows_at", coef_rows, B), rs, slots, _stream()))
+    return z
 
 
 # ---------------------------------------------------------------------------------------------

@@ -99,13 +99,19 @@ class UniPCMultistepScheduler:
 
     The coefficients of every update depend only on the timestep history, so they are computed on the host in float64
     (`x0_terms`, `corrector_terms`, `predictor_terms` return (coefficient, tensor-name) lists) and applied to the fp32
-    latents by ONE `imd_lincomb` launch each: x0 prediction + classifier-free guidance, corrector, predictor."""
+    latents by ONE `imd_lincomb` launch each: x0 prediction + classifier-free guidance, corrector, predictor.
+
+    `fused_step=True` / `enable_fused_step()` (off by default; off, nothing above changes): the same three updates as ONE
+    `imd_unipc_step` launch per step -- `plan_fused` states a step as a :class:`UniPCRow` from the same term lists and the
+    same order bookkeeping, :class:`UniPCHistory` lays the x0 predictions and `last_sample` into `solver_order + 1` planes
+    of a device buffer -- which gives the pipelines per-request guidance, the inpainting blend, step-graph replay and
+    denoising sessions for this class.  The bits then differ from the three-launch route at fp32-rounding level."""
 
     init_noise_sigma = 1.0
 
     def __init__(self, num_train_timesteps=1000, beta_start=0.0001, beta_end=0.02, beta_schedule="linear", solver_order=2,
                  prediction_type="epsilon", predict_x0=True, solver_type="bh2", lower_order_final=True, disable_corrector=(),
-                 timestep_spacing="linspace", steps_offset=0, thresholding=False, **unused):
+                 timestep_spacing="linspace", steps_offset=0, thresholding=False, fused_step=False, **unused):
         if beta_schedule == "scaled_linear":
             betas = np.linspace(beta_start ** 0.5, beta_end ** 0.5, num_train_timesteps, dtype=np.float64) ** 2
         elif beta_schedule == "linear":
@@ -129,7 +135,20 @@ class UniPCMultistepScheduler:
         self.config = dict(num_train_timesteps=num_train_timesteps, solver_order=solver_order, solver_type=solver_type)
         self.num_inference_steps = None
         self.timesteps = torch.from_numpy(np.arange(0, num_train_timesteps)[::-1].copy().astype(np.int64))
+        self.fused_step = bool(fused_step)
         self._reset()
+
+    # ---- the fused-step switch (off by default: nothing about the class changes while it is off) ------------------------
+    def enable_fused_step(self, flag: bool = True):
+        """Opt in to ONE ``imd_unipc_step`` launch per step (:meth:`plan_fused`): the pipelines then give UniPC what the other
+        samplers have -- per-request guidance, the inpainting blend and ``strength`` < 1, step-graph replay, denoising sessions.
+        The bits change at fp32-rounding level against the three ``imd_lincomb`` launches (no intermediate tensor is rounded
+        through memory); ``step`` / ``step_guided`` themselves are untouched."""
+        self.fused_step = bool(flag)
+        return self
+
+    def disable_fused_step(self):
+        return self.enable_fused_step(False)
 
     # ---- schedule --------------------------------------------------------------------------------------------------
     def _reset(self):
@@ -209,24 +228,73 @@ class UniPCMultistepScheduler:
         terms.insert(1, (c_m0, "m0"))
         return terms
 
-    def predictor_terms(self, pos_s0, order):
-        """UniP-p: sample at schedule position pos_s0 + 1 from `x` (at pos_s0) and the x0 history (m0 newest)."""
-        a_t, ratio, h_phi_1, B_h, rks, R, b = self._bh(pos_s0, pos_s0 + 1, self.ts_hist, order)
+    def predictor_terms(self, pos_s0, order, hist_pos=None):
+        """UniP-p: sample at schedule position pos_s0 + 1 from `x` (at pos_s0) and the x0 history (m0 newest).  `hist_pos`: the
+        positions the history was made at, oldest first (None: this instance's running `ts_hist`)."""
+        a_t, ratio, h_phi_1, B_h, rks, R, b = self._bh(pos_s0, pos_s0 + 1, self.ts_hist if hist_pos is None else hist_pos, order)
         rhos = [] if order == 1 else ([0.5] if order == 2 else list(np.linalg.solve(R[:-1, :-1], b[:-1])))
         return self._expand(ratio, -a_t * h_phi_1, [-a_t * B_h * r for r in rhos], rks)
 
-    def corrector_terms(self, pos_t, order):
+    def corrector_terms(self, pos_t, order, hist_pos=None):
         """UniC-p: re-estimate the sample at pos_t from `x` = the sample at pos_t - 1, the history (m0 = x0 at pos_t - 1) and
-        `mt` = the x0 prediction just made at pos_t."""
-        a_t, ratio, h_phi_1, B_h, rks, R, b = self._bh(pos_t - 1, pos_t, self.ts_hist, order)
+        `mt` = the x0 prediction just made at pos_t.  `hist_pos` as for `predictor_terms`."""
+        a_t, ratio, h_phi_1, B_h, rks, R, b = self._bh(pos_t - 1, pos_t, self.ts_hist if hist_pos is None else hist_pos, order)
         rhos = [0.5] if order == 1 else list(np.linalg.solve(R, b))
         return self._expand(ratio, -a_t * h_phi_1, [-a_t * B_h * r for r in rhos[:-1]], rks, extra=-a_t * B_h * rhos[-1])
 
     def _order_now(self):
+        return self._order_at(self.step_index, self.lower_order_nums)
+
+    def _order_at(self, pos, lower_order_nums):
+        """order of the predictor at schedule position `pos` when `lower_order_nums` steps of the ramp-up are behind it"""
         o = self.solver_order
         if self.lower_order_final:
-            o = min(o, self.num_inference_steps - self.step_index)
-        return min(o, self.lower_order_nums + 1)
+            o = min(o, self.num_inference_steps - pos)
+        return min(o, lower_order_nums + 1)
+
+    # ---- the fused step: the same bookkeeping as `_advance`, as one coefficient row per step ------------------------------
+    @property
+    def history(self) -> int:
+        """planes of the device history buffer of the fused step: `solver_order` x0 predictions and `last_sample`"""
+        return self.solver_order + 1
+
+    stochastic = False
+
+    def steps(self, start: int = 0) -> int:
+        return len(self.timesteps) - int(start)
+
+    def input_scale(self, pos: int) -> float:
+        return 1.0
+
+    def plan_fused(self, i: int, t_start: int = 0, blend: bool = False) -> "UniPCRow":
+        """The i-th step of a run that begins at schedule position `t_start`, as ONE :class:`UniPCRow` in float64 -- what
+        `step_guided` + `_advance` apply with three launches, from the same `x0_terms` / `corrector_terms` / `predictor_terms` and
+        the same order bookkeeping (ramp-up from order 1, `lower_order_final`, `disable_corrector`).  A pure function of the
+        positions: the rows of a whole run are known before its first launch and the instance's running state is not touched.
+        `blend`: the coefficients of the inpainting blend toward the NEXT position (the image latents re-noised to the next
+        timestep; the clean image after the last step), as `plan` of the other samplers computes them."""
+        i, start, so = int(i), int(t_start), self.solver_order
+        pos = start + i
+        N = len(self.timesteps)
+        if not 0 <= pos < N:
+            raise ValueError(f"plan_fused: step {i} of a run from position {start} is outside the {N} steps of the schedule")
+        made = list(range(start, pos))                         # positions of the x0 predictions made before this step
+        (m_x, _), (m_e, _) = self.x0_terms(pos)
+        row = dict(m_x=m_x, m_e=m_e, s_h=(0.0,) * so)
+        if i > 0 and (pos - 1) not in self.disable_corrector:
+            order_prev = self._order_at(pos - 1, min(i - 1, so))     # `this_order` as the previous step left it
+            named = {n: c for c, n in self.corrector_terms(pos, order_prev, made[-so:])}
+            row.update(s_x=0.0, s_l=named.pop("x"), s_m=named.pop("mt"))
+            row["s_h"] = tuple(named.get(f"m{k}", 0.0) for k in range(so))
+        order = self._order_at(pos, min(i, so))
+        named = {n: c for c, n in self.predictor_terms(pos, order, (made + [pos])[-so:])}
+        row.update(z_s=named.pop("x"), z_m=named.pop("m0"))
+        row["z_h"] = tuple(named.get(f"m{k + 1}", 0.0) for k in range(so))          # age k = the k-th newest BEFORE this step
+        if blend:
+            last = pos == N - 1
+            a = 1.0 if last else float(self._ac[int(self.timesteps[pos + 1])])
+            row.update(b_img=a ** 0.5, b_noise=(1.0 - a) ** 0.5)
+        return UniPCRow(**row)
 
     # ---- device-side application -------------------------------------------------------------------------------
     def _apply(self, terms, named, out=None):
@@ -266,6 +334,67 @@ class UniPCMultistepScheduler:
     def add_noise(self, original_samples, noise, timesteps):
         a = float(self._ac[int(torch.as_tensor(timesteps).reshape(-1)[0])])
         return a ** 0.5 * original_samples + (1 - a) ** 0.5 * noise
+
+
+def unipc_fused(scheduler) -> bool:
+    """a UniPC whose fused-step switch is on: the pipelines' loop, the request checks and the sessions treat it like the samplers of
+    ``imd_sampler_step`` (one launch per step, ``imd_unipc_step``); off, it is the three-launch class with its refusals"""
+    return hasattr(scheduler, "plan_fused") and bool(getattr(scheduler, "fused_step", False))
+
+
+class UniPCRow:
+    """The float64 coefficients of ONE UniPC step, as ``imd_unipc_step`` applies them to the guided epsilon e:
+
+        m  = m_x z + m_e e                                            the x0 prediction made at this position
+        s' = s_x z + s_m m + s_l L + sum_j s_h[j] M_j                  UniC (no corrector: s_x = 1, the rest 0, s' = z)
+        z' = z_s s' + z_m m + sum_j z_h[j] M_j                         UniP from s'
+        z' = (1 - mask) (b_img z_img + b_noise blend_noise) + mask z'
+        x_next = 16-bit(in_scale z');  the history gains m, and s' replaces L
+
+    L = ``last_sample`` (the s' of the previous step), M_j = the j-th NEWEST x0 prediction stored BEFORE this step.  ``s_h`` /
+    ``z_h`` are ordered by AGE; :class:`UniPCHistory` maps ages (and L) to the physical slots of the device buffer."""
+    __slots__ = ("m_x", "m_e", "s_x", "s_m", "s_l", "s_h", "z_s", "z_m", "z_h", "b_img", "b_noise", "in_scale")
+
+    def __init__(self, m_x=0.0, m_e=1.0, s_x=1.0, s_m=0.0, s_l=0.0, s_h=(), z_s=1.0, z_m=0.0, z_h=(), b_img=1.0, b_noise=0.0, in_scale=1.0):
+        self.m_x, self.m_e, self.s_x, self.s_m, self.s_l = float(m_x), float(m_e), float(s_x), float(s_m), float(s_l)
+        self.s_h, self.z_h = tuple(float(c) for c in s_h), tuple(float(c) for c in z_h)
+        self.z_s, self.z_m = float(z_s), float(z_m)
+        self.b_img, self.b_noise, self.in_scale = float(b_img), float(b_noise), float(in_scale)
+
+    def __repr__(self):
+        return "UniPCRow(" + ", ".join(f"{k}={getattr(self, k)!r}" for k in self.__slots__) + ")"
+
+
+class UniPCHistory:
+    """Host-side bookkeeping of the device history buffer [K][B HW 4] of the fused UniPC step, like :class:`SamplerHistory`: ONE slot
+    is ``last_sample`` and is overwritten in place at every step; the new x0 prediction takes a free slot while there is one, then
+    the slot of the oldest prediction (which the same launch may still read: every thread reads before it stores).  Data never
+    moves; the slot indices travel in the coefficient block.  K = solver_order + 1 suffices: a step reads at most ``solver_order``
+    stored predictions and ``last_sample``."""
+
+    def __init__(self, K: int):
+        self.K = int(K)
+        if self.K < 2:
+            raise ValueError(f"UniPCHistory: K = {K}; the fused step keeps last_sample and at least one x0 prediction")
+        self.last = 0                     # the slot of last_sample
+        self.slots = []                   # physical slots of the x0 predictions, newest first
+
+    def coefs(self, row: UniPCRow):
+        """-> the 19 values of ``ops.unipc_coefs`` for ``row`` (``s_h`` / ``z_h`` permuted to physical slots) -- and the history
+        advances."""
+        sh, zh = [0.0] * ops.SAMPLER_MAX_HISTORY, [0.0] * ops.SAMPLER_MAX_HISTORY
+        for name, src, dst in (("s_h", row.s_h, sh), ("z_h", row.z_h, zh)):
+            for age, c in enumerate(src):
+                if c != 0.0:
+                    if age >= len(self.slots):
+                        raise ValueError(f"the step reads x0 prediction {age} ({name}) but only {len(self.slots)} are stored")
+                    dst[self.slots[age]] = c
+        sh[self.last] = row.s_l
+        free = [s for s in range(self.K) if s != self.last and s not in self.slots]
+        store_m = free[0] if free else self.slots[-1]
+        self.slots = [store_m] + [s for s in self.slots if s != store_m]
+        return ops.unipc_coefs(row.m_x, row.m_e, row.s_x, row.s_m, sh, row.z_s, row.z_m, zh, row.b_img, row.b_noise, row.in_scale,
+                               store_m, self.last)
 
 
 # ---------------------------------------------------------------------------------------------------------------------

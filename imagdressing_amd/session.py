@@ -4,7 +4,9 @@ A request-batched pipeline call needs all its requests in hand before it starts,
 session keeps ONE batch of ``slots`` latent rows alive across calls instead: a request enters a free slot at the start of any step,
 runs its own schedule (its own step count, its own position in it) and leaves when done.  Every :meth:`DenoiseSession.step` is one
 UNet forward (plus ControlNet) over all 2 x slots rows of the CFG batch and one fused step launch (``imd_sampler_step_rows``) that
-gives every latent row its own coefficients, its own history slots and its own "this row is not running" flag.
+gives every latent row its own coefficients, its own history slots and its own "this row is not running" flag.  A session has ONE
+scheduler, so every row of a step goes through the same kernel: a UniPC whose fused-step switch is on runs on ``imd_unipc_step_rows``
+(24-float rows, ``solver_order + 1`` history planes), every other sampler on ``imd_sampler_step_rows``.
 
 Two kinds of index.  A SLOT is the home of a request's per-latent state -- the fp32 latent ``z[S, HW, 4]`` and the history
 ``hist[K, S, HW, 4]``; slots are taken lowest free index first and these buffers never move.  A ROW is a position in the batch the
@@ -19,8 +21,8 @@ with ``compact=True`` a request's bits depend on the sequence of widths it ran u
 Two layers, so that the logic is testable without a GPU:
 
 * :class:`SessionPlan` -- pure Python: slot allocation (lowest free index first), the FIFO queue, one scheduler instance /
-  :class:`~imagdressing_amd.scheduler.SamplerHistory` / position per request, the width and the row of every slot, and per step one
-  16-float coefficient row and one timestep per slot and per row.
+  :class:`~imagdressing_amd.scheduler.SamplerHistory` (UniPC: ``UniPCHistory``) / position per request, the width and the row of every
+  slot, and per step one 16-float (UniPC: 24-float) coefficient row and one timestep per slot and per row.
 * :class:`DenoiseSession` -- the device state: fixed-address buffers for every slot and, at capacity, for every row (one view object
   per width and buffer), admission (prompt encoding, the garment UNet at batch 1, in-place writes of the row), the step, tickets.
 """
@@ -33,14 +35,16 @@ from typing import Any, Dict, List, Optional
 import torch
 
 from . import ops
-from .scheduler import DDIMScheduler, SamplerHistory, ddim_row
+from .scheduler import DDIMScheduler, SamplerHistory, UniPCHistory, ddim_row, unipc_fused
 
 
 # ---- refusals (pure: nothing here touches a device) ----
 def check_scheduler(scheduler) -> None:
     """The samplers a session can drive: every deterministic one whose step is ONE affine row -- DPM-Solver++, Euler, PNDM
-    (``plan``) and DDIM (``ddim_row``)."""
+    (``plan``), DDIM (``ddim_row``) and UniPC with ``enable_fused_step()`` (``plan_fused``)."""
     name = type(scheduler).__name__
+    if unipc_fused(scheduler):
+        return
     if hasattr(scheduler, "step_guided"):
         raise NotImplementedError(f"open_session: scheduler {name} (UniPC) updates the latents with host-built linear combinations of "
                                   "whole tensors, not one affine row per latent row; use DPM-Solver++, Euler, PNDM or DDIM")
@@ -91,7 +95,11 @@ class PlanRun:
         sch = copy.copy(scheduler)          # the class and configuration of the pipeline's scheduler; set_timesteps rebinds, never mutates
         sch.set_timesteps(int(num_inference_steps))
         self.scheduler = sch
-        if self.affine:
+        if self.unipc:
+            self.timesteps = [t.item() for t in sch.timesteps]
+            self.steps = sch.steps()
+            self.ring = UniPCHistory(sch.history)
+        elif self.affine:
             self.timesteps = [t.item() for t in sch.timesteps]          # (fractional ones reach the time embedding unrounded)
             self.steps = sch.steps()                                       # UNet calls: PNDM has one more than it has steps
             self.ring = SamplerHistory(sch.history)
@@ -112,6 +120,11 @@ class PlanRun:
         return hasattr(self.scheduler, "plan")
 
     @property
+    def unipc(self) -> bool:
+        """UniPC on the fused step (``plan_fused``, 19 coefficients)"""
+        return unipc_fused(self.scheduler)
+
+    @property
     def done(self) -> bool:
         return self.i >= self.steps
 
@@ -120,7 +133,11 @@ class PlanRun:
         return float(self.scheduler.input_scale(0)) if self.affine else 1.0
 
     def next_coefs(self) -> List[float]:
-        """the 13 coefficients of step ``i`` -- and the history bookkeeping advances"""
+        """the 13 coefficients of step ``i`` (UniPC: the 19 of ``ops.unipc_coefs``) -- and the history bookkeeping advances"""
+        if self.unipc:
+            coefs = self.ring.coefs(self.scheduler.plan_fused(self.i))
+            self.in_scale = coefs[ops.UNIPC_IN_SCALE]
+            return coefs
         row = self.scheduler.plan(self.i) if self.affine else ddim_row(self.scheduler, self.timesteps[self.i])
         coefs = self.ring.coefs(row)
         self.in_scale = coefs[11]
@@ -181,10 +198,13 @@ class SessionPlan:
             raise ValueError("widths is the ladder of a compacting session: pass compact=True with it")
         self.widths = check_widths(self.S, widths) if self.compact else (self.S,)
         self.scheduler = scheduler
-        self.K = int(getattr(scheduler, "history", 0)) if hasattr(scheduler, "plan") else 0          # history slots of the device buffer
+        self.unipc = unipc_fused(scheduler)          # every row of a step goes through ONE kernel: imd_unipc_step_rows or imd_sampler_step_rows
+        self.K = int(getattr(scheduler, "history", 0)) if hasattr(scheduler, "plan") or self.unipc else 0          # history slots of the device buffer
         self._slots: List[Optional[PlanRun]] = [None] * self.S
         self.queue = deque()
-        self.idle_row = ops.sampler_coef_row(ops.sampler_coefs(), active=False)
+        self.coef_row = ops.unipc_coef_row if self.unipc else ops.sampler_coef_row
+        self.row_floats = ops.UNIPC_ROW_FLOATS if self.unipc else ops.SAMPLER_ROW_FLOATS
+        self.idle_row = self.coef_row(ops.unipc_coefs() if self.unipc else ops.sampler_coefs(), active=False)
         # the batch: width 0 until the first step lays it out (nothing to move: that is no repack)
         self.width = 0 if self.compact else self.S
         self._rows: List[Optional[PlanRun]] = [] if self.compact else [None] * self.S
@@ -192,6 +212,9 @@ class SessionPlan:
         self.repacks = 0
 
     def submit(self, num_inference_steps: int, payload=None) -> PlanRun:
+        if unipc_fused(self.scheduler) != self.unipc:
+            raise RuntimeError("the scheduler's fused-step switch changed since the session was opened: its buffers and its step kernel "
+                               "were chosen for the other setting; open a new session")
         run = PlanRun(self.scheduler, num_inference_steps, payload)
         self.queue.append(run)
         return run
@@ -271,7 +294,7 @@ class SessionPlan:
                 continue
             ts.append(run.timesteps[run.i])
             running.append((s, run, run.i))
-            rows.append(ops.sampler_coef_row(run.next_coefs(), active=True))
+            rows.append(self.coef_row(run.next_coefs(), active=True))
             run.i += 1
             if run.done:
                 finished.append(run)
@@ -408,7 +431,7 @@ class DenoiseSession:
         self.mask_rows = torch.zeros(2 * S, dtype=torch.float32, device=dev)          # [image_scale of the cond rows; 0 for the uncond rows]
         self.guidance = torch.ones(S, dtype=torch.float32, device=dev)
         self.guidance_rows = torch.ones(S, dtype=torch.float32, device=dev) if self.compact else None
-        self.coef_rows = torch.zeros(S, ops.SAMPLER_ROW_FLOATS, dtype=torch.float32, device=dev)
+        self.coef_rows = torch.zeros(S, self.plan.row_floats, dtype=torch.float32, device=dev)
         self.row_slot = torch.arange(S, dtype=torch.int32, device=dev)
         self._row_slot_host = list(range(S))
         self.encoders = [m for m in [pipe.unet] + ([self.controlnet] if self.controlnet is not None else []) if hasattr(m, "use_time_embedding")]
@@ -654,10 +677,11 @@ class DenoiseSession:
         finally:
             for e in self.encoders:
                 e.clear_time_embeddings()
+        step_rows_at, step_rows = (ops.unipc_step_rows_at, ops.unipc_step_rows) if self.plan.unipc else (ops.sampler_step_rows_at, ops.sampler_step_rows)
         if self.compact:
-            ops.sampler_step_rows_at(self.z, eps, v.x_flat, guidance=v.guidance_rows, coef_rows=v.coef_rows, row_slot=v.row_slot, hist=self.hist)
+            step_rows_at(self.z, eps, v.x_flat, guidance=v.guidance_rows, coef_rows=v.coef_rows, row_slot=v.row_slot, hist=self.hist)
         else:
-            ops.sampler_step_rows(self.z, eps, v.x_flat, guidance=self.guidance, coef_rows=v.coef_rows, hist=self.hist)
+            step_rows(self.z, eps, v.x_flat, guidance=self.guidance, coef_rows=v.coef_rows, hist=self.hist)
         self.steps_run += 1
         self._last_width = B
         self.steps_at_width[B] = self.steps_at_width.get(B, 0) + 1

@@ -314,6 +314,43 @@ typedef struct imd_sampler_params {
                            * holds no pointer or scalar that changes between replays -- the host refreshes 52 bytes per step */
 } imd_sampler_params;
 
+/* One step of the UniPC multistep sampler (imd_unipc_step) over the [B, HW, 4] latent, per element in fp32:
+ *   e  = eps_u + g (eps_c - eps_u)                         g = guidance, or guidance_rows[row]
+ *   m  = m_x z + m_e e                                     the x0 prediction made at this position
+ *   s' = s_x z + s_m m + sum_{k < K} s_h[k] hist[k]        the corrected sample (UniC), the library's last_sample; no corrector: s_x = 1, rest 0
+ *   z' = z_s s' + z_m m + sum_{k < K} z_h[k] hist[k]       the predictor (UniP), from the value s' just computed
+ *   z' = (1 - mask) (b_img z_img + b_noise blend_noise) + mask z'            (with mask; the blend touches z' only, never s')
+ *   z <- z';  hist[store_m] <- m;  hist[store_s] <- s';  x_next[both CFG halves] <- 16-bit(in_scale z'), channels 4..7 = 0
+ * imd_sampler_step stores ONE derived quantity per step, UniPC two, and the second is an intermediate of the same step's predictor:
+ * hence a block and a kernel of its own (unipc_step.hip).  hist holds up to solver_order older x0 predictions and last_sample:
+ * K = solver_order + 1 <= IMD_SAMPLER_MAX_HISTORY.  The coefficients are host-computed (imagdressing_amd/scheduler.py, plan_fused). */
+#define IMD_UNIPC_COEFS 19       /* floats of the device coefficient block: m_x, m_e, s_x, s_m, s_h[4], z_s, z_m, z_h[4], b_img, b_noise,
+                                    in_scale, store_m, store_s */
+typedef struct imd_unipc_params {
+    uint32_t struct_bytes; /* sizeof(imd_unipc_params) in the caller's view; checked on entry */
+    float* z;             /* [B, HW, 4] fp32 latent state, updated in place */
+    const float* eps;     /* [2B, HW, 4] fp32: rows [0,B) cond pass, [B,2B) uncond pass */
+    uint16_t* x_next;     /* [2B, HW, 8] 16-bit next UNet input (channels 4..7 = 0) or NULL */
+    float* hist;          /* [K][B HW 4] fp32, ONE contiguous buffer owned by the caller (NULL iff K == 0).  A slot may be read and
+                           * overwritten by the same launch: every thread reads its element of each slot before it stores */
+    int B, HW, K;         /* K: history slots, 0..IMD_SAMPLER_MAX_HISTORY */
+    int dtype;            /* element type of x_next */
+    float guidance;
+    const float* guidance_rows; /* NULL, or DEVICE [B] fp32: the guidance scale of each latent row, read instead of `guidance` */
+    float m_x, m_e, s_x, s_m;
+    float s_h[4];         /* by PHYSICAL slot; a slot whose coefficient is 0 in s_h AND z_h is not read */
+    float z_s, z_m;
+    float z_h[4];
+    float b_img, b_noise, in_scale;
+    int store_m, store_s; /* physical slots that receive m and s', -1: none; equal non-negative values are refused */
+    const float* mask;    /* NULL, or [B, HW] inpaint mask; then z_img and blend_noise [B, HW, 4] are required */
+    const float* z_img;
+    const float* blend_noise;
+    const float* coefs;   /* NULL, or DEVICE pointer to IMD_UNIPC_COEFS fp32 read by the kernel INSTEAD of m_x .. store_s above (the stores
+                           * as floats holding the integers; a value outside 0..K-1 stores nothing): a captured HIP graph of a step then
+                           * holds no pointer or scalar that changes between replays -- the host refreshes 76 bytes per step */
+} imd_unipc_params;
+
 /* Device-side image input (imd_image_resample): separable antialiased resampling of uint8 images, bit-exact with Pillow's 8-bit
  * resampler (libImaging/Resample.c), with a fused output stage -- the work diffusers' VaeImageProcessor / transformers'
  * CLIPImageProcessor do on the host in front of IMAGDressing_v1_pipeline*.py.  Per axis whose size changes the caller passes a
@@ -597,6 +634,28 @@ int imd_sampler_step_rows_at(const imd_sampler_params* p, const float* coef_rows
  * x_in not 16-byte aligned, row_slot or in_scale_rows not 4-byte aligned, an unknown dtype. */
 int imd_session_input_rows(const float* z, const int* row_slot, const float* in_scale_rows, void* x_in, int B, int slots, int HW,
                            int dtype_code, void* stream);
+/* CFG combine + one UniPC step (x0 prediction, corrector, predictor, both history stores, inpaint blend) + next UNet input as ONE
+ * launch; see imd_unipc_params.  Replaces `scheduler.step` of diffusers' UniPCMultistepScheduler at the call site
+ * IMAGDressing_v1_pipeline.py:530-532 -- and the three imd_lincomb launches plus the identity imd_ddim_cfg_step this engine spends
+ * on it otherwise.  The arithmetic is one fixed sequence of fused multiply-adds, so the three forms below are bit-identical wherever
+ * they describe the same step.  Errors without launching: a foreign struct_bytes, K outside 0..4, K > 0 without hist, store_m or
+ * store_s outside -1..K-1 or equal and non-negative (host coefficients), a mask without z_img / blend_noise, misaligned pointers
+ * (16 bytes for the float4 / uint4 tensors, 4 for mask, guidance_rows and coefs). */
+int imd_unipc_step(const imd_unipc_params* p, void* stream);
+/* The same step with the coefficient block read PER LATENT ROW (a denoising session).  Row b = pixel / HW reads coef_rows[b];
+ * p->coefs and the scalar fields m_x .. store_s are ignored; a store slot outside 0..K-1 stores nothing.  A row whose `active` float
+ * is 0 is neither read nor written: its z, its pixels of every history slot and of both CFG halves of x_next keep their bytes.
+ * Errors without launching: those of imd_unipc_step (but the store checks), coef_rows NULL or not 16-byte aligned. */
+#define IMD_UNIPC_ROW_FLOATS 24     /* per latent row: [0..18] the coefficient block in imd_unipc_params.coefs order,
+                                       [19] active (0: the row is skipped), [20..23] reserved, 0 */
+int imd_unipc_step_rows(const imd_unipc_params* p, const float* coef_rows /* DEVICE [B][24] fp32 */, void* stream);
+/* imd_unipc_step_rows of a COMPACTING session, with the semantics of imd_sampler_step_rows_at.  Addressed by ROW (p->B of them): eps,
+ * x_next (rows r and B + r), coef_rows and p->guidance_rows.  Addressed by SLOT (`slots` of them): z, hist (plane k starts at
+ * hist + k slots HW), mask, z_img and blend_noise.  A row whose block is inactive, or whose slot is outside [0, slots), is skipped
+ * whole; slots that no row names keep their bytes; two rows must not name one slot.  Errors without launching: those of
+ * imd_unipc_step_rows, row_slot NULL or not 4-byte aligned, slots < 1, B > slots. */
+int imd_unipc_step_rows_at(const imd_unipc_params* p, const float* coef_rows /* DEVICE [B][24] fp32 */,
+                           const int* row_slot /* DEVICE [B] */, int slots, void* stream);
 
 /* Pillow-exact resize (+ crop, normalise, layout) of uint8 images on the device; see imd_image_resample_params.  Errors without
  * launching: a foreign struct size, null src / out, C outside {1, 3}, an incomplete table or a skipped axis whose size changes, a
