@@ -163,6 +163,13 @@ class ImageInpaintConditionParams(_Sized):
                 ("B", C.c_int), ("H", C.c_int), ("W", C.c_int), ("dtype", C.c_int)]
 
 
+class ImageMaskFilterParams(_Sized):
+    _fields_ = [("struct_bytes", C.c_uint32), ("src", C.c_void_p), ("src_row_stride", C.c_int64), ("src_img_stride", C.c_int64),
+                ("out", C.c_void_p), ("out_row_stride", C.c_int64), ("out_img_stride", C.c_int64), ("tmp", C.c_void_p), ("bounds", C.c_void_p),
+                ("B", C.c_int), ("H", C.c_int), ("W", C.c_int), ("k", C.c_int), ("blur", C.c_int), ("passes", C.c_int),
+                ("r", C.c_uint32), ("ww", C.c_uint32), ("fw", C.c_uint32), ("flags", C.c_int)]
+
+
 # every symbol include/imagdressing_hip.h declares: name -> (restype, argtypes)
 SYMBOLS = {
     "imd_abi_version": (C.c_int, []),
@@ -215,6 +222,8 @@ SYMBOLS = {
     "imd_image_pack_u8": (C.c_int, [C.POINTER(ImagePackParams), C.c_void_p]),
     "imd_image_overlay": (C.c_int, [C.POINTER(ImageOverlayParams), C.c_void_p]),
     "imd_image_inpaint_condition": (C.c_int, [C.POINTER(ImageInpaintConditionParams), C.c_void_p]),
+    "imd_image_mask_filter": (C.c_int, [C.POINTER(ImageMaskFilterParams), C.c_void_p]),
+    "imd_image_mask_filter_form": (C.c_int, [C.POINTER(ImageMaskFilterParams)]),
     "imd_timestep_embedding": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "imd_add": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_long, C.c_int, C.c_float, C.c_int, C.c_void_p]),
     "imd_embed_tokens": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_long, C.c_int, C.c_int, C.c_void_p]),

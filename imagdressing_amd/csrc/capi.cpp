@@ -362,6 +362,17 @@ int imd_image_inpaint_condition(const imd_image_inpaint_condition_params* p, voi
     return imd_launch_image_inpaint_condition(*p, (hipStream_t)stream);
 }
 
+int imd_image_mask_filter(const imd_image_mask_filter_params* p, void* stream) {
+    IMD_REQUIRE(p != nullptr, "image_mask_filter: null params");
+    IMD_REQUIRE_SIZE(p, "image_mask_filter");
+    return imd_launch_image_mask_filter(*p, (hipStream_t)stream);
+}
+
+int imd_image_mask_filter_form(const imd_image_mask_filter_params* p) {
+    if (!p || p->struct_bytes != sizeof(*p)) return 0;
+    return imd_image_mask_filter_form_of(*p);
+}
+
 int imd_ddim_cfg_step_rows(const imd_ddim_params* p, const float* guidance, void* stream) {
     IMD_REQUIRE(p != nullptr, "ddim_cfg_step_rows: null params");
     IMD_REQUIRE_SIZE(p, "ddim_cfg_step_rows");

@@ -19,6 +19,7 @@ typedef imd_image_resample_params ImageResampleParams;
 typedef imd_image_pack_params ImagePackParams;
 typedef imd_image_overlay_params ImageOverlayParams;
 typedef imd_image_inpaint_condition_params ImageInpaintConditionParams;
+typedef imd_image_mask_filter_params ImageMaskFilterParams;
 
 enum { ACT_NONE = IMD_ACT_NONE, ACT_SILU = IMD_ACT_SILU, ACT_GEGLU = IMD_ACT_GEGLU, ACT_GELU = IMD_ACT_GELU, ACT_QUICK_GELU = IMD_ACT_QUICK_GELU };
 enum { OUT_ROWMAJOR = IMD_OUT_ROWMAJOR, OUT_HEADS = IMD_OUT_HEADS };
@@ -110,6 +111,8 @@ int imd_image_resample_form_of(const ImageResampleParams& p);                   
 int imd_launch_image_pack_u8(const ImagePackParams& p, hipStream_t s);
 int imd_launch_image_overlay(const ImageOverlayParams& p, hipStream_t s);
 int imd_launch_image_inpaint_condition(const ImageInpaintConditionParams& p, hipStream_t s);
+int imd_launch_image_mask_filter(const ImageMaskFilterParams& p, hipStream_t s);      // image_filter.hip
+int imd_image_mask_filter_form_of(const ImageMaskFilterParams& p);                   // launches it would make, 0 = refused
 int imd_launch_timestep_embedding(const float* t, float* out, int B, int dim, hipStream_t s);
 int imd_launch_add(const bf16_t* a, int a_ld, const bf16_t* b, int b_ld, bf16_t* out, int out_ld, long rows, int C, float b_scale, int dtype, hipStream_t s);
 int imd_launch_embed_tokens(const bf16_t* table, int vocab, const bf16_t* pos, int T, const int64_t* ids, bf16_t* out, long rows, int C, int dtype, hipStream_t s);

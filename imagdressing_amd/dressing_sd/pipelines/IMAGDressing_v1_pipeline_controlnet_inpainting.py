@@ -35,15 +35,32 @@ def _pil_images(value, name: str, mode: Optional[str]) -> list:
     return [im if mode is None or im.mode == mode else im.convert(mode) for im in out]
 
 
+def _mask_filter_requests(mask_dilate, mask_blur, R: int):
+    """``mask_dilate`` / ``mask_blur`` of a call, checked -> [(k, b)] * R, or None when every value is 0 (the call is then the one
+    without the arguments).  A list gives one value per request: any other length raises ValueError."""
+    from ...image import mask_filter_values
+
+    def per_request(name, v):
+        if isinstance(v, (list, tuple)):
+            if len(v) != R:
+                raise ValueError(f"{name} has {len(v)} entries for {R} requests (give one value, or one per request)")
+            return list(v)
+        return [v] * R
+    vals = [mask_filter_values(k, b) for k, b in zip(per_request("mask_dilate", mask_dilate), per_request("mask_blur", mask_blur))]
+    return vals if any(k > 0 or b > 0.0 for k, b in vals) else None
+
+
 class _InpaintImages:
     """The person image(s) and mask(s) of a call that crops (``padding_mask_crop``), composites (``overlay``) or builds the inpaint
     condition itself: pair j = (image j, mask j) of request j (one pair: shared), its crop box, and its inputs on either image route --
     the host route through Pillow, the device route (``enable_device_image_io``) from ONE upload of each image as uint8, windows being
     tensor views."""
 
-    def __init__(self, pipe, image, mask_image, size, pad, device):
-        from ...image import get_crop_region
+    def __init__(self, pipe, image, mask_image, size, pad, device, mask_filter=None):
+        from ...image import crop_region_of_bounds, get_crop_region
         self.pipe, self.size, self.device = pipe, size, torch.device(device)          # size = (height, width), VAE multiples
+        self.on_device = bool(getattr(pipe, "_device_image_io", False)) and self.device.type == "cuda"
+        self._up = {}
         self.images, self.masks = _pil_images(image, "image", "RGB"), _pil_images(mask_image, "mask_image", None)
         self.n = max(len(self.images), len(self.masks))
         if len(self.images) not in (1, self.n) or len(self.masks) not in (1, self.n):
@@ -54,10 +71,31 @@ class _InpaintImages:
                 raise ValueError(f"image is {self.image(j).size} and mask_image {self.mask(j).size} (width, height): padding_mask_crop / "
                                  "overlay / control_image=None need them of equal size")
         self.cropped = pad is not None
-        self.boxes = [get_crop_region(self.mask_l(j), size[1], size[0], pad=pad) if self.cropped
-                      else (0, 0) + self.image(j).size for j in range(self.n)]
-        self.on_device = bool(getattr(pipe, "_device_image_io", False)) and self.device.type == "cuda"
-        self._up = {}
+        # mask_dilate / mask_blur on the device route (the host route hands in masks that are filtered already): mask j as "L" is
+        # uploaded once, filtered by imd_image_mask_filter and stands where uploaded("mask_l", j) would; the crop box comes from the
+        # bounds the last launch wrote, ONE copy of 16 bytes per mask for the call.  No reader sees the unfiltered mask.
+        self.filtered = mask_filter is not None
+        bounds = None
+        if self.filtered:
+            if not self.on_device or len(mask_filter) != len(self.masks):
+                raise ValueError("mask_filter: one (dilate, blur) per mask, on the device image route")
+            proc, ups, bnd = pipe._image_processor(), {}, []
+            for j, (k, b) in enumerate(mask_filter):
+                if id(self.masks[j]) not in ups:
+                    ups[id(self.masks[j])] = proc._upload(self.masks_l[j], "L")
+                res = proc.mask_filter(ups[id(self.masks[j])], k, b, bounds=self.cropped)
+                self._up[("mask_l", j)] = res[0] if self.cropped else res
+                if self.cropped:
+                    bnd.append(res[1])
+            self.masks_l = [None] * len(self.masks)               # (nothing may read the unfiltered "L" masks from here on)
+            if self.cropped:
+                bounds = torch.cat(bnd).cpu().tolist()
+        if bounds is not None:
+            self.boxes = [crop_region_of_bounds(bounds[j if len(self.masks) > 1 else 0], *self.image(j).size, size[1], size[0], pad=pad)
+                          for j in range(self.n)]
+        else:
+            self.boxes = [get_crop_region(self.mask_l(j), size[1], size[0], pad=pad) if self.cropped
+                          else (0, 0) + self.image(j).size for j in range(self.n)]
 
     def image(self, j):
         return self.images[j if len(self.images) > 1 else 0]
@@ -93,7 +131,7 @@ class _InpaintImages:
         rows = []
         for j in range(self.n):
             if self.on_device:
-                gray = self.mask(j).mode in ("1", "L")          # (their RGB conversion repeats the one channel)
+                gray = self.filtered or self.mask(j).mode in ("1", "L")          # (their RGB conversion repeats the one channel)
                 view = self.window(self.uploaded("mask_l" if gray else "mask_rgb", j), self.boxes[j])
                 m = self.pipe._image_processor().preprocess(view, size=None, out="nchw", normalize=False, binarize=True,
                                                             mode="L" if gray else "RGB")[:, :1]
@@ -158,6 +196,13 @@ class IMAGDressing_v1(PipelineBase):
     def set_scale(self, scale):
         set_scale_by_type(self.unet, RefSAttnProcessor2_0, scale=scale)
 
+    @property
+    def mask_processor(self):
+        """diffusers' ``pipe.mask_processor``: ``.blur(mask, blur_factor=4)`` -- Pillow for a PIL mask, ``imd_image_mask_filter`` for an
+        uploaded uint8 one (``imagdressing_amd.image.MaskProcessor``)"""
+        from ...image import MaskProcessor
+        return MaskProcessor(self._image_processor)
+
     def _image_latents(self, image, device, generator, size=None):
         """VAE-encode the person image (inherited ``prepare_latents(..., return_image_latents=True)``, :330-346)."""
         p = next(self.vae.parameters())
@@ -211,7 +256,12 @@ class IMAGDressing_v1(PipelineBase):
                  ref_clip_hidden_states: Optional[torch.Tensor] = None, ref_image_latents: Optional[torch.Tensor] = None,
                  image_latents: Optional[torch.Tensor] = None, mask_latents: Optional[torch.Tensor] = None,
                  noise: Optional[torch.Tensor] = None, shard_over_ranks: bool = False, trace: Optional[list] = None,
-                 overlay: bool = False, **kwargs):
+                 mask_dilate: Union[int, List[int]] = 0, mask_blur: Union[float, List[float]] = 0.0, overlay: bool = False, **kwargs):
+        """``mask_dilate`` = k and ``mask_blur`` = b (one value, or a list with one per request; 0: the step is skipped) grow and feather
+        the mask before ANY reader sees it -- the crop box, the binarised latent mask, the built-in inpaint condition, the overlay and
+        the plain route with a caller's ``control_image``: the call equals, byte for byte, the same call given each mask as
+        ``m.convert("L").filter(ImageFilter.MaxFilter(2 k + 1)).filter(ImageFilter.GaussianBlur(b))`` (always "L" first, also for an
+        RGB mask).  Host route: those Pillow calls.  ``enable_device_image_io()``: ``imd_image_mask_filter`` on the uploaded mask."""
         R = self._request_count(dict(prompt=prompt, prompt_embeds=prompt_embeds, negative_prompt=negative_prompt, null_prompt=null_prompt,
                                      negative_prompt_embeds=negative_prompt_embeds, ref_image=ref_image, ref_clip_image=ref_clip_image,
                                      ref_clip_hidden_states=ref_clip_hidden_states, ref_image_latents=ref_image_latents,
@@ -224,6 +274,24 @@ class IMAGDressing_v1(PipelineBase):
         if guess_mode or min_guidance(guidance_scale) <= 1.0 or timesteps:
             raise NotImplementedError("guess_mode, guidance_scale <= 1 and custom timesteps are not implemented "
                                       "(the reference script uses none of them)")
+        # mask_dilate / mask_blur: the host route swaps the filtered "L" masks in for mask_image here, before anything reads it; the
+        # device route filters the uploaded masks (in _InpaintImages, or below for the plain route)
+        mask_filter = _mask_filter_requests(mask_dilate, mask_blur, R)
+        if mask_filter is not None:
+            if mask_image is None:
+                raise ValueError("mask_dilate / mask_blur filter mask_image; mask_latents cannot be dilated or blurred, and no mask_image was given")
+            masks = _pil_images(mask_image, "mask_image", None)
+            if len(masks) not in (1, R):
+                raise ValueError(f"mask_image has {len(masks)} entries for {R} requests (give one, shared, or one per request)")
+            if len(masks) == 1 and len(set(mask_filter)) > 1:
+                masks = masks * R                                             # one mask, filtered differently per request
+            mask_filter = mask_filter[:len(masks)]
+            if getattr(self, "_device_image_io", False) and torch.device(self.device).type == "cuda":
+                mask_image = masks if len(masks) > 1 else masks[0]
+            else:
+                from ...image import mask_filter_host
+                done = [mask_filter_host(m, k, b) for m, (k, b) in zip(masks, mask_filter)]
+                mask_image, mask_filter = (done if len(done) > 1 else done[0]), None
         # padding_mask_crop / overlay / control_image=None (the condition built here): the image and mask as images, one box per request
         front = None
         if padding_mask_crop is not None or overlay or (control_image is None and image is not None and mask_image is not None):
@@ -234,7 +302,8 @@ class IMAGDressing_v1(PipelineBase):
             if overlay and shard_over_ranks:
                 raise NotImplementedError("overlay=True with shard_over_ranks: each rank holds a part of the rows; composite per rank instead")
             vsf = self.vae_scale_factor
-            front = _InpaintImages(self, image, mask_image, (height // vsf * vsf, width // vsf * vsf), padding_mask_crop, self.device)
+            front = _InpaintImages(self, image, mask_image, (height // vsf * vsf, width // vsf * vsf), padding_mask_crop, self.device,
+                                   mask_filter=mask_filter)
             if overlay and output_type == "np" and len({front.image(j).size for j in range(front.n)}) > 1:
                 raise ValueError("overlay=True with output_type='np' needs person images of one size (one array holds them); use 'pil'")
         if not 0.0 < float(strength) <= 1.0:
@@ -289,6 +358,16 @@ class IMAGDressing_v1(PipelineBase):
             lat = self.scheduler.add_noise(il, noise.to(device=device, dtype=torch.float32), t0)
         if mask_latents is None and front is not None and front.cropped:
             mask_latents = front.mask_latents(h, w)
+        elif mask_latents is None and mask_filter is not None:                # (device route: the uploaded masks, filtered; then as below)
+            proc = self._image_processor()
+            if front is not None:                                             # (filtered there already)
+                ups = [front.uploaded("mask_l", j) for j in range(len(front.masks))]
+            else:
+                masks = mask_image if isinstance(mask_image, list) else [mask_image]
+                raw = {id(mk): proc._upload(mk, "L") for mk in {id(mk): mk for mk in masks}.values()}          # (a shared mask is uploaded once)
+                ups = [proc.mask_filter(raw[id(mk)], k, b) for mk, (k, b) in zip(masks, mask_filter)]
+            m = proc.preprocess(ups, size=None, resample="lanczos", out="nchw", normalize=False, binarize=True, multiple=8, mode="L")[:, :1]
+            mask_latents = torch.nn.functional.interpolate((m >= 0.5).float(), size=(h, w))
         elif mask_latents is None:                                            # prepare_mask_latents: nearest resize to h x w
             m = self._image_tensor(as_batch(mask_image, "mask_image"), device, normalize=False, binarize=True)[0][:, :1]
             m = (m >= 0.5).float()

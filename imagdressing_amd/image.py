@@ -10,6 +10,11 @@ applies it on the GPU and fuses what follows the resize on the host today -- cro
 ``inpaint_condition_host`` are the host side of the inpainting front and back end; ``DeviceImageProcessor.overlay`` /
 ``.inpaint_condition`` give the same bytes from the GPU (``imd_image_overlay``, ``imd_image_inpaint_condition``).
 
+``mask_filter_host`` is the host side of the inpainting pipeline's ``mask_dilate`` / ``mask_blur`` (``ImageFilter.MaxFilter`` then
+``ImageFilter.GaussianBlur`` on the "L" mask); ``gaussian_box`` gives the three integers of Pillow's extended box blur (float32, as
+libImaging/BoxBlur.c), ``blur_reference`` / ``dilate_reference`` restate both filters in numpy, and ``DeviceImageProcessor.mask_filter``
+gives Pillow's bytes from the GPU (``imd_image_mask_filter``, csrc/image_filter.hip).  Pinned against Pillow ``PILLOW_PINNED``.
+
 ``DeviceImageProcessor`` is what the pipelines use after ``enable_device_image_io()``: the only host work left per image is
 ``convert("RGB" | "L")``, one copy of the uint8 pixels into pinned memory and their upload; the decoder's output comes back as ONE uint8 copy instead of fp32 NCHW.
 """
@@ -192,9 +197,18 @@ def get_crop_region(mask, width: int, height: int, pad: int = 0) -> Tuple[int, i
     h, w = m.shape
     cols, rows = np.flatnonzero(m.any(axis=0)), np.flatnonzero(m.any(axis=1))
     if cols.size == 0:
+        return crop_region_of_bounds((w, h, -1, -1), w, h, width, height, pad)
+    return crop_region_of_bounds((int(cols[0]), int(rows[0]), int(cols[-1]), int(rows[-1])), w, h, width, height, pad)
+
+
+def crop_region_of_bounds(bounds, w: int, h: int, width: int, height: int, pad: int = 0) -> Tuple[int, int, int, int]:
+    """``get_crop_region`` from the box ``bounds`` = (x_min, y_min, x_max, y_max) of the non-zero pixels of a ``w`` x ``h`` mask (what
+    ``DeviceImageProcessor.mask_filter(bounds=True)`` reads back); (w, h, -1, -1) is the all-zero mask and raises ValueError."""
+    x_min, y_min, x_max, y_max = (int(v) for v in bounds)
+    if x_max < 0 or y_max < 0:
         raise ValueError("get_crop_region: the mask is all zero, there is no region to crop to")
-    crop_left, crop_right = int(cols[0]), w - 1 - int(cols[-1])
-    crop_top, crop_bottom = int(rows[0]), h - 1 - int(rows[-1])
+    crop_left, crop_right = x_min, w - 1 - x_max
+    crop_top, crop_bottom = y_min, h - 1 - y_max
     pad = int(pad)
     x1, y1 = max(crop_left - pad, 0), max(crop_top - pad, 0)
     x2, y2 = min(w - crop_right + pad, w), min(h - crop_bottom + pad, h)
@@ -226,6 +240,102 @@ def get_crop_region(mask, width: int, height: int, pad: int = 0) -> Tuple[int, i
         if x2 >= w:
             x2 = w
     return x1, y1, x2, y2
+
+
+GAUSSIAN_PASSES = 3                      # box blurs per axis of Pillow's GaussianBlur
+PILLOW_PINNED = "12.2.0"                 # the Pillow version the blur / maximum restatement was checked against
+
+
+def gaussian_box(radius: float) -> Tuple[int, int, int]:
+    """(r, ww, fw) of ``ImageFilter.GaussianBlur(radius)``: the integers of its extended box blur (libImaging/BoxBlur.c).  The box
+    radius is FLOAT32 arithmetic as in the C code (the square root and the floor see double operands, their results are stored as
+    float) -- in double precision the integers differ for some radii (0.3 is one).  One pass is then
+    ``out[x] = (ww * sum_{j=-r..r} in[c(x+j)] + fw * (in[c(x-r-1)] + in[c(x+r+1)]) + 2^23) >> 24``."""
+    radius = float(radius)
+    if not math.isfinite(radius) or radius <= 0.0:
+        raise ValueError(f"gaussian_box: the radius must be positive and finite, got {radius}")
+    f = np.float32
+    with np.errstate(over="raise"):
+        sigma2 = f(f(f(radius) * f(radius)) / f(GAUSSIAN_PASSES))
+        L = f(math.sqrt(12.0 * float(sigma2) + 1.0))
+        l = f(math.floor((float(L) - 1.0) / 2.0))
+        a = f(f(f(2) * l + f(1)) * f(f(l * f(l + f(1))) - f(f(3) * sigma2)))
+        a = f(a / f(f(6) * f(sigma2 - f(f(l + f(1)) * f(l + f(1))))))
+        fr = f(l + a)
+        r = int(fr)
+        ww = int(f(f(1 << 24) / f(f(fr * f(2)) + f(1))))
+    fw = (((1 << 24) - (2 * r + 1) * ww) & 0xFFFFFFFF) // 2
+    return r, ww, fw
+
+
+def _box_pass(a: np.ndarray, box: Tuple[int, int, int]) -> np.ndarray:
+    """one extended box blur along the last axis of uint8 ``a``, edges replicated, from an inclusive prefix sum"""
+    r, ww, fw = box
+    n = a.shape[-1]
+    x = np.arange(n)
+    v = a.astype(np.uint64)
+    P = np.concatenate([np.zeros(a.shape[:-1] + (1,), np.uint64), np.cumsum(v, axis=-1)], axis=-1)          # P[i + 1] = sum in[0..i]
+    total = (P[..., np.minimum(x + r, n - 1) + 1] - P[..., np.maximum(x - r - 1, -1) + 1]
+             + np.maximum(0, r - x).astype(np.uint64) * v[..., :1] + np.maximum(0, x + r - n + 1).astype(np.uint64) * v[..., -1:])
+    edges = v[..., np.clip(x - r - 1, 0, n - 1)] + v[..., np.clip(x + r + 1, 0, n - 1)]
+    return ((np.uint64(ww) * total + np.uint64(fw) * edges + np.uint64(1 << 23)) >> np.uint64(24)).astype(np.uint8)
+
+
+def blur_reference(arr: np.ndarray, radius: float) -> np.ndarray:
+    """``Image.filter(ImageFilter.GaussianBlur(radius))`` of uint8 "L" images [..., H, W] by the integer formula, in numpy: three box
+    passes along the rows, then three along the columns, each over the uint8 result of the one before.  radius 0 copies."""
+    arr = np.asarray(arr)
+    if arr.dtype != np.uint8 or arr.ndim < 2:
+        raise ValueError("blur_reference: uint8 [..., H, W] expected")
+    if float(radius) == 0.0:
+        return arr.copy()
+    box = gaussian_box(radius)
+    for _ in range(GAUSSIAN_PASSES):
+        arr = _box_pass(arr, box)
+    arr = np.swapaxes(arr, -1, -2)
+    for _ in range(GAUSSIAN_PASSES):
+        arr = _box_pass(arr, box)
+    return np.ascontiguousarray(np.swapaxes(arr, -1, -2))
+
+
+def dilate_reference(arr: np.ndarray, k: int) -> np.ndarray:
+    """``Image.filter(ImageFilter.MaxFilter(2 k + 1))`` of uint8 "L" images [..., H, W] in numpy: the maximum over the
+    (2k + 1) x (2k + 1) window clipped at the border, one axis after the other.  k = 0 copies."""
+    arr = np.asarray(arr)
+    if arr.dtype != np.uint8 or arr.ndim < 2 or int(k) < 0:
+        raise ValueError("dilate_reference: uint8 [..., H, W] and k >= 0 expected")
+    out = arr.copy()
+    for axis in (-1, -2):
+        a = np.moveaxis(out, axis, -1)
+        n = a.shape[-1]
+        res = a.copy()
+        for d in range(1, min(int(k), n - 1) + 1):
+            res[..., d:] = np.maximum(res[..., d:], a[..., :-d])
+            res[..., :-d] = np.maximum(res[..., :-d], a[..., d:])
+        out = np.ascontiguousarray(np.moveaxis(res, -1, axis))
+    return out
+
+
+def mask_filter_values(dilate, blur) -> Tuple[int, float]:
+    """(dilate, blur) of one mask, checked: a non-negative integer and a non-negative finite radius"""
+    if isinstance(dilate, bool) or not isinstance(dilate, (int, np.integer)) or int(dilate) < 0:
+        raise ValueError(f"mask_dilate must be a non-negative integer (the window is 2k + 1 pixels), got {dilate!r}")
+    if isinstance(blur, bool) or not isinstance(blur, (int, float, np.integer, np.floating)) or not math.isfinite(float(blur)) or float(blur) < 0:
+        raise ValueError(f"mask_blur must be a non-negative finite radius, got {blur!r}")
+    return int(dilate), float(blur)
+
+
+def mask_filter_host(mask, dilate: int = 0, blur: float = 0.0):
+    """The host route of ``mask_dilate`` / ``mask_blur``: ``mask`` (PIL image of any mode, or a uint8 array) as "L", then
+    ``ImageFilter.MaxFilter(2 dilate + 1)`` and ``ImageFilter.GaussianBlur(blur)``; a step whose value is 0 is skipped -> PIL "L" image"""
+    from PIL import Image, ImageFilter
+    dilate, blur = mask_filter_values(dilate, blur)
+    m = mask.convert("L") if _is_pil(mask) else Image.fromarray(mask_as_l(mask))
+    if dilate > 0:
+        m = m.filter(ImageFilter.MaxFilter(2 * dilate + 1))
+    if blur > 0.0:
+        m = m.filter(ImageFilter.GaussianBlur(blur))
+    return m
 
 
 def overlay_reference(orig: np.ndarray, gen: np.ndarray, mask: np.ndarray, box: Tuple[int, int, int, int]) -> np.ndarray:
@@ -379,6 +489,22 @@ class DeviceImageProcessor:
             img, m = img[:, y1:y2, x1:x2, :], m[:, y1:y2, x1:x2, :]
         return ops.image_inpaint_condition(resize_to(img, size, "lanczos"), resize_to(m, size, "lanczos"), self.dtype)
 
+    def mask_filter(self, mask_u8, dilate: int = 0, blur: float = 0.0, bounds: bool = False, out: Optional[torch.Tensor] = None):
+        """``mask_filter_host`` on the device: ``mask_u8`` ("L": PIL / uint8 [H, W], [1 | B, H, W, 1] or an uploaded tensor of that
+        shape) through ``ImageFilter.MaxFilter(2 dilate + 1)`` and ``ImageFilter.GaussianBlur(blur)``, Pillow's bytes, a step whose
+        value is 0 skipped -> uint8 [B, H, W, 1] on the device.  ``bounds``: -> (mask, int32 [B, 4] on the device) with
+        (x_min, y_min, x_max, y_max) of its non-zero pixels, (W, H, -1, -1) when there is none (``crop_region_of_bounds``)."""
+        dilate, blur = mask_filter_values(dilate, blur)
+        if not isinstance(mask_u8, torch.Tensor) and not _is_pil(mask_u8):
+            mask_u8 = mask_as_l(mask_u8)
+        m = self._upload(mask_u8, "L")
+        src = m[..., 0]
+        dst = None if out is None else (out[..., 0] if out.dim() == 4 else out)
+        res = ops.image_mask_filter(src, dilate, gaussian_box(blur) if blur > 0.0 else None, out=dst, bounds=bounds)
+        if bounds:
+            return res[0].unsqueeze(-1), res[1]
+        return res.unsqueeze(-1)
+
     # ---- output ----
     def overlay(self, decoded: torch.Tensor, orig, mask, box: Tuple[int, int, int, int], out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """``overlay_host`` on the device: uint8 ``decoded`` [B, H, W, 3] (``pack``) resized to ``box`` = (x1, y1, x2, y2) with Lanczos and
@@ -405,5 +531,37 @@ class DeviceImageProcessor:
         return [Image.fromarray(a) for a in arr]
 
 
+class MaskProcessor:
+    """``pipe.mask_processor``: diffusers' name for the mask side of ``VaeImageProcessor``.  ``blur(image, blur_factor)`` is
+    ``image.filter(ImageFilter.GaussianBlur(blur_factor))``: Pillow on the host for a PIL image (its mode kept, as diffusers does), the
+    same bytes from the GPU for an uploaded uint8 mask ([H, W], [B, H, W] or [B, H, W, 1] on the device; the shape is kept)."""
+
+    def __init__(self, processor=None):
+        self._processor = processor            # () -> DeviceImageProcessor, asked for only when a device tensor comes
+
+    def _device(self, image: torch.Tensor, dilate: int, blur: float) -> torch.Tensor:
+        if not image.is_cuda or image.dtype != torch.uint8 or image.dim() not in (2, 3, 4) or (image.dim() == 4 and image.shape[-1] != 1):
+            raise TypeError(f"mask_processor takes PIL images or uploaded uint8 [H, W], [B, H, W] or [B, H, W, 1] masks, got "
+                            f"{image.dtype} {tuple(image.shape)} on {image.device}")
+        proc = self._processor() if self._processor is not None else DeviceImageProcessor(image.device)
+        m = image if image.dim() == 4 else (image[None, ..., None] if image.dim() == 2 else image[..., None])
+        return proc.mask_filter(m, dilate, blur).reshape(image.shape)
+
+    def blur(self, image, blur_factor: float = 4):
+        if isinstance(image, torch.Tensor):
+            return self._device(image, 0, mask_filter_values(0, blur_factor)[1])
+        from PIL import ImageFilter
+        return image.filter(ImageFilter.GaussianBlur(blur_factor))
+
+    def dilate(self, image, k: int = 1):
+        """``image.filter(ImageFilter.MaxFilter(2 k + 1))``, host or device as ``blur``"""
+        if isinstance(image, torch.Tensor):
+            return self._device(image, mask_filter_values(k, 0.0)[0], 0.0)
+        from PIL import ImageFilter
+        return image.filter(ImageFilter.MaxFilter(2 * int(k) + 1)) if int(k) > 0 else image.copy()
+
+
 __all__ = ["resample_tables", "resample_reference", "tile_rows", "device_tables", "resize_to", "DeviceImageProcessor", "CLIP_MEAN", "CLIP_STD",
-           "get_crop_region", "mask_as_l", "overlay_reference", "overlay_host", "inpaint_condition_host"]
+           "get_crop_region", "crop_region_of_bounds", "mask_as_l", "overlay_reference", "overlay_host", "inpaint_condition_host",
+           "gaussian_box", "blur_reference", "dilate_reference", "mask_filter_host", "mask_filter_values", "MaskProcessor", "GAUSSIAN_PASSES",
+           "PILLOW_PINNED"]

@@ -1444,7 +1444,9 @@ IMAGE_U8, IMAGE_F32_NCHW, IMAGE_16_NHWC8 = 0, 1, 2          # IMD_IMG_*
 IMAGE_FORCE_TWO_PASS = 1                                    # IMD_IMG_FORCE_TWO_PASS
 IMAGE_TILE_W, IMAGE_TILE_H, IMAGE_LDS_BYTES = 32, 8, 32768  # IMD_IMG_TILE_W / _TILE_H / _LDS_BYTES
 IMAGE_IO_COUNTER = {"resample": 0, "resample_single": 0, "resample_two_pass": 0, "pack_u8": 0, "overlay": 0,
-                    "inpaint_condition": 0}                 # calls made (tests, tools/image_io_bench.py, tools/inpaint_overlay_bench.py)
+                    "inpaint_condition": 0, "mask_filter": 0, "mask_filter_launches": 0}          # calls made (tests, tools/*_bench.py)
+IMAGE_MASK_LINE_MAX = 16384                                 # IMD_IMG_MASK_LINE_MAX
+IMAGE_MASK_FORCE_GLOBAL = 1                                 # IMD_IMG_MASK_FORCE_GLOBAL
 
 
 def image_resample(src: torch.Tensor, size: Tuple[int, int], table_h: Optional[dict], table_v: Optional[dict], *, kind: int = IMAGE_U8,
@@ -1584,6 +1586,47 @@ def image_inpaint_condition(image: torch.Tensor, mask: torch.Tensor, dtype) -> t
     L.check(L.load().imd_image_inpaint_condition(C.byref(p), _stream()))
     IMAGE_IO_COUNTER["inpaint_condition"] += 1
     return out
+
+
+def image_mask_filter(src: torch.Tensor, dilate: int = 0, box: Optional[Tuple[int, int, int]] = None, *, out: Optional[torch.Tensor] = None,
+                      bounds: bool = False, passes: int = 3, _force_global: bool = False):
+    """``ImageFilter.MaxFilter(2 dilate + 1)`` then ``ImageFilter.GaussianBlur`` of uint8 ``src`` [B, H, W] (rows and images may be
+    strided, the bytes of a row are contiguous) -> uint8 [B, H, W], Pillow's bytes.  ``box`` = ``image.gaussian_box(radius)`` =
+    (r, ww, fw), None: no blur; ``dilate`` = 0: no maximum.  ``out`` may be ``src`` (in place).  ``bounds``: also return int32 [B, 4] =
+    (x_min, y_min, x_max, y_max) of the non-zero output pixels, (W, H, -1, -1) for an all-zero image -> (out, bounds)."""
+    if not isinstance(src, torch.Tensor) or not src.is_cuda:
+        raise L.ImdError(f"src: tensor is on {getattr(src, 'device', type(src))}; imagdressing_amd runs on MI355X only (no CPU path)")
+    if src.dtype != torch.uint8 or src.dim() != 3 or (src.shape[2] > 1 and src.stride(2) != 1):
+        raise L.ImdError(f"src: expected uint8 [B, H, W] with contiguous rows, got {src.dtype} {tuple(src.shape)} strides {src.stride()}")
+    ensure_device(src.device)
+    B, H, W = (int(v) for v in src.shape)
+    if out is None:
+        out = torch.empty(B, H, W, dtype=torch.uint8, device=src.device)
+    elif (not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or out.device != src.device or tuple(out.shape) != (B, H, W)
+          or (W > 1 and out.stride(2) != 1)):
+        raise L.ImdError(f"out: expected uint8 {(B, H, W)} with contiguous rows on {src.device}, got {getattr(out, 'dtype', None)} "
+                         f"{tuple(getattr(out, 'shape', ()))}")
+    p = L.ImageMaskFilterParams()
+    p.src, p.src_row_stride, p.src_img_stride = src.data_ptr(), src.stride(1), src.stride(0)
+    p.out, p.out_row_stride, p.out_img_stride = out.data_ptr(), out.stride(1), out.stride(0)
+    p.B, p.H, p.W, p.k, p.passes = B, H, W, int(dilate), int(passes)
+    if box is not None:
+        p.blur = 1
+        p.r, p.ww, p.fw = (int(v) for v in box)
+    tmp = None
+    if _force_global or H > IMAGE_MASK_LINE_MAX or W > IMAGE_MASK_LINE_MAX:
+        tmp = torch.empty(B, H, W, dtype=torch.uint8, device=src.device)
+        p.tmp = tmp.data_ptr()
+        p.flags = IMAGE_MASK_FORCE_GLOBAL if _force_global else 0
+    bnd = torch.empty(B, 4, dtype=torch.int32, device=src.device) if bounds else None
+    if bnd is not None:
+        p.bounds = bnd.data_ptr()
+    lib = L.load()
+    form = lib.imd_image_mask_filter_form(C.byref(p))
+    L.check(lib.imd_image_mask_filter(C.byref(p), _stream()))
+    IMAGE_IO_COUNTER["mask_filter"] += 1
+    IMAGE_IO_COUNTER["mask_filter_launches"] += form
+    return (out, bnd) if bounds else out
 
 
 def timestep_embedding(t: torch.Tensor, dim: int) -> torch.Tensor:

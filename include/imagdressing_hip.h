@@ -444,6 +444,44 @@ typedef struct imd_image_inpaint_condition_params {
     int dtype;             /* IMD_DTYPE_* of out */
 } imd_image_inpaint_condition_params;
 
+/* Mask growing and feathering on the device (imd_image_mask_filter): Pillow's ImageFilter.MaxFilter(2k + 1) followed by
+ * ImageFilter.GaussianBlur(radius) on uint8 "L" images, byte for byte, integer only.
+ *   window maximum (k >= 1):  out[y][x] = max of in over [y - k, y + k] x [x - k, x + k] clipped at the border (separable)
+ *   Gaussian (blur != 0):     Pillow's three extended box blurs per axis.  The caller computes the box in FLOAT32 with passes = 3:
+ *       sigma2 = radius * radius / passes;  L = sqrt(12 sigma2 + 1);  l = floor((L - 1) / 2)
+ *       a = (2l + 1)(l (l + 1) - 3 sigma2) / (6 (sigma2 - (l + 1)(l + 1)));  fr = l + a
+ *       r = int(fr);  ww = uint32(float32(2^24) / (fr * 2 + 1));  fw = (2^24 - (2r + 1) ww) / 2
+ *     and one pass along a line of n samples, indices clamped to [0, n - 1] (edge replication), is
+ *       out[x] = (ww * sum_{j = -r..r} in[c(x + j)] + fw * (in[c(x - r - 1)] + in[c(x + r + 1)]) + 2^23) >> 24
+ *     in uint32 (every intermediate is below 2^32).  Three passes along rows, then three along columns, each over the uint8 result
+ *     of the one before.  Any r, also r >= n.
+ * src and out are [B, H, W] with row and image strides in bytes; out may be src (in place).  No pointer needs any alignment.
+ * bounds (optional, int32 [B][4]): (x_min, y_min, x_max, y_max) of the non-zero pixels of out, (W, H, -1, -1) for an all-zero image.
+ * Launches: one per axis and step through LDS -- columns (maximum), rows (maximum and the three row passes), columns (the three
+ * column passes); two for one step alone; plus one that initialises bounds -- at most 4.  A line (row or column) longer than
+ * IMD_IMG_MASK_LINE_MAX bytes, or IMD_IMG_MASK_FORCE_GLOBAL, takes one launch per pass through tmp, uint8 [B, H, W] contiguous
+ * (needed only then).  imd_image_mask_filter_form answers the number of launches without launching, 0 = refused.
+ * Refused: null pointers (src / out; tmp where it is needed), an empty image, a stride below the row / image, blur with passes != 3,
+ * k < 0, ww / fw inconsistent with r ((2r + 1) ww + 2 fw must be 2^24 or 2^24 - 1), an image of more than 2^31 bytes. */
+#define IMD_IMG_MASK_LINE_MAX 16384
+#define IMD_IMG_MASK_FORCE_GLOBAL 1
+typedef struct imd_image_mask_filter_params {
+    uint32_t struct_bytes;   /* sizeof(imd_image_mask_filter_params) in the caller's view; checked on entry */
+    const uint8_t* src;      /* uint8 [B, H, W] */
+    int64_t src_row_stride;  /* bytes between rows of src (>= W) */
+    int64_t src_img_stride;  /* bytes between images of src */
+    uint8_t* out;            /* uint8 [B, H, W]; may be src */
+    int64_t out_row_stride, out_img_stride;
+    uint8_t* tmp;            /* uint8 [B, H, W] contiguous; only for the one-launch-per-pass form */
+    int32_t* bounds;         /* optional int32 [B][4] */
+    int B, H, W;
+    int k;                   /* half-width of the window maximum; 0: skipped */
+    int blur;                /* 0: the Gaussian is skipped */
+    int passes;              /* box blurs per axis of the Gaussian: 3 */
+    uint32_t r, ww, fw;      /* the box, see above */
+    int flags;               /* IMD_IMG_MASK_FORCE_GLOBAL */
+} imd_image_mask_filter_params;
+
 /* library / device */
 int imd_abi_version(void);
 const char* imd_last_error(void);
@@ -669,6 +707,10 @@ int imd_image_pack_u8(const imd_image_pack_params* p, void* stream);
 int imd_image_overlay(const imd_image_overlay_params* p, void* stream);
 /* uint8 image + mask -> the inpainting ControlNet's 16-bit NHWC8 condition; see imd_image_inpaint_condition_params. */
 int imd_image_inpaint_condition(const imd_image_inpaint_condition_params* p, void* stream);
+/* MaxFilter(2k + 1) then GaussianBlur of uint8 masks, Pillow's bytes; see imd_image_mask_filter_params.  Errors without launching.
+ * imd_image_mask_filter_form: the number of launches imd_image_mask_filter would make for *p, 0 when it would refuse. */
+int imd_image_mask_filter(const imd_image_mask_filter_params* p, void* stream);
+int imd_image_mask_filter_form(const imd_image_mask_filter_params* p);
 
 /* diffusers Timesteps(dim, flip_sin_to_cos=True, freq_shift=0): out[B, dim] fp32 = [cos | sin]. */
 int imd_timestep_embedding(const float* t, float* out, int B, int dim, void* stream);
