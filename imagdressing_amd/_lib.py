@@ -135,6 +135,12 @@ class UnipcParams(_Sized):
     ]
 
 
+class LoraRowsParams(_Sized):
+    _fields_ = [("struct_bytes", C.c_uint32), ("x", C.c_void_p), ("down", C.c_void_p), ("row_scale", C.c_void_p), ("out", C.c_void_p),
+                ("M", C.c_int), ("C", C.c_int), ("T", C.c_int), ("E", C.c_int), ("rows_per_entry", C.c_int),
+                ("x_ld", C.c_int), ("out_ld", C.c_int), ("dtype", C.c_int)]
+
+
 class ImageResampleParams(_Sized):
     _fields_ = [("struct_bytes", C.c_uint32),
         ("src", C.c_void_p), ("src_row_stride", C.c_int64), ("src_img_stride", C.c_int64), ("out", C.c_void_p), ("tmp", C.c_void_p),
@@ -216,6 +222,7 @@ SYMBOLS = {
     "imd_unipc_step": (C.c_int, [C.POINTER(UnipcParams), C.c_void_p]),
     "imd_unipc_step_rows": (C.c_int, [C.POINTER(UnipcParams), C.c_void_p, C.c_void_p]),
     "imd_unipc_step_rows_at": (C.c_int, [C.POINTER(UnipcParams), C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "imd_lora_expand_rows": (C.c_int, [C.POINTER(LoraRowsParams), C.c_void_p]),
     "imd_session_input_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "imd_image_resample": (C.c_int, [C.POINTER(ImageResampleParams), C.c_void_p]),
     "imd_image_resample_form": (C.c_int, [C.POINTER(ImageResampleParams)]),

@@ -29,6 +29,10 @@ Extensions over the reference (all optional, all default to reference behaviour)
     :602-603 is only defined for B == 1).
   * ``encoder_hidden_states`` with fewer rows than ``hidden_states`` is shared by contiguous groups
     of batch rows.
+  * ``lora_rows`` / ``ip_scale_rows`` (keywords of the LoRA and IP-Adapter processors; the pipelines pass them
+    as ``s_lora_rows`` / ``c_lora_rows`` / ``ip_scale_rows`` in the cross_attention_kwargs): fp32 [B] device
+    tensors read INSTEAD of ``lora_scale`` / ``scale`` -- one value per batch row.  The LoRA then runs
+    unfolded, y = [x | s_row (x D^T)] [W | U]^T (``ops.lora_expand_rows`` + the existing projections).
 """
 from __future__ import annotations
 
@@ -199,6 +203,15 @@ def _project_kv(tokens: torch.Tensor, wkv: torch.Tensor, heads: int):
     return k, vt, Lk, LP
 
 
+def _check_rows(rows, n: int, name: str, device) -> torch.Tensor:
+    """a per-row scale tensor of the engine-side keywords: fp32 [n], contiguous, on the device"""
+    if not isinstance(rows, torch.Tensor) or rows.dtype != torch.float32 or rows.dim() != 1 or rows.numel() != n \
+            or rows.device != device or not rows.is_contiguous():
+        raise ValueError(f"{name} must be a contiguous fp32 tensor of {n} values (one per row of the CFG batch) on {device}, got "
+                         f"{tuple(rows.shape) if isinstance(rows, torch.Tensor) else type(rows)}")
+    return rows
+
+
 _FP8_KV: Dict[int, tuple] = {}          # (dropped by ops.clear_workspaces(): it pins the 16-bit K and the e4m3 K / V^T of every layer)
 ops._clear_hooks.append(_FP8_KV.clear)
 
@@ -224,14 +237,21 @@ def _fp8_kv(kv, cache: bool):
 def _fused_attention(x: torch.Tensor, heads: int, *, wq_or_qkv: torch.Tensor, self_attn: bool,
                      kv1=None, kv1_bdiv: int = 1, kv2=None, kv2_bdiv: int = 1, scale2: Optional[torch.Tensor] = None,
                      wo: torch.Tensor, bo: Optional[torch.Tensor], residual: Optional[torch.Tensor],
-                     q_ln: Optional[tuple] = None, pair_half: bool = False, phase2_rows: int = 0) -> torch.Tensor:
+                     q_ln: Optional[tuple] = None, pair_half: bool = False, phase2_rows: int = 0,
+                     lora: Optional[dict] = None) -> torch.Tensor:
     """x [B, N, C] bf16 -> out-projected attention output [B, N, C] (+ residual).  ``q_ln`` = (W_q', b_q', eps): ``x`` is the
     block's UN-normalised hidden state and LayerNorm runs inside the Q projection (cross-attention, C = 320 only).
     ``pair_half`` (self-attention with a garment key set only): ``x`` holds the B cond rows of a CFG batch whose uncond rows have
     bit-identical hidden states; the result has 2B rows -- [0, B) the hybrid output, [B, 2B) the plain self-attention output of
     the same rows (the attention launch stores its first phase twice, ``imd_attn_params.out_dup``) -- and ``residual`` has 2B rows, or B (the same block input for both halves, one copy).
     ``phase2_rows`` = R: exactly the rows [0, R) carry the second key set (``scale2`` non-zero): ops.attention may run their two softmaxes as separate
-    workgroups (``imd_attn_params.phase2_rows``; bit-identical)."""
+    workgroups (``imd_attn_params.phase2_rows``; bit-identical).
+    ``lora`` = dict(d_in, d_out, rows_in, rows_out): per-row LoRA scales, the low-rank path unfolded (csrc/lora_rows.hip).  ``wq_or_qkv`` / ``wo``
+    are then the augmented weights [W | U] (:meth:`_LoraFold._unfolded`), ``d_in`` / ``d_out`` the stacked down matrices of the two projections,
+    ``rows_in`` / ``rows_out`` fp32 device tensors with one scale per image of ``x`` / of the result (they differ under ``pair_half`` only).  One
+    ``ops.lora_expand_rows`` launch in front of each projection writes [x | s_row (x D^T)]; the projection launches are the ones below with Cin grown
+    by the tail.  Every width C + T the models produce is a multiple of 16, which the dispatcher takes as it is: nothing is padded beyond the tail
+    itself (T rounded up to 16, zero columns).  The fused routes (LayerNorm prologue, one-launch text attention, FUSED_OUT_PROJ) are not taken."""
     B, N, Cc = x.shape
     D = Cc // heads
     dpk, dpv = ops.attn_padded_dims(D)
@@ -239,6 +259,8 @@ def _fused_attention(x: torch.Tensor, heads: int, *, wq_or_qkv: torch.Tensor, se
     qscale = D ** -0.5 * LOG2E
     # text cross-attention of a 64x64-level block (norm2 fused, one key set of <= 96 keys, residual = the block state itself): norm2 -> to_q ->
     # attention -> to_out + residual as ONE launch (csrc/row_xattn.hip); Q and O never exist in memory.  Everything else: the three launches below.
+    if lora is not None and q_ln is not None:
+        raise NotImplementedError("per-row LoRA scales together with a LayerNorm folded into the projection weights")
     if (ops.FUSED_XATTN and not self_attn and q_ln is not None and kv1 is not None and kv2 is None and not pair_half
             and ops.text_xattn_supported(Cc, heads, N, kv1[2]) and not ops.ATTN_FP8 and not ops.FUSED_OUT_PROJ
             and residual is not None and residual.data_ptr() == x.data_ptr() and residual.shape == x.shape
@@ -247,6 +269,15 @@ def _fused_attention(x: torch.Tensor, heads: int, *, wq_or_qkv: torch.Tensor, se
                               Lk=kv1[2], kv_bdiv=kv1_bdiv, ln_eps=q_ln[2], q_scale=qscale)
     q = ops.workspace("attn_q", (B, heads, N, dpk), dt, dev)
     x2 = x.view(B * N, Cc)
+    Cin = Cc
+
+    def out_proj(o2, res2):
+        if lora is not None:
+            o2 = ops.lora_expand_rows(o2, lora["d_out"], lora["rows_out"], N)
+        return ops.linear(o2, wo, bo, res=res2)
+    if lora is not None:
+        x2 = ops.lora_expand_rows(x2, lora["d_in"], lora["rows_in"], N)
+        Cin = x2.shape[1]
     if self_attn:
         LP = ops.pad64(N)
         k = ops.k_buffer((B, heads, N, dpk), D, dt, dev, tag="attn_k")
@@ -255,13 +286,13 @@ def _fused_attention(x: torch.Tensor, heads: int, *, wq_or_qkv: torch.Tensor, se
         if q_ln is not None:          # x is the un-normalised block state: norm1 runs inside the projection (row_qkv.hip)
             ops.conv_gemm(x2, q_ln[0], M=B * N, N=3 * Cc, Cin=Cc, Hin=N, Win=1, Hout=N, Wout=1, bias=q_ln[1], ln_eps=q_ln[2], heads=dests)
         else:
-            ops.conv_gemm(x2, wq_or_qkv, M=B * N, N=3 * Cc, Cin=Cc, Hin=N, Win=1, Hout=N, Wout=1, heads=dests)
+            ops.conv_gemm(x2, wq_or_qkv, M=B * N, N=3 * Cc, Cin=Cin, Hin=N, Win=1, Hout=N, Wout=1, heads=dests)
         kv1, kv1_bdiv = (k, vt, N, LP), 1
     elif q_ln is not None:
         ops.conv_gemm(x2, q_ln[0], M=B * N, N=Cc, Cin=Cc, Hin=N, Win=1, Hout=N, Wout=1, bias=q_ln[1], ln_eps=q_ln[2],
                       heads=dict(C=Cc, H=heads, D=D, dests=[(q, 0, dpk, N, qscale)]))
     else:
-        ops.conv_gemm(x2, wq_or_qkv, M=B * N, N=Cc, Cin=Cc, Hin=N, Win=1, Hout=N, Wout=1,
+        ops.conv_gemm(x2, wq_or_qkv, M=B * N, N=Cc, Cin=Cin, Hin=N, Win=1, Hout=N, Wout=1,
                       heads=dict(C=Cc, H=heads, D=D, dests=[(q, 0, dpk, N, qscale)]))
     o = torch.empty(B, N, Cc, dtype=dt, device=dev)
     if ops.ATTN_FP8 and D == 40:            # BASELINE configs[4]: level-0 attention on the MX-FP8 MFMA (opt-in)
@@ -274,12 +305,12 @@ def _fused_attention(x: torch.Tensor, heads: int, *, wq_or_qkv: torch.Tensor, se
             kw = dict(k2=k28, v2t=v28, L2=kv2[2], L2P=kv2[3], kv2_bdiv=kv2_bdiv, scale2=scale2)
         ops.attention_fp8(q8, k18, v18, o, B=B, H=heads, N=N, L1=kv1[2], L1P=kv1[3], kv1_bdiv=kv1_bdiv, **kw)
         res2 = None if residual is None else residual.view(B * N, Cc)
-        return ops.linear(o.view(B * N, Cc), wo, bo, res=res2).view(B, N, Cc)
+        return out_proj(o.view(B * N, Cc), res2).view(B, N, Cc)
     kw = {}
     if kv2 is not None and scale2 is not None:
         kw = dict(k2=kv2[0], v2t=kv2[1], L2=kv2[2], L2P=kv2[3], kv2_bdiv=kv2_bdiv, scale2=scale2)
     # every K operand on this path comes from ops.k_buffer (pad column = 1): the d = 40 kernel may stage by LDS-DMA
-    if ops.FUSED_OUT_PROJ and ops.attention_proj_supported(heads, N, D):
+    if ops.FUSED_OUT_PROJ and lora is None and ops.attention_proj_supported(heads, N, D):
         # the 64x64-level blocks: to_out[0] + bias + residual ride in the attention launch (ABI v7) -- the hybrid block is TWO launches
         out = torch.empty(B, N, Cc, dtype=dt, device=dev)
         return ops.attention(q, kv1[0], kv1[1], o, B=B, H=heads, N=N, D=D, L1=kv1[2], L1P=kv1[3], kv1_bdiv=kv1_bdiv, k_pad_one=True,
@@ -290,10 +321,10 @@ def _fused_attention(x: torch.Tensor, heads: int, *, wq_or_qkv: torch.Tensor, se
                       out_dup=o[B:], **kw)
         # (the residual may hold B or 2B rows: B = one copy for both halves, added periodically by the projection -- ops.conv_gemm)
         res2 = None if residual is None else residual.reshape(-1, Cc)
-        return ops.linear(o.view(2 * B * N, Cc), wo, bo, res=res2).view(2 * B, N, Cc)
+        return out_proj(o.view(2 * B * N, Cc), res2).view(2 * B, N, Cc)
     ops.attention(q, kv1[0], kv1[1], o, B=B, H=heads, N=N, D=D, L1=kv1[2], L1P=kv1[3], kv1_bdiv=kv1_bdiv, k_pad_one=True, phase2_rows=phase2_rows if kw else 0, **kw)
     res2 = None if residual is None else residual.view(B * N, Cc)
-    return ops.linear(o.view(B * N, Cc), wo, bo, res=res2).view(B, N, Cc)
+    return out_proj(o.view(B * N, Cc), res2).view(B, N, Cc)
 
 
 class _FusedBase:
@@ -456,12 +487,26 @@ class RefSAttnProcessor2_0(nn.Module, _FusedBase, _RefMixin):
 
     def __call__(self, attn, hidden_states, encoder_hidden_states=None, attention_mask=None, temb=None, scale=1.0,
                  num_images_per_prompt=1, cond_hidden_states=None, sa_hidden_states=None, sa_batch_mask=None,
-                 imd_residual=None, imd_layernorm=None, imd_pair_half=False, **kwargs):
+                 imd_residual=None, imd_layernorm=None, imd_pair_half=False, lora_rows=None, **kwargs):
         if encoder_hidden_states is not None:
             raise NotImplementedError(f"{type(self).__name__} is a self-attention (attn1) processor")
         dt = _compute_dtype(attn, hidden_states, attention_mask)
         x, shape4 = _as_tokens(hidden_states, dt)
-        wqkv, wo, bo = self._weights(attn, dt, x.device)
+        # engine-side extension of the LoRA siblings: ``lora_rows`` (the pipelines pass it as ``s_lora_rows``, attn1 and attn2 share one kwargs
+        # dict), fp32 [2B] on the device -- the LoRA scale of every row of the CFG batch, read INSTEAD of ``lora_scale``; the low-rank path then
+        # runs unfolded (_fused_attention ``lora``).  Under imd_pair_half x holds the B cond rows, whose entries are the first B.
+        rows = lora_rows if lora_rows is not None else kwargs.get("s_lora_rows")
+        lora = None
+        if rows is not None and isinstance(self, _LoraFold):
+            nrows = x.shape[0] * (2 if imd_pair_half else 1)
+            rows = _check_rows(rows, nrows, "lora_rows", x.device)
+            u = self._unfolded(attn, x.device, dt)
+            if u["qkv"] is None:
+                raise NotImplementedError("per-row LoRA scales on a self-attention whose k / v width differs from its q width")
+            wqkv, wo, bo = u["qkv"], u["o"], _layer_weights(attn, "bo", dt, x.device)
+            lora = dict(d_in=u["d_qkv"], d_out=u["d_o"], rows_in=rows[:x.shape[0]], rows_out=rows)
+        else:
+            wqkv, wo, bo = self._weights(attn, dt, x.device)
         q_ln = None
         if imd_layernorm is not None:
             g, be, eps = imd_layernorm
@@ -484,7 +529,7 @@ class RefSAttnProcessor2_0(nn.Module, _FusedBase, _RefMixin):
         #  of the cond rows over workgroups)
         pr = x.shape[0] // 2 if (kwargs.get("sa_pair_layout") and sa_batch_mask is not None and kv2 is not None and not imd_pair_half and x.shape[0] % 2 == 0) else 0
         out = _fused_attention(x, attn.heads, wq_or_qkv=wqkv, self_attn=True, kv2=kv2, kv2_bdiv=bdiv2,
-                               scale2=s2, wo=wo, bo=bo, residual=imd_residual, q_ln=q_ln, pair_half=bool(imd_pair_half), phase2_rows=pr)
+                               scale2=s2, wo=wo, bo=bo, residual=imd_residual, q_ln=q_ln, pair_half=bool(imd_pair_half), phase2_rows=pr, lora=lora)
         return self._finish(attn, out, imd_residual is not None, hidden_states, shape4, ln_fused=imd_layernorm is not None)
 
 
@@ -499,11 +544,53 @@ class _LoraFold:
         self.to_v_lora = LoRALinearLayer(kdim, hidden_size, rank, network_alpha)
         self.to_out_lora = LoRALinearLayer(hidden_size, hidden_size, rank, network_alpha)
         self._folded = _TensorCache()
+        self._unfold = _TensorCache()
+
+    def _lora_srcs(self, attn):
+        return tuple(l.weight for lo in (self.to_q_lora, self.to_k_lora, self.to_v_lora, self.to_out_lora)
+                     for l in (lo.down, lo.up)) + (attn.to_q.weight, attn.to_k.weight, attn.to_v.weight, attn.to_out[0].weight)
+
+    def _unfolded(self, attn, device, dtype):
+        """The augmented weights of the per-row route, y = [x | s_row (x D^T)] [W | U]^T: per projection launch ``[W | U]`` (network_alpha / rank
+        folded into U) and the stacked down matrices D.  A launch that serves G projections (q / k / v: G = 3, the text k / v pair: G = 2) is
+        block-structured: projection g sees its own U in tail columns [g r, (g + 1) r) and zeros in the others.  Built once per layer and cached
+        like the folded weights, keyed on tensor identity / version -- NOT on a scale: that lives in the activations.  The tail is padded with
+        zero rows of D / zero columns of U to a multiple of 16 (rank 4 .. 8 adapters)."""
+        srcs = self._lora_srcs(attn)
+        w = self._unfold.get(srcs, extra=(dtype, str(device)))
+        if w is None:
+            r = self.rank
+
+            def aug(bases, loras):
+                G = len(bases)
+                T = (G * r + 15) // 16 * 16
+                if T > 384:
+                    raise NotImplementedError(f"per-row LoRA scales: {G} x rank {r} exceeds the 384 tail columns of imd_lora_expand_rows")
+                rows, downs = [], []
+                for g_, (b, lo) in enumerate(zip(bases, loras)):
+                    u = lo.up.weight.detach().float().to(device)
+                    if lo.network_alpha is not None:
+                        u = u * (lo.network_alpha / lo.rank)
+                    blk = torch.zeros(b.shape[0], T, dtype=torch.float32, device=device)
+                    blk[:, g_ * r:(g_ + 1) * r] = u
+                    rows.append(torch.cat([b.detach().to(device).float(), blk], 1))
+                    downs.append(lo.down.weight.detach().float().to(device))
+                d = torch.cat(downs, 0)
+                if d.shape[0] < T:
+                    d = torch.cat([d, torch.zeros(T - d.shape[0], d.shape[1], dtype=torch.float32, device=device)], 0)
+                return torch.cat(rows, 0).to(dtype).contiguous(), d.to(dtype).contiguous()
+            wq, dq = aug([attn.to_q.weight], [self.to_q_lora])
+            wkv, dkv = aug([attn.to_k.weight, attn.to_v.weight], [self.to_k_lora, self.to_v_lora])
+            wo, do = aug([attn.to_out[0].weight], [self.to_out_lora])
+            wqkv = dqkv = None
+            if attn.to_k.weight.shape[1] == attn.to_q.weight.shape[1]:
+                wqkv, dqkv = aug([attn.to_q.weight, attn.to_k.weight, attn.to_v.weight], [self.to_q_lora, self.to_k_lora, self.to_v_lora])
+            w = self._unfold.put(srcs, dict(q=wq, d_q=dq, kv=wkv, d_kv=dkv, o=wo, d_o=do, qkv=wqkv, d_qkv=dqkv), extra=(dtype, str(device)))
+        return w
 
     def _fold(self, attn, device, dtype):
         ls = float(self.lora_scale)
-        srcs = tuple(l.weight for lo in (self.to_q_lora, self.to_k_lora, self.to_v_lora, self.to_out_lora)
-                     for l in (lo.down, lo.up)) + (attn.to_q.weight, attn.to_k.weight, attn.to_v.weight, attn.to_out[0].weight)
+        srcs = self._lora_srcs(attn)
         w = self._folded.get(srcs, extra=(ls, dtype, str(device)))
         if w is None:
             def eff(base, lora):
@@ -587,16 +674,45 @@ class _IPBase(nn.Module, _FusedBase, _LoraFold):
         return w["q"], w["kv"], w["o"]
 
     def __call__(self, attn, hidden_states, encoder_hidden_states=None, attention_mask=None, scale=1.0, temb=None,
-                 *args, imd_residual=None, **kwargs):
+                 *args, imd_residual=None, lora_rows=None, ip_scale_rows=None, **kwargs):
         if encoder_hidden_states is None:
             raise NotImplementedError(f"{type(self).__name__} is a cross-attention (attn2) processor")
         dt = _compute_dtype(attn, hidden_states, attention_mask)
         x, shape4 = _as_tokens(hidden_states, dt)
-        wq, wkv, wo = self._weights(attn, dt, x.device)
+        B = x.shape[0]
+        bdiv = self._ehs_bdiv(B, encoder_hidden_states)
+        # engine-side extensions (the pipelines pass ``c_lora_rows`` / ``ip_scale_rows`` in the kwargs attn1 and attn2 share), fp32 [B] on the
+        # device: the LoRA scale / the face-token weight of every row of the CFG batch, read INSTEAD of ``lora_scale`` / ``scale``.  The rows
+        # that share a text-context row (a request's images) carry one LoRA scale: the text K / V are projected per context row.
+        rows = lora_rows if lora_rows is not None else kwargs.get("c_lora_rows")
+        lora = None
+        if rows is not None and isinstance(self, _LoraFold) and hasattr(self, "to_q_lora"):
+            rows = _check_rows(rows, B, "lora_rows", x.device)
+            u = self._unfolded(attn, x.device, dt)
+            wq, wkv, wo = u["q"], u["kv"], u["o"]
+            lora = dict(d_in=u["d_q"], d_out=u["d_o"], rows_in=rows, rows_out=rows)
+        else:
+            rows = None
+            wq, wkv, wo = self._weights(attn, dt, x.device)
         wsrc = (self.to_k_ip.weight, self.to_v_ip.weight)
         ls = float(getattr(self, "lora_scale", 0.0))
         ksrc = (encoder_hidden_states, attn.to_k.weight, attn.to_v.weight) + wsrc
-        kvs = self._kv.get(ksrc, extra=(ls, x.dtype))
+        if rows is not None:          # cached as below, on the conditioning tensor plus the identity / version of the scale rows
+            ksrc = ksrc + (rows,)
+            kvs = self._kv.get(ksrc, extra=("rows", x.dtype))
+            if kvs is None:
+                wip = self._wip.get(wsrc, extra=(x.dtype,))
+                if wip is None:
+                    wip = self._wip.put(wsrc, torch.cat([t.detach().to(device=x.device, dtype=x.dtype) for t in wsrc], 0).contiguous(),
+                                        extra=(x.dtype,))
+                e = encoder_hidden_states.to(device=x.device, dtype=x.dtype)
+                end = e.shape[1] - self.num_tokens
+                Be, Kd = e.shape[0], e.shape[2]
+                text = ops.lora_expand_rows(e[:, :end].contiguous().view(Be * end, Kd), u["d_kv"], rows[::bdiv].contiguous(), end)
+                kvs = self._kv.put(ksrc, (_project_kv(text.view(Be, end, text.shape[1]), wkv, attn.heads),
+                                          _project_kv(e[:, end:].contiguous(), wip, attn.heads)), extra=("rows", x.dtype))
+        else:
+            kvs = self._kv.get(ksrc, extra=(ls, x.dtype))
         if kvs is None:
             wip = self._wip.get(wsrc, extra=(x.dtype,))
             if wip is None:
@@ -607,15 +723,16 @@ class _IPBase(nn.Module, _FusedBase, _LoraFold):
             kvs = self._kv.put(ksrc,
                                (_project_kv(e[:, :end].contiguous(), wkv, attn.heads),
                                 _project_kv(e[:, end:].contiguous(), wip, attn.heads)), extra=(ls, x.dtype))
-        B = x.shape[0]
-        key = (B, float(self.scale), str(x.device))
-        s2 = self._s2.get(key)
-        if s2 is None:
-            s2 = torch.full((B,), float(self.scale), dtype=torch.float32, device=x.device)
-            self._s2 = {key: s2}
-        bdiv = self._ehs_bdiv(B, encoder_hidden_states)
+        if ip_scale_rows is not None:
+            s2 = _check_rows(ip_scale_rows, B, "ip_scale_rows", x.device)
+        else:
+            key = (B, float(self.scale), str(x.device))
+            s2 = self._s2.get(key)
+            if s2 is None:
+                s2 = torch.full((B,), float(self.scale), dtype=torch.float32, device=x.device)
+                self._s2 = {key: s2}
         out = _fused_attention(x, attn.heads, wq_or_qkv=wq, self_attn=False, kv1=kvs[0], kv1_bdiv=bdiv, kv2=kvs[1],
-                               kv2_bdiv=bdiv, scale2=s2, wo=wo, bo=_layer_weights(attn, "bo", dt, x.device), residual=imd_residual)
+                               kv2_bdiv=bdiv, scale2=s2, wo=wo, bo=_layer_weights(attn, "bo", dt, x.device), residual=imd_residual, lora=lora)
         return self._finish(attn, out, imd_residual is not None, hidden_states, shape4)
 
 

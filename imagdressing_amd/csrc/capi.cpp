@@ -314,6 +314,13 @@ int imd_unipc_step(const imd_unipc_params* p, void* stream) {
     return imd_launch_unipc_step(*p, (hipStream_t)stream);
 }
 
+int imd_lora_expand_rows(const imd_lora_rows_params* p, void* stream) {
+    IMD_REQUIRE(p != nullptr, "lora_expand_rows: null params");
+    IMD_REQUIRE_SIZE(p, "lora_expand_rows");
+    IMD_REQUIRE(p->x && p->down && p->row_scale && p->out, "lora_expand_rows: null pointer");
+    return imd_launch_lora_expand_rows(*p, (hipStream_t)stream);
+}
+
 int imd_unipc_step_rows(const imd_unipc_params* p, const float* coef_rows, void* stream) {
     IMD_REQUIRE(p != nullptr, "unipc_step_rows: null params");
     IMD_REQUIRE_SIZE(p, "unipc_step_rows");

@@ -15,6 +15,7 @@ typedef imd_layernorm_params LayerNormParams;
 typedef imd_ddim_params DdimParams;
 typedef imd_sampler_params SamplerParams;
 typedef imd_unipc_params UnipcParams;
+typedef imd_lora_rows_params LoraRowsParams;
 typedef imd_image_resample_params ImageResampleParams;
 typedef imd_image_pack_params ImagePackParams;
 typedef imd_image_overlay_params ImageOverlayParams;
@@ -104,6 +105,7 @@ int imd_launch_sampler_step_rows_at(const SamplerParams& p, const float* coef_ro
 int imd_launch_unipc_step(const UnipcParams& p, hipStream_t s);                                      // unipc_step.hip
 int imd_launch_unipc_step_rows(const UnipcParams& p, const float* coef_rows, hipStream_t s);
 int imd_launch_unipc_step_rows_at(const UnipcParams& p, const float* coef_rows, const int* row_slot, int slots, hipStream_t s);
+int imd_launch_lora_expand_rows(const LoraRowsParams& p, hipStream_t s);                              // lora_rows.hip
 int imd_launch_session_input_rows(const float* z, const int* row_slot, const float* in_scale_rows, bf16_t* x_in, int B, int slots, int HW,
                                   int dtype, hipStream_t s);
 int imd_launch_image_resample(const ImageResampleParams& p, hipStream_t s);          // image.hip

@@ -96,6 +96,8 @@ class IMAGDressing_v1(PipelineBase):
                  ref_clip_hidden_states: Optional[torch.Tensor] = None, ref_image_latents: Optional[torch.Tensor] = None,
                  face_clip_hidden_states: Optional[torch.Tensor] = None, face_uncond_clip_hidden_states: Optional[torch.Tensor] = None,
                  latents: Optional[torch.Tensor] = None, shard_over_ranks: bool = False, trace: Optional[list] = None, **kwargs):
+        rows_on = bool(getattr(self, "_request_adapter_scales", False))          # enable_request_adapter_scales
+        adapter = dict(ipa_scale=ipa_scale, s_lora_scale=s_lora_scale, c_lora_scale=c_lora_scale)
         R = self._request_count(dict(prompt=prompt, prompt_embeds=prompt_embeds, negative_prompt=negative_prompt, null_prompt=null_prompt,
                                      negative_prompt_embeds=negative_prompt_embeds, ref_image=ref_image, ref_clip_image=ref_clip_image,
                                      ref_clip_hidden_states=ref_clip_hidden_states, ref_image_latents=ref_image_latents,
@@ -103,10 +105,18 @@ class IMAGDressing_v1(PipelineBase):
                                      face_clip_hidden_states=face_clip_hidden_states,
                                      face_uncond_clip_hidden_states=face_uncond_clip_hidden_states,
                                      guidance_scale=guidance_scale, image_scale=image_scale),
-                                dict(num_inference_steps=num_inference_steps, eta=eta, ipa_scale=ipa_scale, s_lora_scale=s_lora_scale,
-                                     c_lora_scale=c_lora_scale, controlnet_conditioning_scale=controlnet_conditioning_scale), shard_over_ranks)
+                                dict(dict(num_inference_steps=num_inference_steps, eta=eta, controlnet_conditioning_scale=controlnet_conditioning_scale),
+                                     **({} if rows_on else adapter)), shard_over_ranks)
         num_inference_steps, eta = per_call_value("num_inference_steps", num_inference_steps), per_call_value("eta", eta)
-        if R > 1:
+        adapter_rows = None
+        if rows_on:
+            # each argument on its own: equal values keep the folded route (set_scale / set_ipa_scale below, bit for bit); differing ones ride
+            # in rows, read by the processors INSTEAD of their own attribute, which gets the neutral value (no LoRA folded; face weight 1)
+            ipa_scale, ip_rows = self._adapter_scales("ipa_scale", ipa_scale, R, 1.0)
+            s_lora_scale, s_rows = self._adapter_scales("s_lora_scale", s_lora_scale, R, 0.0)
+            c_lora_scale, c_rows = self._adapter_scales("c_lora_scale", c_lora_scale, R, 0.0)
+            adapter_rows = dict(s_lora_rows=s_rows, c_lora_rows=c_rows, ip_scale_rows=ip_rows)
+        elif R > 1:
             ipa_scale, s_lora_scale, c_lora_scale = (per_call_value("ipa_scale", ipa_scale), per_call_value("s_lora_scale", s_lora_scale),
                                                      per_call_value("c_lora_scale", c_lora_scale))
         if guess_mode or min_guidance(guidance_scale) <= 1.0:
@@ -124,6 +134,7 @@ class IMAGDressing_v1(PipelineBase):
         if not has_face:                                                      # :432-437
             self.set_scale(scale, lora_scale=0.0)
             self.set_ipa_scale(ipa_scale=0.0, lora_scale=0.0)
+            adapter_rows = None                                               # (the three scales are not read without a face)
         else:
             self.set_scale(scale, lora_scale=s_lora_scale)
             self.set_ipa_scale(ipa_scale, lora_scale=c_lora_scale)
@@ -154,5 +165,6 @@ class IMAGDressing_v1(PipelineBase):
         out = self.denoise(latents=lat, prompt_embeds=prompt_embeds, negative_prompt_embeds=negative_prompt_embeds,
                            sa_hidden_states=sa, num_inference_steps=num_inference_steps, guidance_scale=guidance_scale,
                            control=control, callback=callback, callback_steps=callback_steps or 1, trace=trace,
-                           eta=eta, generator=generator, variance_noise=kwargs.get("variance_noise"), requests=R, image_scale=scale_rows)
+                           eta=eta, generator=generator, variance_noise=kwargs.get("variance_noise"), requests=R, image_scale=scale_rows,
+                           adapter_rows=adapter_rows)
         return self._decode(out, output_type, generator)

@@ -189,6 +189,31 @@ class PipelineBase:
     def disable_device_image_io(self):
         return self.enable_device_image_io(False)
 
+    def enable_request_adapter_scales(self, flag: bool = True):
+        """Opt in to ``ipa_scale``, ``s_lora_scale`` and ``c_lora_scale`` PER REQUEST in a request-batched call of the IP-Adapter +
+        ControlNet pipeline: each takes one value or one per request.  Each argument on its own: equal values (or a scalar) keep the
+        folded route -- ``set_scale`` / ``set_ipa_scale``, LoRA folded into the weights, every launch and every bit as with the switch
+        off; differing values ride in rows (``s_lora_rows`` / ``c_lora_rows`` / ``ip_scale_rows`` of the cross-attention kwargs) and the
+        LoRA of those layers runs unfolded, y = [x | s_row (x D^T)] [W | U]^T: one ``imd_lora_expand_rows`` launch in front of each
+        projection, whose K grows by the rank.  That route costs time (see README); grouping requests by equal scales avoids it.
+        A request with all three at 0 gets the scale settings of the reference's no-face branch, which is how a call mixes requests
+        with and without a face (face arguments themselves stay all-or-none).  Off by default: differing sequences then raise, as
+        ever.  A no-op on the pipelines without LoRA / IP-Adapter processors (base, ControlNet, inpainting): they have none of the
+        three arguments."""
+        self._request_adapter_scales = bool(flag)
+        return self
+
+    def disable_request_adapter_scales(self):
+        return self.enable_request_adapter_scales(False)
+
+    @staticmethod
+    def _adapter_scales(name, value, R, neutral):
+        """-> (the value the processors get through set_scale / set_ipa_scale, per-request values for the loop or None), like
+        :meth:`_image_scales`: equal values (and a scalar) keep the folded route; differing ones ride in rows, the processors' own
+        attribute at ``neutral`` (the rows are read instead of it)."""
+        vals = per_request_floats(name, value, R)
+        return (vals[0], None) if len(set(vals)) == 1 else (neutral, vals)
+
     def _image_processor(self):
         from ...image import DeviceImageProcessor
         proc = self.__dict__.get("_image_proc")
@@ -306,7 +331,8 @@ class PipelineBase:
                 control: Optional[dict] = None, inpaint: Optional[dict] = None,
                 callback: Optional[Callable] = None, callback_steps: int = 1, trace: Optional[list] = None,
                 eta: float = 0.0, generator=None, variance_noise: Optional[List[torch.Tensor]] = None, t_start: int = 0,
-                requests: int = 1, image_scale: Optional[Sequence[float]] = None) -> torch.Tensor:
+                requests: int = 1, image_scale: Optional[Sequence[float]] = None,
+                adapter_rows: Optional[Dict[str, Optional[Sequence[float]]]] = None) -> torch.Tensor:
         """latents [B, 4, h, w] fp32 -> final latents [B, 4, h, w] fp32.
 
         ``requests`` = R > 1: a request-batched call (:class:`RequestLayout`) -- latent rows [r n, (r+1) n) belong to request r
@@ -314,7 +340,9 @@ class PipelineBase:
         tensors in ``sa_hidden_states`` hold R rows (or 1, shared); ``guidance_scale`` may be a sequence of R values (the per-row
         fused step, ``imd_ddim_cfg_step_rows``, when they differ) and ``image_scale`` a sequence of R garment-branch weights
         (carried in the ``sa_batch_mask`` rows; the processors' own ``scale`` is then expected to be 1).  ``control["image"]`` and
-        the ``inpaint`` tensors hold 1, R or B rows.
+        the ``inpaint`` tensors hold 1, R or B rows.  ``adapter_rows`` (``enable_request_adapter_scales``): for each of ``s_lora_rows``,
+        ``c_lora_rows``, ``ip_scale_rows`` None or R values -- they become fp32 [2B] device tensors in the cross-attention kwargs, a
+        request's value on all its rows, cond and uncond alike (the reference's processors do not look at the CFG half).
 
         The scheduler decides the step: DDIM (``imd_ddim_cfg_step``), a scheduler with a ``plan`` method -- DPM-Solver++, Euler,
         Euler-ancestral, PNDM (scheduler.py) -- one ``imd_sampler_step`` per step with the same guidance / blend / graph-replay
@@ -369,6 +397,9 @@ class PipelineBase:
         # sa_pair_layout: the mask above IS "garment on for rows [0, B), off for rows [B, 2B)" -- together with cfg_pair (identical latents in
         # the two halves) it lets the engine run the first hybrid block's self-attention phase once per image (unet.call_pair_half)
         cak = {"sa_hidden_states": sa_hidden_states, "sa_batch_mask": mask_rows, "sa_pair_layout": True}
+        for key, vals in (adapter_rows or {}).items():          # alive for the whole call (a captured step graph reads them at every replay)
+            if vals is not None:
+                cak[key] = lay.per_row(per_request_floats(key, vals, lay.requests)).repeat(2).to(device=dev, dtype=torch.float32).contiguous()
         ctrl_img = ctrl_ehs = None
         if control is not None:
             img = control["image"]

@@ -1352,7 +1352,51 @@ def session_input_rows(z, row_slot, in_scale_rows, x_in):
     return x_in
 
 
-# ---- UniPC on one fused step launch (csrc/unipc_step.hip; the coefficients come from scheduler.UniPCMultistepScheduler.plan_fused) ----
+# ---- per-row LoRA scales: the augmented activation rows [x | s_row (x D^T)] (csrc/lora_rows.hip) ----
+LORA_ROWS_COUNTER = {"launches": 0}      # imd_lora_expand_rows launches of this process (tests check that the folded route makes none)
+
+
+def _rows2d(t, name: str):
+    """(pointer, leading dimension) of a 16-bit [rows, cols] tensor or row-strided view of one"""
+    if not isinstance(t, torch.Tensor) or t.dim() != 2 or not t.is_cuda or t.dtype not in DTYPE_CODE or (t.shape[1] > 1 and t.stride(1) != 1):
+        raise L.ImdError(f"lora_expand_rows: {name} must be a 16-bit [rows, channels] device tensor with contiguous channels")
+    return t.data_ptr(), (t.stride(0) if t.shape[0] > 1 else max(t.stride(0), t.shape[1]))
+
+
+def lora_expand_rows(x: torch.Tensor, down: torch.Tensor, row_scale: torch.Tensor, rows_per_entry: int, *,
+                     out: Optional[torch.Tensor] = None, out_cols: Optional[int] = None) -> torch.Tensor:
+    """``out[m, :C] = x[m]`` (the same bits), ``out[m, C + j] = 16-bit(row_scale[m // rows_per_entry] * sum_c x[m, c] down[j, c])``
+    (``imd_lora_expand_rows``): the activations of a LoRA layer whose scale differs per row, for the projection launch with the augmented
+    weight ``[W | U]``.  x [M, C] (rows may be strided), down [T, C] contiguous, row_scale fp32 [E] on the device with
+    ``M == E * rows_per_entry``.  ``out``: a [M, >= C + T] tensor or row-strided view (columns past C + T keep their bytes); without it a
+    fresh [M, out_cols or C + T] tensor whose columns past C + T are zero."""
+    ensure_device(x.device)
+    xp, x_ld = _rows2d(x, "x")
+    M, C_ = x.shape
+    if not isinstance(down, torch.Tensor) or down.dim() != 2 or down.shape[1] != C_ or down.dtype != x.dtype:
+        raise L.ImdError(f"lora_expand_rows: down must be [T, {C_}] of {x.dtype}")
+    T = down.shape[0]
+    if not isinstance(row_scale, torch.Tensor) or row_scale.dim() != 1:
+        raise L.ImdError("lora_expand_rows: row_scale must be a 1-d fp32 device tensor")
+    if out is None:
+        cols = C_ + T if out_cols is None else int(out_cols)
+        out = torch.empty((M, cols), dtype=x.dtype, device=x.device) if cols == C_ + T else torch.zeros((M, cols), dtype=x.dtype, device=x.device)
+    if out.dtype != x.dtype or out.shape[0] != M:
+        raise L.ImdError(f"lora_expand_rows: out must be [{M}, >= {C_ + T}] of {x.dtype}")
+    op, out_ld = _rows2d(out, "out")
+    if out.shape[1] < C_ + T:
+        raise L.ImdError(f"lora_expand_rows: out has {out.shape[1]} columns, needs {C_ + T}")
+    p = L.LoraRowsParams()
+    p.x, p.down, p.row_scale, p.out = xp, _dev(down, x.dtype, "down"), _dev(row_scale, torch.float32, "row_scale"), op
+    p.M, p.C, p.T, p.E, p.rows_per_entry = M, C_, T, row_scale.numel(), int(rows_per_entry)
+    p.x_ld, p.out_ld, p.dtype = x_ld, out_ld, _code(x, "x")
+    L.check(L.load().imd_lora_expand_rows(C.byref(p), _stream()))
+    LORA_ROWS_COUNTER["launches"] += 1
+    _count("lora_expand", 2.0 * M * T * C_)
+    return out
+
+
+# ---- UniPC on one fused step launch (csrc/unipc_step.hip;the coefficients come from scheduler.UniPCMultistepScheduler.plan_fused) ----
 UNIPC_COEFS = 19
 UNIPC_ROW_FLOATS = 24
 UNIPC_IN_SCALE = 16          # index of in_scale in the block (what ``session_input_rows`` needs of a request's last step)

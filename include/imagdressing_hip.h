@@ -351,6 +351,26 @@ typedef struct imd_unipc_params {
                            * holds no pointer or scalar that changes between replays -- the host refreshes 76 bytes per step */
 } imd_unipc_params;
 
+/* Per-row LoRA with the low-rank path unfolded (imd_lora_expand_rows).  For a linear layer with LoRA,
+ *   y = x W^T + s_row ((x D^T) U^T) = [x | s_row (x D^T)] [W | U]^T
+ * so a scale that differs from row to row goes into the ACTIVATIONS and the augmented weight [W | U] (network_alpha / rank folded into
+ * U) does not depend on it: the projection launch that follows is the existing one with Cin = C + T.  This launch writes the augmented
+ * rows:   out[m, c]     = x[m, c]                                                   c < C, the same bits
+ *         out[m, C + j] = 16-bit( row_scale[m / rows_per_entry] * sum_c x[m, c] down[j, c] )       j < T
+ * The sum is accumulated in fp32 on the MFMA, the scale multiplies the finished sum in fp32, and the product is rounded ONCE to the
+ * element type (round to nearest even).  Bytes of an output row past C + T are not written. */
+typedef struct imd_lora_rows_params {
+    uint32_t struct_bytes; /* sizeof(imd_lora_rows_params) in the caller's view; checked on entry */
+    const uint16_t* x;     /* [M, C] 16-bit, row stride x_ld */
+    const uint16_t* down;  /* [T, C] 16-bit, contiguous: the stacked LoRA down matrices of the launch (T = G rank) */
+    const float* row_scale; /* DEVICE [E] fp32 */
+    uint16_t* out;         /* [M, >= C + T] 16-bit, row stride out_ld; must not overlap x */
+    int M, C, T;           /* C: a multiple of 16 in 64..1280; T: a multiple of 16 in 16..384 */
+    int E, rows_per_entry; /* M == E * rows_per_entry */
+    int x_ld, out_ld;      /* in elements, multiples of 8; x_ld >= C, out_ld >= C + T */
+    int dtype;
+} imd_lora_rows_params;
+
 /* Device-side image input (imd_image_resample): separable antialiased resampling of uint8 images, bit-exact with Pillow's 8-bit
  * resampler (libImaging/Resample.c), with a fused output stage -- the work diffusers' VaeImageProcessor / transformers'
  * CLIPImageProcessor do on the host in front of IMAGDressing_v1_pipeline*.py.  Per axis whose size changes the caller passes a
@@ -694,6 +714,12 @@ int imd_unipc_step_rows(const imd_unipc_params* p, const float* coef_rows /* DEV
  * imd_unipc_step_rows, row_slot NULL or not 4-byte aligned, slots < 1, B > slots. */
 int imd_unipc_step_rows_at(const imd_unipc_params* p, const float* coef_rows /* DEVICE [B][24] fp32 */,
                            const int* row_slot /* DEVICE [B] */, int slots, void* stream);
+
+/* Augmented activation rows [x | s_row (x D^T)] of a per-row-scaled LoRA layer; see imd_lora_rows_params (lora_rows.hip).  Errors
+ * without launching: a foreign struct_bytes, a null pointer, an unknown dtype, C or T not a multiple of 16, C outside 64..1280, T
+ * outside 16..384, M != E * rows_per_entry (or any of them < 1), x_ld < C, out_ld < C + T, a leading dimension that is not a multiple of
+ * 8 elements, x / down / out not 16-byte aligned, row_scale not 4-byte aligned, out overlapping x, an operand of 2 GiB or more. */
+int imd_lora_expand_rows(const imd_lora_rows_params* p, void* stream);
 
 /* Pillow-exact resize (+ crop, normalise, layout) of uint8 images on the device; see imd_image_resample_params.  Errors without
  * launching: a foreign struct size, null src / out, C outside {1, 3}, an incomplete table or a skipped axis whose size changes, a
