@@ -36,11 +36,12 @@ class IMAGDressing_v1(PipelineBase):
                  negative_prompt_embeds: Optional[torch.Tensor] = None, cross_attention_kwargs: Optional[Dict[str, Any]] = None,
                  # --- extensions: bypass the out-of-scope encoders / inject latents / shard over ranks ---
                  ref_clip_hidden_states: Optional[torch.Tensor] = None, ref_image_latents: Optional[torch.Tensor] = None,
-                 latents: Optional[torch.Tensor] = None, shard_over_ranks: bool = False, trace: Optional[list] = None, **kwargs):
+                 latents: Optional[torch.Tensor] = None, shard_over_ranks: bool = False, trace: Optional[list] = None,
+                 guidance_rescale: Union[float, List[float]] = 0.0, **kwargs):
         R = self._request_count(dict(prompt=prompt, prompt_embeds=prompt_embeds, negative_prompt=negative_prompt, null_prompt=null_prompt,
                                      negative_prompt_embeds=negative_prompt_embeds, ref_image=ref_image, ref_clip_image=ref_clip_image,
                                      ref_clip_hidden_states=ref_clip_hidden_states, ref_image_latents=ref_image_latents,
-                                     guidance_scale=guidance_scale, image_scale=image_scale),
+                                     guidance_scale=guidance_scale, image_scale=image_scale, guidance_rescale=guidance_rescale),
                                 dict(num_inference_steps=num_inference_steps, eta=eta), shard_over_ranks)
         num_inference_steps, eta = per_call_value("num_inference_steps", num_inference_steps), per_call_value("eta", eta)
         if min_guidance(guidance_scale) <= 1.0:
@@ -64,5 +65,5 @@ class IMAGDressing_v1(PipelineBase):
                            sa_hidden_states=sa, num_inference_steps=num_inference_steps, guidance_scale=guidance_scale,
                            callback=callback, callback_steps=callback_steps or 1, trace=trace,
                            eta=eta, generator=generator, variance_noise=kwargs.get("variance_noise"),          # eta: :451, :530
-                           requests=R, image_scale=scale_rows)
+                           requests=R, image_scale=scale_rows, guidance_rescale=guidance_rescale)
         return self._decode(out, output_type, generator)                                            # :544-547

@@ -49,11 +49,13 @@ class IMAGDressing_v1(PipelineBase):
                  controlnet_conditioning_scale: Union[float, List[float]] = 1.0, guess_mode: bool = False,
                  control_guidance_start: Union[float, List[float]] = 0.0, control_guidance_end: Union[float, List[float]] = 1.0,
                  ref_clip_hidden_states: Optional[torch.Tensor] = None, ref_image_latents: Optional[torch.Tensor] = None,
-                 latents: Optional[torch.Tensor] = None, shard_over_ranks: bool = False, trace: Optional[list] = None, **kwargs):
+                 latents: Optional[torch.Tensor] = None, shard_over_ranks: bool = False, trace: Optional[list] = None,
+                 guidance_rescale: Union[float, List[float]] = 0.0, **kwargs):
         R = self._request_count(dict(prompt=prompt, prompt_embeds=prompt_embeds, negative_prompt=negative_prompt, null_prompt=null_prompt,
                                      negative_prompt_embeds=negative_prompt_embeds, ref_image=ref_image, ref_clip_image=ref_clip_image,
                                      ref_clip_hidden_states=ref_clip_hidden_states, ref_image_latents=ref_image_latents,
-                                     pose_image=pose_image, guidance_scale=guidance_scale, image_scale=image_scale),
+                                     pose_image=pose_image, guidance_scale=guidance_scale, image_scale=image_scale,
+                                     guidance_rescale=guidance_rescale),
                                 dict(num_inference_steps=num_inference_steps, eta=eta, controlnet_conditioning_scale=controlnet_conditioning_scale),
                                 shard_over_ranks)
         num_inference_steps, eta = per_call_value("num_inference_steps", num_inference_steps), per_call_value("eta", eta)
@@ -83,5 +85,6 @@ class IMAGDressing_v1(PipelineBase):
         out = self.denoise(latents=lat, prompt_embeds=prompt_embeds, negative_prompt_embeds=negative_prompt_embeds,
                            sa_hidden_states=sa, num_inference_steps=num_inference_steps, guidance_scale=guidance_scale,
                            control=control, callback=callback, callback_steps=callback_steps or 1, trace=trace,
-                           eta=eta, generator=generator, variance_noise=kwargs.get("variance_noise"), requests=R, image_scale=scale_rows)
+                           eta=eta, generator=generator, variance_noise=kwargs.get("variance_noise"), requests=R, image_scale=scale_rows,
+                           guidance_rescale=guidance_rescale)
         return self._decode(out, output_type, generator)

@@ -256,7 +256,8 @@ class IMAGDressing_v1(PipelineBase):
                  ref_clip_hidden_states: Optional[torch.Tensor] = None, ref_image_latents: Optional[torch.Tensor] = None,
                  image_latents: Optional[torch.Tensor] = None, mask_latents: Optional[torch.Tensor] = None,
                  noise: Optional[torch.Tensor] = None, shard_over_ranks: bool = False, trace: Optional[list] = None,
-                 mask_dilate: Union[int, List[int]] = 0, mask_blur: Union[float, List[float]] = 0.0, overlay: bool = False, **kwargs):
+                 mask_dilate: Union[int, List[int]] = 0, mask_blur: Union[float, List[float]] = 0.0,
+                 guidance_rescale: Union[float, List[float]] = 0.0, overlay: bool = False, **kwargs):
         """``mask_dilate`` = k and ``mask_blur`` = b (one value, or a list with one per request; 0: the step is skipped) grow and feather
         the mask before ANY reader sees it -- the crop box, the binarised latent mask, the built-in inpaint condition, the overlay and
         the plain route with a caller's ``control_image``: the call equals, byte for byte, the same call given each mask as
@@ -266,7 +267,8 @@ class IMAGDressing_v1(PipelineBase):
                                      negative_prompt_embeds=negative_prompt_embeds, ref_image=ref_image, ref_clip_image=ref_clip_image,
                                      ref_clip_hidden_states=ref_clip_hidden_states, ref_image_latents=ref_image_latents,
                                      control_image=control_image, image=image, mask_image=mask_image, image_latents=image_latents,
-                                     mask_latents=mask_latents, guidance_scale=guidance_scale, image_scale=image_scale),
+                                     mask_latents=mask_latents, guidance_scale=guidance_scale, image_scale=image_scale,
+                                     guidance_rescale=guidance_rescale),
                                 dict(num_inference_steps=num_inference_steps, strength=strength, eta=eta,
                                      controlnet_conditioning_scale=controlnet_conditioning_scale), shard_over_ranks)
         num_inference_steps, strength, eta = (per_call_value("num_inference_steps", num_inference_steps), per_call_value("strength", strength),
@@ -379,7 +381,7 @@ class IMAGDressing_v1(PipelineBase):
                            sa_hidden_states=sa, num_inference_steps=num_inference_steps, guidance_scale=guidance_scale,
                            control=control, inpaint=inpaint, callback=callback, callback_steps=callback_steps, trace=trace,
                            eta=eta, generator=generator, variance_noise=kwargs.get("variance_noise"), t_start=t_start,
-                           requests=R, image_scale=scale_rows)
+                           requests=R, image_scale=scale_rows, guidance_rescale=guidance_rescale)
         if overlay:
             return self._decode_overlay(out, output_type, front)
         return self._decode(out, output_type, generator)

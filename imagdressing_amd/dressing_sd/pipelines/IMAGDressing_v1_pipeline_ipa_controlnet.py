@@ -95,7 +95,8 @@ class IMAGDressing_v1(PipelineBase):
                  control_guidance_start: Union[float, List[float]] = 0.0, control_guidance_end: Union[float, List[float]] = 1.0,
                  ref_clip_hidden_states: Optional[torch.Tensor] = None, ref_image_latents: Optional[torch.Tensor] = None,
                  face_clip_hidden_states: Optional[torch.Tensor] = None, face_uncond_clip_hidden_states: Optional[torch.Tensor] = None,
-                 latents: Optional[torch.Tensor] = None, shard_over_ranks: bool = False, trace: Optional[list] = None, **kwargs):
+                 latents: Optional[torch.Tensor] = None, shard_over_ranks: bool = False, trace: Optional[list] = None,
+                 guidance_rescale: Union[float, List[float]] = 0.0, **kwargs):
         rows_on = bool(getattr(self, "_request_adapter_scales", False))          # enable_request_adapter_scales
         adapter = dict(ipa_scale=ipa_scale, s_lora_scale=s_lora_scale, c_lora_scale=c_lora_scale)
         R = self._request_count(dict(prompt=prompt, prompt_embeds=prompt_embeds, negative_prompt=negative_prompt, null_prompt=null_prompt,
@@ -104,7 +105,7 @@ class IMAGDressing_v1(PipelineBase):
                                      pose_image=pose_image, face_clip_image=face_clip_image, faceid_embeds=faceid_embeds,
                                      face_clip_hidden_states=face_clip_hidden_states,
                                      face_uncond_clip_hidden_states=face_uncond_clip_hidden_states,
-                                     guidance_scale=guidance_scale, image_scale=image_scale),
+                                     guidance_scale=guidance_scale, image_scale=image_scale, guidance_rescale=guidance_rescale),
                                 dict(dict(num_inference_steps=num_inference_steps, eta=eta, controlnet_conditioning_scale=controlnet_conditioning_scale),
                                      **({} if rows_on else adapter)), shard_over_ranks)
         num_inference_steps, eta = per_call_value("num_inference_steps", num_inference_steps), per_call_value("eta", eta)
@@ -166,5 +167,5 @@ class IMAGDressing_v1(PipelineBase):
                            sa_hidden_states=sa, num_inference_steps=num_inference_steps, guidance_scale=guidance_scale,
                            control=control, callback=callback, callback_steps=callback_steps or 1, trace=trace,
                            eta=eta, generator=generator, variance_noise=kwargs.get("variance_noise"), requests=R, image_scale=scale_rows,
-                           adapter_rows=adapter_rows)
+                           adapter_rows=adapter_rows, guidance_rescale=guidance_rescale)
         return self._decode(out, output_type, generator)

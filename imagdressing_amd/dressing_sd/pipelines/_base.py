@@ -22,6 +22,7 @@ modules supplied by the caller, or bypassed with pre-computed tensors (``prompt_
 """
 from __future__ import annotations
 
+import math
 from dataclasses import dataclass
 from typing import Any, Callable, Dict, List, Optional, Sequence, Union
 
@@ -332,7 +333,8 @@ class PipelineBase:
                 callback: Optional[Callable] = None, callback_steps: int = 1, trace: Optional[list] = None,
                 eta: float = 0.0, generator=None, variance_noise: Optional[List[torch.Tensor]] = None, t_start: int = 0,
                 requests: int = 1, image_scale: Optional[Sequence[float]] = None,
-                adapter_rows: Optional[Dict[str, Optional[Sequence[float]]]] = None) -> torch.Tensor:
+                adapter_rows: Optional[Dict[str, Optional[Sequence[float]]]] = None,
+                guidance_rescale: Union[float, Sequence[float]] = 0.0) -> torch.Tensor:
         """latents [B, 4, h, w] fp32 -> final latents [B, 4, h, w] fp32.
 
         ``requests`` = R > 1: a request-batched call (:class:`RequestLayout`) -- latent rows [r n, (r+1) n) belong to request r
@@ -355,6 +357,11 @@ class PipelineBase:
         ``t_start``: skip the first t_start timesteps of the schedule (inpainting ``strength`` < 1,
         ..._controlnet_inpainting.py:316-319 -> diffusers ``get_timesteps``); ``latents`` is then the noised image latent.
 
+        ``guidance_rescale``: the CFG rescale of Lin et al. 2023, section 3.4 (diffusers' ``rescale_noise_cfg``), one value in [0, 1] per
+        call or per request.  All 0: nothing new happens.  Otherwise ONE ``imd_guidance_rescale`` launch between the UNet and the step
+        writes the rescaled guided prediction into both CFG halves of eps, so every fused step recovers it unchanged -- eager or captured;
+        a host-stepped UniPC (``step_guided``) refuses it.
+
         ``control`` = dict(image=[1|B, 3, H, W] in [0,1] or NHWC8 bf16, prompt_embeds=[1,77,768],
         negative_prompt_embeds=[1,77,768], scale=float, keep=[float]*steps)
         ``inpaint`` = dict(mask=[B|1,1,h,w], image_latents=[B|1,4,h,w], noise=[B,4,h,w])
@@ -375,6 +382,12 @@ class PipelineBase:
         # uniform guidance: the scalar step (a single-request call is unchanged); otherwise one fp32 value per latent row, alive for the
         # whole call (a captured step graph reads it at every replay)
         g_arg = gs[0] if len(set(gs)) == 1 else lay.per_row(gs).to(dev)
+        # guidance_rescale: None (every value 0: no tensor, no launch), the scalar, or one fp32 value per latent row alive like g_arg
+        phis = guidance_rescale_values(guidance_rescale, lay.requests)
+        phi_arg = None if not any(phis) else (phis[0] if len(set(phis)) == 1 else lay.per_row(phis).to(dev))
+        if phi_arg is not None and multistep:
+            raise NotImplementedError("guidance_rescale with the host-stepped UniPC (step_guided): the rescale runs in front of a fused "
+                                      "step; call scheduler.enable_fused_step() first")
         sch = self.scheduler
         sch.set_timesteps(num_inference_steps, device=dev)
         if fused:          # fractional timesteps (Euler, "linspace" spacing or Karras sigmas) reach the time embedding unrounded
@@ -460,6 +473,8 @@ class PipelineBase:
             if control is not None:
                 down, mid = self.controlnet.forward_nhwc(x_in, t, ctrl_ehs, ctrl_img, ctrl_scale * (keeps[0] if i is None else keeps[i]), **mode)
             eps = self.unet.forward_nhwc(x_in, t, ehs, cak, down, mid, cfg_pair=True, **mode)
+            if phi_arg is not None:
+                ops.guidance_rescale(eps.view(2 * B, HW, Cl), guidance=g_arg, rescale=phi_arg)
             kw = {}
             if inp is not None:
                 kw = dict(mask=inp["mask"], z_img=inp["z_img"], blend_noise=inp["noise"])
@@ -475,6 +490,8 @@ class PipelineBase:
             if control is not None:
                 down, mid = self.controlnet.forward_nhwc(x_in, t, ctrl_ehs, ctrl_img, ctrl_scale * (keeps[0] if i is None else keeps[i]), **mode)
             eps = self.unet.forward_nhwc(x_in, t, ehs, cak, down, mid, cfg_pair=True, **mode)     # x_in = [z; z]: both halves see the same latent
+            if phi_arg is not None:
+                ops.guidance_rescale(eps.view(2 * B, HW, Cl), guidance=g_arg, rescale=phi_arg)
             kw = {}
             if inp is not None:
                 kw = dict(mask=inp["mask"], z_img=inp["z_img"], noise=inp["noise"])
@@ -747,6 +764,16 @@ def per_request_floats(name: str, value, R: int) -> List[float]:
     return vals
 
 
+def guidance_rescale_values(value, R: int) -> List[float]:
+    """``guidance_rescale`` of a call or a session request -> R floats, each finite and in [0, 1] (diffusers takes any float; outside
+    [0, 1] the factor extrapolates past both standard deviations, which no caller means)"""
+    vals = per_request_floats("guidance_rescale", value, R)
+    for v in vals:
+        if not (math.isfinite(v) and 0.0 <= v <= 1.0):
+            raise ValueError(f"guidance_rescale must be finite and in [0, 1], got {v}")
+    return vals
+
+
 def per_call_value(name: str, value):
     """Arguments folded into weights or shared by the schedule (steps, strength, eta, LoRA / IP-Adapter / ControlNet scales) stay per call:
     a sequence is accepted only if its entries agree."""
@@ -804,6 +831,8 @@ def request_count(args: Dict[str, Any], per_call: Optional[Dict[str, Any]] = Non
                              "guidance step is the fused DDIM step)")
     if "image_scale" in args and _is_seq(args["image_scale"]):
         per_request_floats("image_scale", args["image_scale"], R)
+    if "guidance_rescale" in args:
+        guidance_rescale_values(args["guidance_rescale"], R)
     return R
 
 
@@ -870,6 +899,6 @@ def set_scale_by_type(unet, cls, **attrs):
                 setattr(proc, k, v)
 
 
-__all__ = ["deepcache_plan", "RequestLayout", "request_count", "request_rows", "unipc_fused", "per_request_floats", "per_call_value", "as_batch", "min_guidance", "entries",
+__all__ = ["deepcache_plan", "RequestLayout", "request_count", "request_rows", "unipc_fused", "per_request_floats", "guidance_rescale_values", "per_call_value", "as_batch", "min_guidance", "entries",
            "controlnet_keep", "first", "to_image_tensor", "PipelineBase", "StableDiffusionPipelineOutput", "randn_tensor", "set_scale_by_type",
            "RefSAttnProcessor2_0", "LoraRefSAttnProcessor2_0", "LoRAIPAttnProcessor2_0", "IPAttnProcessor2_0"]

@@ -1481,6 +1481,33 @@ def unipc_step_rows_at(z, eps, x_next, *, guidance, coef_rows, row_slot, hist=No
     return z
 
 
+# ---- CFG rescale in front of any step (csrc/guidance_rescale.hip) ----
+def guidance_rescale(eps, *, guidance, rescale):
+    """The CFG rescale of Lin et al. 2023, section 3.4 (diffusers' ``rescale_noise_cfg``) in place on ``eps`` [2B,HW,4] fp32
+    (``imd_guidance_rescale``): for every latent row b whose ``rescale`` is not 0, rows b and B + b both receive
+    f (eps_u + g (eps_c - eps_u)), f = rescale * std(eps_c) / std(guided) + 1 - rescale -- so the step launch that follows recovers
+    that value whatever guidance it is given.  A row with ``rescale`` 0 keeps its bytes.  ``guidance`` / ``rescale``: a float each, or
+    a contiguous device fp32 tensor [B] (the conventions of the step wrappers' ``guidance``)."""
+    ensure_device(eps.device)
+    p = L.GuidanceRescaleParams()
+    p.eps = _dev(eps, torch.float32, "eps")
+    if eps.dim() != 3 or eps.shape[2] != 4 or eps.shape[0] < 2 or eps.shape[0] % 2:
+        raise L.ImdError(f"guidance_rescale: eps {tuple(eps.shape)}: expected [2B, HW, 4]")
+    p.B, p.HW = eps.shape[0] // 2, eps.shape[1]
+    for name, val in (("guidance", guidance), ("rescale", rescale)):
+        if isinstance(val, torch.Tensor):
+            if val.dtype != torch.float32 or val.numel() != p.B or not val.is_contiguous():
+                raise L.ImdError(f"guidance_rescale: per-row {name} must be a contiguous fp32 tensor of {p.B} values, got "
+                                 f"{val.dtype} {tuple(val.shape)}")
+            setattr(p, name + "_rows", _dev(val, torch.float32, name))
+            setattr(p, name, 0.0)
+        else:
+            setattr(p, name + "_rows", None)
+            setattr(p, name, float(val))
+    L.check(L.load().imd_guidance_rescale(C.byref(p), _stream()))
+    return eps
+
+
 # ---------------------------------------------------------------------------------------------
 # image input / output (csrc/image.hip; imagdressing_amd/image.py builds the coefficient tables)
 # ---------------------------------------------------------------------------------------------

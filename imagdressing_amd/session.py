@@ -29,6 +29,7 @@ Two layers, so that the logic is testable without a GPU:
 from __future__ import annotations
 
 import copy
+import math
 from collections import deque
 from typing import Any, Dict, List, Optional
 
@@ -63,9 +64,11 @@ def check_pipeline(pipe) -> None:
 
 
 def check_request(*, size, width=None, height=None, num_inference_steps, guidance_scale, image_scale=1.0, eta=0.0,
-                  shard_over_ranks=False, control_guidance_start=0.0, control_guidance_end=1.0, num_images_per_prompt=1, slots=1) -> None:
+                  shard_over_ranks=False, control_guidance_start=0.0, control_guidance_end=1.0, num_images_per_prompt=1, slots=1,
+                  guidance_rescale=0.0) -> None:
     """what ``submit`` refuses, before anything is launched or queued.  ``size`` = (width, height) of the session."""
-    for name, v in (("num_inference_steps", num_inference_steps), ("guidance_scale", guidance_scale), ("image_scale", image_scale)):
+    for name, v in (("num_inference_steps", num_inference_steps), ("guidance_scale", guidance_scale), ("image_scale", image_scale),
+                    ("guidance_rescale", guidance_rescale)):
         if isinstance(v, (list, tuple)):
             raise ValueError(f"{name} is per request in a session: submit one request per call, got {list(v)}")
     if float(eta) > 0.0:
@@ -82,6 +85,8 @@ def check_request(*, size, width=None, height=None, num_inference_steps, guidanc
                                   "(IMAGDressing_v1_pipeline.py:476-479, :511); sample with guidance_scale > 1")
     if int(num_inference_steps) < 1:
         raise ValueError(f"num_inference_steps must be >= 1, got {num_inference_steps}")
+    if not (math.isfinite(float(guidance_rescale)) and 0.0 <= float(guidance_rescale) <= 1.0):
+        raise ValueError(f"guidance_rescale must be finite and in [0, 1], got {guidance_rescale}")
     if not 1 <= int(num_images_per_prompt) <= int(slots):
         raise ValueError(f"num_images_per_prompt = {num_images_per_prompt} takes that many slots; the session has {slots}")
 
@@ -390,6 +395,7 @@ class _WidthViews:
         self.ctrl_img = ses.ctrl_img[:2 * B] if ses.ctrl_img is not None else None
         self.coef_rows = ses.coef_rows[:B]
         self.guidance_rows = ses.guidance_rows[:B] if ses.guidance_rows is not None else None
+        self.rescale_rows = ses.rescale_rows[:B] if ses.rescale_rows is not None else None
         self.row_slot = ses.row_slot[:B]
         self.ehs = self.garment = self.cak = None          # with the context buffers, at the first admission
 
@@ -431,6 +437,10 @@ class DenoiseSession:
         self.mask_rows = torch.zeros(2 * S, dtype=torch.float32, device=dev)          # [image_scale of the cond rows; 0 for the uncond rows]
         self.guidance = torch.ones(S, dtype=torch.float32, device=dev)
         self.guidance_rows = torch.ones(S, dtype=torch.float32, device=dev) if self.compact else None
+        # guidance_rescale beside the guidance: 0 = imd_guidance_rescale leaves the row alone -- the value of every idle slot / row, always
+        self.rescale = torch.zeros(S, dtype=torch.float32, device=dev)
+        self.rescale_rows = torch.zeros(S, dtype=torch.float32, device=dev) if self.compact else None
+        self._rescale_seen = False          # a request with a non-zero value was admitted: repacks then clear the rows first
         self.coef_rows = torch.zeros(S, self.plan.row_floats, dtype=torch.float32, device=dev)
         self.row_slot = torch.arange(S, dtype=torch.int32, device=dev)
         self._row_slot_host = list(range(S))
@@ -491,7 +501,7 @@ class DenoiseSession:
                 t.error = RuntimeError("the session was closed")
         self._tickets = []
         self.plan = None
-        for name in ("z", "x_in", "hist", "mask_rows", "guidance", "guidance_rows", "coef_rows", "row_slot", "temb", "ctrl_img", "ehs",
+        for name in ("z", "x_in", "hist", "mask_rows", "guidance", "guidance_rows", "rescale", "rescale_rows", "coef_rows", "row_slot", "temb", "ctrl_img", "ehs",
                      "garment", "_views"):
             setattr(self, name, None)
 
@@ -505,15 +515,15 @@ class DenoiseSession:
                generator=None, output_type: Optional[str] = "pil", clip_skip: Optional[int] = None, prompt_embeds=None,
                negative_prompt_embeds=None, ref_clip_hidden_states=None, ref_image_latents=None, latents=None,
                width: Optional[int] = None, height: Optional[int] = None, eta: float = 0.0, shard_over_ranks: bool = False,
-               control_guidance_start: float = 0.0, control_guidance_end: float = 1.0) -> SessionTicket:
-        """Queue one request (the per-request arguments of the pipeline's ``__call__``, with ``num_inference_steps``, ``guidance_scale``
-        and ``image_scale`` per request) and return its ticket.  Never blocks and launches nothing: the request is admitted at the
+               control_guidance_start: float = 0.0, control_guidance_end: float = 1.0, guidance_rescale: float = 0.0) -> SessionTicket:
+        """Queue one request (the per-request arguments of the pipeline's ``__call__``, with ``num_inference_steps``, ``guidance_scale``,
+        ``image_scale`` and ``guidance_rescale`` per request) and return its ticket.  Never blocks and launches nothing: the request is admitted at the
         start of the first ``step()`` in which a slot is free.  ``num_images_per_prompt`` = n takes n slots."""
         self._check_open()
         check_request(size=(self.image_width, self.image_height), width=width, height=height, num_inference_steps=num_inference_steps,
                       guidance_scale=guidance_scale, image_scale=image_scale, eta=eta, shard_over_ranks=shard_over_ranks,
                       control_guidance_start=control_guidance_start, control_guidance_end=control_guidance_end,
-                      num_images_per_prompt=num_images_per_prompt, slots=self.S)
+                      num_images_per_prompt=num_images_per_prompt, slots=self.S, guidance_rescale=guidance_rescale)
         n = int(num_images_per_prompt)
         if self.controlnet is not None and pose_image is None:
             raise ValueError("pose_image: every request of a ControlNet session brings its pose image")
@@ -523,7 +533,8 @@ class DenoiseSession:
             raise ValueError(f"latents {tuple(latents.shape)}: this session's requests have latents {(n, 4, self.h, self.w)} "
                              f"({self.image_width} x {self.image_height}, one geometry per session)")
         req = _Request(prompt=prompt, null_prompt=null_prompt, negative_prompt=negative_prompt, ref_image=ref_image, ref_clip_image=ref_clip_image,
-                       pose_image=pose_image, guidance_scale=float(guidance_scale), image_scale=float(image_scale), n=n, generator=generator,
+                       pose_image=pose_image, guidance_scale=float(guidance_scale), image_scale=float(image_scale), guidance_rescale=float(guidance_rescale),
+                       n=n, generator=generator,
                        output_type=output_type, clip_skip=clip_skip, prompt_embeds=prompt_embeds, negative_prompt_embeds=negative_prompt_embeds,
                        ref_clip_hidden_states=ref_clip_hidden_states, ref_image_latents=ref_image_latents, latents=latents)
         ticket = SessionTicket(req)
@@ -592,6 +603,9 @@ class DenoiseSession:
                 raise ValueError(f"garment features of layer {k}: {tuple(v.shape)} does not fit this session's {tuple(self.garment.get(k, v).shape)}")
         self.z[s].copy_(req.z0[j])
         self.guidance[s] = req.guidance_scale
+        if req.guidance_rescale:          # (a released slot is back at 0: a request that does not ask costs no launch)
+            self.rescale[s] = req.guidance_rescale
+            self._rescale_seen = True
         ts = torch.tensor([float(t) for t in run.timesteps], dtype=torch.float32).to(self.device)
         req.temb[j] = [e._time_embed_rows(ts) for e in self.encoders]          # the request's whole schedule, once
 
@@ -607,9 +621,21 @@ class DenoiseSession:
         v.mask_rows[r] = req.image_scale
         if self.compact:
             v.guidance_rows[r] = req.guidance_scale
+            if req.guidance_rescale:
+                v.rescale_rows[r] = req.guidance_rescale
         if v.ctrl_img is not None:
             v.ctrl_img[r].copy_(req.pose[0])
             v.ctrl_img[B + r].copy_(req.pose[0])
+
+    def _release_rescale(self, run: PlanRun):
+        """the slot -- and, compacting, the batch row -- of a run that leaves goes back to guidance_rescale 0: an idle row of eps may
+        hold anything and must not be read"""
+        if not run.payload[0]._request.guidance_rescale:
+            return
+        if run.slot is not None:
+            self.rescale[run.slot] = 0.0
+        if self.compact and run.row is not None:
+            self.rescale_rows[run.row] = 0.0
 
     def _write_inputs(self, v: _WidthViews, runs: List[PlanRun]):
         """the UNet input of the rows of ``runs`` from their slots' fp32 latents, both CFG halves (``imd_session_input_rows``; the
@@ -643,6 +669,7 @@ class DenoiseSession:
                 ticket.error = e
                 for r in ticket._runs:          # the whole request leaves: its slots and queue entries are free again
                     if not r.done:
+                        self._release_rescale(r)
                         self.plan.cancel(r)
                 raise
         if not self.plan.running:
@@ -653,6 +680,8 @@ class DenoiseSession:
         moved = [r for r in lay.rows if r is not None] if lay.repack else lay.placed
         if lay.repack:
             v.mask_rows.zero_()
+            if self._rescale_seen:
+                v.rescale_rows.zero_()
         for run in moved:
             self._write_row(v, run)
         if moved:
@@ -677,6 +706,10 @@ class DenoiseSession:
         finally:
             for e in self.encoders:
                 e.clear_time_embeddings()
+        # guidance_rescale: ONE launch in front of the step, only while a running request asks for it; eps and both arrays by ROW
+        if any(run.payload[0]._request.guidance_rescale for _, run, _ in st.running):
+            ops.guidance_rescale(eps.view(2 * B, self.HW, 4), guidance=v.guidance_rows if self.compact else self.guidance,
+                                 rescale=v.rescale_rows if self.compact else self.rescale)
         step_rows_at, step_rows = (ops.unipc_step_rows_at, ops.unipc_step_rows) if self.plan.unipc else (ops.sampler_step_rows_at, ops.sampler_step_rows)
         if self.compact:
             step_rows_at(self.z, eps, v.x_flat, guidance=v.guidance_rows, coef_rows=v.coef_rows, row_slot=v.row_slot, hist=self.hist)
@@ -688,6 +721,7 @@ class DenoiseSession:
         finished = []
         for run in st.finished:
             ticket, j = run.payload
+            self._release_rescale(run)
             ticket._latents[j] = self.z[run.slot].view(1, self.h, self.w, 4).permute(0, 3, 1, 2).contiguous()
             ticket._request.temb.pop(j, None)
             if all(t is not None for t in ticket._latents):

@@ -351,6 +351,24 @@ typedef struct imd_unipc_params {
                            * holds no pointer or scalar that changes between replays -- the host refreshes 76 bytes per step */
 } imd_unipc_params;
 
+/* CFG rescale (imd_guidance_rescale): Lin et al. 2023, "Common Diffusion Noise Schedules and Sample Steps Are Flawed", section 3.4 --
+ * diffusers' rescale_noise_cfg with the standard deviation over all non-batch dimensions.  Per latent row b with phi != 0, in fp32
+ * (t = eps[b], u = eps[B + b], N = 4 HW):
+ *   e = u + g (t - u);   mu_t = (sum t) / N,  mu_e = (sum e) / N;   S_t = sum (t - mu_t)^2,  S_e = sum (e - mu_e)^2
+ *   r = sqrt(S_t / S_e)  (1 if S_e == 0);   f = phi r + (1 - phi);   eps[b] = eps[B + b] = f e
+ * Both CFG halves receive the rescaled guided prediction, so the step launch that follows recovers it exactly whatever guidance it
+ * is given (eps_c - eps_u == 0): the launch goes between the UNet and ANY of the step entry points, none of which changes.  A row
+ * with phi == 0 is neither read nor written.  The reduction order is a function of HW alone (guidance_rescale.hip). */
+typedef struct imd_guidance_rescale_params {
+    uint32_t struct_bytes; /* sizeof(imd_guidance_rescale_params) in the caller's view; checked on entry */
+    float* eps;            /* [2B, HW, 4] fp32, in place: rows b and B + b both receive the rescaled guided prediction */
+    int B, HW;
+    float guidance;
+    const float* guidance_rows; /* NULL, or DEVICE [B] fp32, read instead of `guidance` */
+    float rescale;
+    const float* rescale_rows;  /* NULL, or DEVICE [B] fp32, read instead of `rescale`; 0 = leave the row alone */
+} imd_guidance_rescale_params;
+
 /* Per-row LoRA with the low-rank path unfolded (imd_lora_expand_rows).  For a linear layer with LoRA,
  *   y = x W^T + s_row ((x D^T) U^T) = [x | s_row (x D^T)] [W | U]^T
  * so a scale that differs from row to row goes into the ACTIVATIONS and the augmented weight [W | U] (network_alpha / rank folded into
@@ -714,6 +732,11 @@ int imd_unipc_step_rows(const imd_unipc_params* p, const float* coef_rows /* DEV
  * imd_unipc_step_rows, row_slot NULL or not 4-byte aligned, slots < 1, B > slots. */
 int imd_unipc_step_rows_at(const imd_unipc_params* p, const float* coef_rows /* DEVICE [B][24] fp32 */,
                            const int* row_slot /* DEVICE [B] */, int slots, void* stream);
+/* The CFG rescale of the rows that ask for it, in place on eps, as ONE launch (one workgroup per latent row) in front of any of the
+ * step entry points above; see imd_guidance_rescale_params.  A scalar rescale of 0 without rescale_rows launches nothing.  Errors
+ * without launching: null params, a foreign struct_bytes, eps NULL or not 16-byte aligned, guidance_rows or rescale_rows not 4-byte
+ * aligned, B < 1 or HW < 1, a scalar rescale that is not finite or outside [0, 1], a scalar guidance that is not finite. */
+int imd_guidance_rescale(const imd_guidance_rescale_params* p, void* stream);
 
 /* Augmented activation rows [x | s_row (x D^T)] of a per-row-scaled LoRA layer; see imd_lora_rows_params (lora_rows.hip).  Errors
  * without launching: a foreign struct_bytes, a null pointer, an unknown dtype, C or T not a multiple of 16, C outside 64..1280, T
