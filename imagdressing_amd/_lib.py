@@ -140,6 +140,15 @@ class GuidanceRescaleParams(_Sized):
                 ("guidance", C.c_float), ("guidance_rows", C.c_void_p), ("rescale", C.c_float), ("rescale_rows", C.c_void_p)]
 
 
+NOISE_ROW_WORDS = 8                  # IMD_NOISE_ROW_WORDS: seed_lo, seed_hi, image, draw, active, 3 reserved
+NOISE_KINDS = {"normal": 0, "bits": 1}
+
+
+class NoiseParams(_Sized):
+    _fields_ = [("struct_bytes", C.c_uint32), ("out", C.c_void_p), ("key_rows", C.c_void_p),
+                ("rows", C.c_int), ("HW", C.c_int), ("kind", C.c_int)]
+
+
 class LoraRowsParams(_Sized):
     _fields_ = [("struct_bytes", C.c_uint32), ("x", C.c_void_p), ("down", C.c_void_p), ("row_scale", C.c_void_p), ("out", C.c_void_p),
                 ("M", C.c_int), ("C", C.c_int), ("T", C.c_int), ("E", C.c_int), ("rows_per_entry", C.c_int),
@@ -228,6 +237,7 @@ SYMBOLS = {
     "imd_unipc_step_rows": (C.c_int, [C.POINTER(UnipcParams), C.c_void_p, C.c_void_p]),
     "imd_unipc_step_rows_at": (C.c_int, [C.POINTER(UnipcParams), C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "imd_guidance_rescale": (C.c_int, [C.POINTER(GuidanceRescaleParams), C.c_void_p]),
+    "imd_noise_rows": (C.c_int, [C.POINTER(NoiseParams), C.c_void_p]),
     "imd_lora_expand_rows": (C.c_int, [C.POINTER(LoraRowsParams), C.c_void_p]),
     "imd_session_input_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "imd_image_resample": (C.c_int, [C.POINTER(ImageResampleParams), C.c_void_p]),

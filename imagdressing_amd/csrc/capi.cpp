@@ -341,6 +341,12 @@ int imd_guidance_rescale(const imd_guidance_rescale_params* p, void* stream) {
     return imd_launch_guidance_rescale(*p, (hipStream_t)stream);
 }
 
+int imd_noise_rows(const imd_noise_params* p, void* stream) {
+    IMD_REQUIRE(p != nullptr, "noise_rows: null params");
+    IMD_REQUIRE_SIZE(p, "noise_rows");
+    return imd_launch_noise_rows(*p, (hipStream_t)stream);
+}
+
 int imd_session_input_rows(const float* z, const int* row_slot, const float* in_scale_rows, void* x_in, int B, int slots, int HW,
                            int dtype_code, void* stream) {
     return imd_launch_session_input_rows(z, row_slot, in_scale_rows, (bf16_t*)x_in, B, slots, HW, dtype_code, (hipStream_t)stream);

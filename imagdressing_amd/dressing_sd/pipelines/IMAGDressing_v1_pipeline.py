@@ -21,11 +21,13 @@ class IMAGDressing_v1(PipelineBase):
     def set_scale(self, scale):                                            # :342-345
         set_scale_by_type(self.unet, RefSAttnProcessor2_0, scale=scale)
 
-    def open_session(self, slots: int, width: int, height: int, controlnet_conditioning_scale: float = 1.0, compact: bool = False, widths=None):
+    def open_session(self, slots: int, width: int, height: int, controlnet_conditioning_scale: float = 1.0, compact: bool = False, widths=None,
+                     device_noise: Optional[bool] = None):
         """In-flight batching: a :class:`imagdressing_amd.session.DenoiseSession` with ``slots`` slots at ``width`` x ``height``
         (``controlnet_conditioning_scale`` is accepted for a uniform surface; this pipeline has no ControlNet).  ``compact`` / ``widths``:
-        run only as many batch rows as requests are running (``_open_session``)."""
-        return self._open_session(slots, width, height, compact=compact, widths=widths)
+        run only as many batch rows as requests are running; ``device_noise``: per-request seeded noise, None = follow
+        ``enable_device_noise`` (``_open_session``)."""
+        return self._open_session(slots, width, height, compact=compact, widths=widths, device_noise=device_noise)
 
     @torch.no_grad()
     def __call__(self, prompt, null_prompt, negative_prompt, ref_image, width, height, num_inference_steps, guidance_scale,
@@ -58,12 +60,14 @@ class IMAGDressing_v1(PipelineBase):
         ref_lat, cloth_tokens, G = self._request_garments(R, null_prompt, ref_image, ref_image_latents, ref_clip_image,
                                                           ref_clip_hidden_states, device)              # :409-427, :454-458
         self.scheduler.set_timesteps(num_inference_steps, device=device)      # (init_noise_sigma may depend on the schedule; IMAGDressing_v1_pipeline.py:386)
-        lat = self.prepare_latents(R * num_images_per_prompt, 4, width, height, torch.float32, device, generator, latents)
+        keyed = self._request_noise(kwargs, generator, R, num_images_per_prompt)          # enable_device_noise: seed= / generator -> one key per row
+        lat = self.prepare_latents(R * num_images_per_prompt, 4, width, height, torch.float32, device, generator, latents, noise_plan=keyed)
         lat = self._shard(lat, shard_over_ranks)
         sa = self._sa_states(ref_lat, cloth_tokens, shard_over_ranks, G)                             # :465-480
         out = self.denoise(latents=lat, prompt_embeds=prompt_embeds, negative_prompt_embeds=negative_prompt_embeds,
                            sa_hidden_states=sa, num_inference_steps=num_inference_steps, guidance_scale=guidance_scale,
                            callback=callback, callback_steps=callback_steps or 1, trace=trace,
                            eta=eta, generator=generator, variance_noise=kwargs.get("variance_noise"),          # eta: :451, :530
-                           requests=R, image_scale=scale_rows, guidance_rescale=guidance_rescale)
+                           requests=R, image_scale=scale_rows, guidance_rescale=guidance_rescale,
+                           noise_plan=self._shard_noise(keyed, shard_over_ranks))
         return self._decode(out, output_type, generator)                                            # :544-547

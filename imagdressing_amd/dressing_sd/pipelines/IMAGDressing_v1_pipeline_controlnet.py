@@ -31,13 +31,15 @@ class IMAGDressing_v1(PipelineBase):
                     negative_prompt_embeds=negative_prompt_embeds, scale=float(first(scale)),
                     keep=controlnet_keep(num_inference_steps, float(first(start)), float(first(end))))
 
-    def open_session(self, slots: int, width: int, height: int, controlnet_conditioning_scale: float = 1.0, compact: bool = False, widths=None):
+    def open_session(self, slots: int, width: int, height: int, controlnet_conditioning_scale: float = 1.0, compact: bool = False, widths=None,
+                     device_noise: Optional[bool] = None):
         """In-flight batching: a :class:`imagdressing_amd.session.DenoiseSession` with ``slots`` slots at ``width`` x ``height``; every
         request brings its own pose image, ``controlnet_conditioning_scale`` holds for the whole session (the gate is one scalar per
         launch).  A pipeline built without a ControlNet opens the session of the base pipeline.  ``compact`` / ``widths``: run only as
-        many batch rows as requests are running (``_open_session``)."""
+        many batch rows as requests are running; ``device_noise``: per-request seeded noise, None = follow ``enable_device_noise``
+        (``_open_session``)."""
         return self._open_session(slots, width, height, controlnet_conditioning_scale, with_controlnet=self.controlnet is not None,
-                                  compact=compact, widths=widths)
+                                  compact=compact, widths=widths, device_noise=device_noise)
 
     @torch.no_grad()
     def __call__(self, prompt, null_prompt, negative_prompt, ref_image, width, height, num_inference_steps, guidance_scale,
@@ -79,12 +81,13 @@ class IMAGDressing_v1(PipelineBase):
         if control is not None:
             height, width = control["hw"]                                   # :501
         self.scheduler.set_timesteps(num_inference_steps, device=device)      # (init_noise_sigma may depend on the schedule; IMAGDressing_v1_pipeline.py:386)
-        lat = self._shard(self.prepare_latents(R * num_images_per_prompt, 4, width, height, torch.float32, device, generator, latents),
-                          shard_over_ranks)
+        keyed = self._request_noise(kwargs, generator, R, num_images_per_prompt)          # enable_device_noise: one key per latent row
+        lat = self._shard(self.prepare_latents(R * num_images_per_prompt, 4, width, height, torch.float32, device, generator, latents,
+                                               noise_plan=keyed), shard_over_ranks)
         sa = self._sa_states(ref_lat, cloth_tokens, shard_over_ranks, G)
         out = self.denoise(latents=lat, prompt_embeds=prompt_embeds, negative_prompt_embeds=negative_prompt_embeds,
                            sa_hidden_states=sa, num_inference_steps=num_inference_steps, guidance_scale=guidance_scale,
                            control=control, callback=callback, callback_steps=callback_steps or 1, trace=trace,
                            eta=eta, generator=generator, variance_noise=kwargs.get("variance_noise"), requests=R, image_scale=scale_rows,
-                           guidance_rescale=guidance_rescale)
+                           guidance_rescale=guidance_rescale, noise_plan=self._shard_noise(keyed, shard_over_ranks))
         return self._decode(out, output_type, generator)

@@ -341,6 +341,9 @@ class IMAGDressing_v1(PipelineBase):
             image_latents = self.vae.encode(x).latent_dist.sample(generator) * self.vae.config.scaling_factor
         elif image_latents is None:                                           # (before the noise draw, like diffusers' prepare_latents)
             image_latents = self._image_latents(as_batch(image, "image"), device, generator, size=(height, width))
+        keyed = self._request_noise(kwargs, generator, R, num_images_per_prompt)          # enable_device_noise: one key per latent row
+        if noise is None and latents is None and keyed is not None:
+            noise = keyed.initial(h, w)          # draw 0: the initial noise, add_noise's noise and the blend's, as below
         if noise is None:
             noise = latents if latents is not None else randn_tensor((B, 4, h, w), generator=generator, device=device, dtype=torch.float32)
         init_steps = min(int(num_inference_steps * float(strength)), num_inference_steps)
@@ -381,7 +384,8 @@ class IMAGDressing_v1(PipelineBase):
                            sa_hidden_states=sa, num_inference_steps=num_inference_steps, guidance_scale=guidance_scale,
                            control=control, inpaint=inpaint, callback=callback, callback_steps=callback_steps, trace=trace,
                            eta=eta, generator=generator, variance_noise=kwargs.get("variance_noise"), t_start=t_start,
-                           requests=R, image_scale=scale_rows, guidance_rescale=guidance_rescale)
+                           requests=R, image_scale=scale_rows, guidance_rescale=guidance_rescale,
+                           noise_plan=self._shard_noise(keyed, shard_over_ranks))
         if overlay:
             return self._decode_overlay(out, output_type, front)
         return self._decode(out, output_type, generator)

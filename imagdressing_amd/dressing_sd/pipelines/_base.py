@@ -117,7 +117,8 @@ class PipelineBase:
         """Opt in to HIP-graph replay of the denoising step (see ``denoise``) -- DDIM and the deterministic samplers of the fused
         sampler step (DPM-Solver++, Euler, PNDM): same kernels, same arithmetic, one graph launch per step instead of ~500 kernel
         launches.  Worth it where the loop is host-bound (small batches); ignored for UniPC (unless ``scheduler.enable_fused_step()``:
-        its one-launch step replays like the others), Euler-ancestral, step callbacks, traces,
+        its one-launch step replays like the others), Euler-ancestral (unless ``enable_device_noise()``: its noise launch is then part
+        of the captured step), step callbacks, traces,
         per-step ControlNet gating and while ``enable_deepcache`` is on."""
         self._step_graph = bool(flag)
         if not flag:
@@ -207,6 +208,43 @@ class PipelineBase:
     def disable_request_adapter_scales(self):
         return self.enable_request_adapter_scales(False)
 
+    def enable_device_noise(self, flag: bool = True):
+        """Opt in to noise that belongs to a REQUEST and is made on the device (``imd_noise_rows``, imagdressing_amd/noise.py): the
+        initial latents (unless ``latents=`` is given), the per-step noise of Euler-ancestral and of ``eta`` > 0 (unless
+        ``variance_noise=`` is given) and the inpainting blend noise become a pure function of (seed, image, draw, pixel) -- Philox4x32-10
+        and Box-Muller, one launch for all rows.  The seed of request r: the keyword ``seed`` (an int in [0, 2^64), or a list with one
+        per request), else ``generator[r].initial_seed()``, else 8 bytes of ``os.urandom``; the seeds used are left in
+        ``pipe.last_seeds``.  A request then gets the same noise alone, in a request batch, under ``enable_step_graph`` (which now
+        replays Euler-ancestral too) and in any slot of a session (``open_session``, which then admits Euler-ancestral and DDIM with
+        ``eta`` > 0).  The result CHANGES: this is not torch's random stream, the noise is fp32 and not rounded to the UNet's element
+        type, and its tails are cut at 5.77 sigma (a mass of about 1e-8); what that does to image quality with real checkpoints is
+        unmeasured.  The VAE's posterior sample stays on torch.  Off by default: every launch, bit and refusal is then today's."""
+        self._device_noise = bool(flag)
+        return self
+
+    def disable_device_noise(self):
+        return self.enable_device_noise(False)
+
+    def _request_noise(self, kwargs: Dict[str, Any], generator, R: int, images_per_request: int):
+        """the :class:`imagdressing_amd.noise.RequestNoise` of this call (``enable_device_noise``), else None; ``seed=`` is read from
+        the call's ``**kwargs`` like ``variance_noise``"""
+        seed = kwargs.get("seed")
+        if not getattr(self, "_device_noise", False):
+            if seed is not None:
+                raise ValueError("seed= is the request seed of the device noise source: call pipe.enable_device_noise() first "
+                                 "(without it the noise comes from generator=, as ever)")
+            return None
+        from ...noise import RequestNoise, resolve_seeds
+        self.last_seeds = resolve_seeds(seed, generator, R)
+        return RequestNoise(self.last_seeds, images_per_request, self.device)
+
+    def _shard_noise(self, plan, shard: bool):
+        """the rows of ``plan`` that :meth:`_shard` leaves this rank"""
+        if plan is None or not shard:
+            return plan
+        from ... import dist as imd_dist
+        return plan.shard(imd_dist.shard_bounds(plan.rows))
+
     @staticmethod
     def _adapter_scales(name, value, R, neutral):
         """-> (the value the processors get through set_scale / set_ipa_scale, per-request values for the loop or None), like
@@ -284,10 +322,14 @@ class PipelineBase:
         dt = next(self.image_encoder.parameters()).dtype
         return self.image_encoder(clip_image.to(device, dtype=dt), output_hidden_states=True).hidden_states[-2]
 
-    def prepare_latents(self, batch_size, num_channels_latents, width, height, dtype, device, generator, latents=None):
+    def prepare_latents(self, batch_size, num_channels_latents, width, height, dtype, device, generator, latents=None, noise_plan=None):
         # NB the reference passes (width, height) in this order to a (height, width) signature, and so keeps
         # shape [B, 4, width//8, height//8] semantics consistent with its own call (:440-448); we take them named.
         shape = (batch_size, num_channels_latents, height // self.vae_scale_factor, width // self.vae_scale_factor)
+        if latents is None and noise_plan is not None:          # enable_device_noise: draw 0 of every request, one launch
+            if noise_plan.rows != batch_size or num_channels_latents != 4:
+                raise ValueError(f"device noise: {noise_plan.rows} keyed rows for latents {shape}")
+            latents = noise_plan.initial(shape[2], shape[3])
         if latents is None:
             latents = randn_tensor(shape, generator=generator, device=device, dtype=torch.float32)
         return latents.to(device=device, dtype=torch.float32) * self.scheduler.init_noise_sigma
@@ -334,7 +376,7 @@ class PipelineBase:
                 eta: float = 0.0, generator=None, variance_noise: Optional[List[torch.Tensor]] = None, t_start: int = 0,
                 requests: int = 1, image_scale: Optional[Sequence[float]] = None,
                 adapter_rows: Optional[Dict[str, Optional[Sequence[float]]]] = None,
-                guidance_rescale: Union[float, Sequence[float]] = 0.0) -> torch.Tensor:
+                guidance_rescale: Union[float, Sequence[float]] = 0.0, noise_plan=None) -> torch.Tensor:
         """latents [B, 4, h, w] fp32 -> final latents [B, 4, h, w] fp32.
 
         ``requests`` = R > 1: a request-batched call (:class:`RequestLayout`) -- latent rows [r n, (r+1) n) belong to request r
@@ -361,6 +403,12 @@ class PipelineBase:
         call or per request.  All 0: nothing new happens.  Otherwise ONE ``imd_guidance_rescale`` launch between the UNet and the step
         writes the rescaled guided prediction into both CFG halves of eps, so every fused step recovers it unchanged -- eager or captured;
         a host-stepped UniPC (``step_guided``) refuses it.
+
+        ``noise_plan`` (``enable_device_noise``; a ``noise.RequestNoise`` of B rows): the per-step noise of a stochastic step, unless
+        ``variance_noise`` is given, is draw 1 + t_start + i of each row's request, written in fp32 by ONE ``imd_noise_rows`` launch in
+        front of the step into a buffer at a fixed address; the key rows of the whole call are uploaded once.  Euler-ancestral then
+        replays under ``enable_step_graph`` (the launch is part of the captured step; the host refreshes 32 bytes of key per row next
+        to the coefficients).  DDIM with ``eta`` > 0 stays eager: its step refuses ``var_noise`` with device coefficients.
 
         ``control`` = dict(image=[1|B, 3, H, W] in [0,1] or NHWC8 bf16, prompt_embeds=[1,77,768],
         negative_prompt_embeds=[1,77,768], scale=float, keep=[float]*steps)
@@ -452,7 +500,18 @@ class PipelineBase:
             dc.full = dc_plan[i]
             return {"deepcache": dc}
 
+        dev_noise = noise_plan is not None and stochastic and variance_noise is None
+        if dev_noise:
+            if noise_plan.rows != B or Cl != 4:
+                raise ValueError(f"device noise: {noise_plan.rows} keyed rows for {B} latent rows of {Cl} channels")
+            from ...noise import step_draws
+            key_table = noise_plan.key_table(step_draws(t_start, len(timesteps)))
+            key_dev = torch.zeros_like(key_table[0])          # the captured step reads its keys here
+            noise_buf = torch.zeros(B, HW, Cl, dtype=torch.float32, device=dev)
+
         def step_noise(i):
+            if dev_noise:          # (i is None: the captured step of a graph replay)
+                return ops.noise_rows(noise_buf, key_dev if i is None else key_table[i])
             vn = variance_noise[i] if variance_noise is not None else randn_tensor((B, Cl, h, w), generator=generator, device=dev, dtype=dt)
             return vn.to(device=dev, dtype=torch.float32).permute(0, 2, 3, 1).reshape(B, HW, Cl).contiguous()
 
@@ -517,7 +576,9 @@ class PipelineBase:
 
         def run_steps():
             nonlocal z
-            use_graph = (getattr(self, "_step_graph", False) and not dc_on and not multistep and not stochastic and callback is None and trace is None
+            # (a stochastic step replays only where its noise is made on the device: Euler-ancestral with enable_device_noise)
+            use_graph = (getattr(self, "_step_graph", False) and not dc_on and not multistep and (not stochastic or (noisy and dev_noise))
+                         and callback is None and trace is None
                          and len(timesteps) > 2 and (keeps is None or len(set(keeps)) == 1) and ops.ATTN_EVENT_HOOK is None)
             if use_graph:
                 # HIP-graph replay of the denoising step (opt-in, ``enable_step_graph``): step 0 runs eagerly on the pipeline's side stream
@@ -541,6 +602,8 @@ class PipelineBase:
                 side.wait_stream(cur)
                 with torch.cuda.stream(side):
                     t_dev.copy_(t_table[0:1]); coef_dev.copy_(coef_table[0])
+                    if dev_noise:
+                        key_dev.copy_(key_table[0])
                     temb_bufs = [torch.empty_like(tab[0:1]) for tab in tables]     # fixed addresses inside the captured step, refreshed like t_dev
                     for e, buf, tab in zip(encs, temb_bufs, tables):
                         buf.copy_(tab[0:1])
@@ -554,6 +617,8 @@ class PipelineBase:
                         g.capture_end()
                     for i in range(1, steps_n):
                         t_dev.copy_(t_table[i:i + 1]); coef_dev.copy_(coef_table[i])
+                        if dev_noise:
+                            key_dev.copy_(key_table[i])
                         for buf, tab in zip(temb_bufs, tables):
                             buf.copy_(tab[i:i + 1])
                         g.replay()
@@ -589,16 +654,19 @@ class PipelineBase:
 
     # ---- in-flight batching (imagdressing_amd/session.py) ----
     def _open_session(self, slots: int, width: int, height: int, controlnet_conditioning_scale: float = 1.0, with_controlnet: bool = False,
-                      compact: bool = False, widths=None):
+                      compact: bool = False, widths=None, device_noise: Optional[bool] = None):
         """A denoising session of ``slots`` latent rows at one geometry: requests are submitted at any time, enter a free slot at the
         start of any step, run their own number of steps and leave when done (``session.DenoiseSession``).  DPM-Solver++, Euler, PNDM
         and DDIM (eta = 0), UniPC after ``scheduler.enable_fused_step()``; refused with UniPC otherwise, Euler-ancestral and while ``enable_deepcache`` is on; ``enable_step_graph`` is ignored.
         ``compact=True``: every step runs a batch only as wide as the running requests need -- the smallest entry of ``widths`` (None:
         every width 1..slots; else a strictly increasing tuple that ends at ``slots``) -- and a request's bits then depend on the
-        widths it ran under."""
+        widths it ran under.
+        ``device_noise`` (None: follow ``enable_device_noise``): every request carries a seed (``submit(seed=...)``) and its noise is
+        made on the device, one ``imd_noise_rows`` launch per step for all slots -- Euler-ancestral is then accepted, and so is
+        ``submit(eta=...)`` > 0 under DDIM, per request; a request's latents do not depend on its slot or on the other requests."""
         from ...session import DenoiseSession
         return DenoiseSession(self, slots, width, height, controlnet_conditioning_scale, with_controlnet=with_controlnet, compact=compact,
-                              widths=widths)
+                              widths=widths, device_noise=device_noise)
 
     # ---- request-batched calls (RequestLayout) ----
     def _request_count(self, args: Dict[str, Any], per_call: Dict[str, Any], shard_over_ranks: bool) -> int:

@@ -1481,6 +1481,54 @@ def unipc_step_rows_at(z, eps, x_next, *, guidance, coef_rows, row_slot, hist=No
     return z
 
 
+# ---- seeded noise that belongs to a request (csrc/noise.hip) ----
+NOISE_ROW_WORDS = L.NOISE_ROW_WORDS
+NOISE_COUNTER = {"launches": 0}          # imd_noise_rows launches of this process (tests check that the switch-off call makes none)
+
+
+def noise_key_row(seed, image, draw, active=True):
+    """One row of ``imd_noise_rows``: ``[seed_lo, seed_hi, image, draw, active, 0, 0, 0]`` as 8 Python ints below 2^32.  ``seed``: an
+    int in [0, 2^64); ``image`` (the index inside num_images_per_prompt) and ``draw`` (0: the initial noise, 1 + i: the variance noise
+    of step index i of the request's full schedule): ints in [0, 2^32).  bool, float and anything out of range raise ValueError."""
+    for name, v, bits in (("seed", seed, 64), ("image", image, 32), ("draw", draw, 32)):
+        if isinstance(v, bool) or not isinstance(v, int) or not 0 <= v < (1 << bits):
+            raise ValueError(f"noise_key_row: {name} must be an int in [0, 2^{bits}), got {v!r}")
+    return [seed & 0xFFFFFFFF, seed >> 32, image, draw, 1 if active else 0, 0, 0, 0]
+
+
+def noise_key_rows(rows, device=None):
+    """:func:`noise_key_row` rows as the [rows, 8] int32 tensor ``imd_noise_rows`` reads (the words reinterpreted as int32: torch has
+    no arithmetic on uint32); a host tensor when ``device`` is None."""
+    import numpy as np
+    a = np.asarray(rows, dtype=np.uint32).reshape(-1, NOISE_ROW_WORDS)
+    t = torch.from_numpy(a.view(np.int32).copy())
+    return t if device is None else t.to(device)
+
+
+def noise_rows(out, key_rows, *, kind="normal"):
+    """Seeded noise of every active row in one launch (``imd_noise_rows``): ``out`` [rows, HW, 4] contiguous on the device -- fp32 for
+    ``kind="normal"`` (standard normals by Philox4x32-10 and Box-Muller, |x| <= 5.77), int32 for ``kind="bits"`` (the four raw
+    Philox words of each pixel) -- and ``key_rows`` [rows, 8] int32 on the device (:func:`noise_key_rows`).  The value of a pixel
+    depends on its key row and its index alone; a row whose ``active`` word is 0 keeps its bytes."""
+    if kind not in L.NOISE_KINDS:
+        raise L.ImdError(f"noise_rows: unknown kind {kind!r} (one of {sorted(L.NOISE_KINDS)})")
+    if not isinstance(out, torch.Tensor) or out.dim() != 3 or out.shape[2] != 4:
+        raise L.ImdError(f"noise_rows: out {tuple(getattr(out, 'shape', ()))}: expected [rows, HW, 4]")
+    ensure_device(out.device)
+    rows, HW = out.shape[0], out.shape[1]
+    if (not isinstance(key_rows, torch.Tensor) or key_rows.dtype != torch.int32 or key_rows.numel() != rows * NOISE_ROW_WORDS
+            or not key_rows.is_contiguous()):
+        raise L.ImdError(f"noise_rows: key_rows must be a contiguous device int32 tensor [{rows}, {NOISE_ROW_WORDS}] "
+                         f"(ops.noise_key_rows), got {getattr(key_rows, 'dtype', type(key_rows))} {tuple(getattr(key_rows, 'shape', ()))}")
+    p = L.NoiseParams()
+    p.out = _dev(out, torch.float32 if kind == "normal" else torch.int32, "out")
+    p.key_rows = _dev(key_rows, torch.int32, "key_rows")
+    p.rows, p.HW, p.kind = rows, HW, L.NOISE_KINDS[kind]
+    L.check(L.load().imd_noise_rows(C.byref(p), _stream()))
+    NOISE_COUNTER["launches"] += 1
+    return out
+
+
 # ---- CFG rescale in front of any step (csrc/guidance_rescale.hip) ----
 def guidance_rescale(eps, *, guidance, rescale):
     """The CFG rescale of Lin et al. 2023, section 3.4 (diffusers' ``rescale_noise_cfg``) in place on ``eps`` [2B,HW,4] fp32

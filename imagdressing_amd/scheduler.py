@@ -445,15 +445,24 @@ class SamplerHistory:
         return ops.sampler_coefs(row.m_x, row.m_e, row.z_x, row.z_m, zh, row.z_n, row.b_img, row.b_noise, row.in_scale, store)
 
 
-def ddim_row(scheduler: "DDIMScheduler", t: int) -> SamplerRow:
-    """The deterministic (eta = 0) DDIM step at timestep ``t`` as a :class:`SamplerRow`, in float64: m = e and
+def ddim_row(scheduler: "DDIMScheduler", t: int, eta: float = 0.0) -> SamplerRow:
+    """The DDIM step at timestep ``t`` as a :class:`SamplerRow`, in float64: m = e and
         z' = (sqrt(a_prev) / sqrt(a_t)) z + (sqrt(1 - a_prev) - sqrt(a_prev) sqrt(1 - a_t) / sqrt(a_t)) e
     -- for the callers that give every latent row its own coefficients (``imd_sampler_step_rows``, the denoising session).  A function
     and not a ``plan`` method of :class:`DDIMScheduler`: the pipelines' loop picks the fused-sampler path by that attribute, and the
-    default DDIM loop stays on ``imd_ddim_cfg_step``."""
+    default DDIM loop stays on ``imd_ddim_cfg_step``.
+    ``eta`` > 0: the stochastic step of diffusers' ``DDIMScheduler.step`` with ``variance_noise`` -- sigma = ``scheduler.sigma(t, eta)``,
+    the direction term becomes sqrt(1 - a_prev - sigma^2) and z_n = sigma scales the step's noise operand.  ``eta`` = 0 is the row
+    above, bit for bit."""
     a_t, a_prev = float(scheduler.alpha(t)), float(scheduler.alpha_prev(t))
     sa_t, sa_p = np.sqrt(a_t), np.sqrt(a_prev)
-    return SamplerRow(m_x=0.0, m_e=1.0, z_x=sa_p / sa_t, z_m=np.sqrt(1.0 - a_prev) - sa_p * np.sqrt(1.0 - a_t) / sa_t, keep=False)
+    if float(eta) == 0.0:
+        return SamplerRow(m_x=0.0, m_e=1.0, z_x=sa_p / sa_t, z_m=np.sqrt(1.0 - a_prev) - sa_p * np.sqrt(1.0 - a_t) / sa_t, keep=False)
+    if float(eta) < 0.0:
+        raise ValueError(f"eta must be >= 0, got {eta}")
+    sigma = float(eta) * np.sqrt((1.0 - a_prev) / (1.0 - a_t) * (1.0 - a_t / a_prev))
+    return SamplerRow(m_x=0.0, m_e=1.0, z_x=sa_p / sa_t, z_m=np.sqrt(1.0 - a_prev - sigma * sigma) - sa_p * np.sqrt(1.0 - a_t) / sa_t,
+                      z_n=sigma, keep=False)
 
 
 def _train_alphas_cumprod(num_train_timesteps, beta_start, beta_end, beta_schedule):

@@ -36,20 +36,22 @@ from typing import Any, Dict, List, Optional
 import torch
 
 from . import ops
+from .noise import RequestNoise, check_seed, resolve_seeds, step_draw
 from .scheduler import DDIMScheduler, SamplerHistory, UniPCHistory, ddim_row, unipc_fused
 
 
 # ---- refusals (pure: nothing here touches a device) ----
-def check_scheduler(scheduler) -> None:
+def check_scheduler(scheduler, *, device_noise: bool = False) -> None:
     """The samplers a session can drive: every deterministic one whose step is ONE affine row -- DPM-Solver++, Euler, PNDM
-    (``plan``), DDIM (``ddim_row``) and UniPC with ``enable_fused_step()`` (``plan_fused``)."""
+    (``plan``), DDIM (``ddim_row``) and UniPC with ``enable_fused_step()`` (``plan_fused``).  ``device_noise`` (the session draws its
+    noise per request on the device, ``imd_noise_rows``): Euler-ancestral too."""
     name = type(scheduler).__name__
     if unipc_fused(scheduler):
         return
     if hasattr(scheduler, "step_guided"):
         raise NotImplementedError(f"open_session: scheduler {name} (UniPC) updates the latents with host-built linear combinations of "
                                   "whole tensors, not one affine row per latent row; use DPM-Solver++, Euler, PNDM or DDIM")
-    if getattr(scheduler, "stochastic", False):
+    if getattr(scheduler, "stochastic", False) and not device_noise:
         raise NotImplementedError(f"open_session: scheduler {name} (Euler-ancestral) draws noise at every step; a session runs the "
                                   "deterministic samplers (DPM-Solver++, Euler, PNDM, DDIM)")
     if not hasattr(scheduler, "plan") and not isinstance(scheduler, DDIMScheduler):
@@ -65,14 +67,26 @@ def check_pipeline(pipe) -> None:
 
 def check_request(*, size, width=None, height=None, num_inference_steps, guidance_scale, image_scale=1.0, eta=0.0,
                   shard_over_ranks=False, control_guidance_start=0.0, control_guidance_end=1.0, num_images_per_prompt=1, slots=1,
-                  guidance_rescale=0.0) -> None:
-    """what ``submit`` refuses, before anything is launched or queued.  ``size`` = (width, height) of the session."""
+                  guidance_rescale=0.0, device_noise=False, scheduler=None, seed=None) -> None:
+    """what ``submit`` refuses, before anything is launched or queued.  ``size`` = (width, height) of the session.  ``device_noise``
+    (the session draws its noise per request on the device): ``eta`` > 0 is accepted where ``scheduler`` is DDIM and raises ValueError
+    for any other sampler, ``seed`` must be None or an int in [0, 2^64); without it ``eta`` > 0 and ``seed`` are refused."""
     for name, v in (("num_inference_steps", num_inference_steps), ("guidance_scale", guidance_scale), ("image_scale", image_scale),
                     ("guidance_rescale", guidance_rescale)):
         if isinstance(v, (list, tuple)):
             raise ValueError(f"{name} is per request in a session: submit one request per call, got {list(v)}")
-    if float(eta) > 0.0:
+    if float(eta) > 0.0 and not device_noise:
         raise NotImplementedError("eta > 0: the stochastic DDIM step draws noise per step; a session runs the deterministic samplers")
+    if not device_noise and seed is not None:
+        raise ValueError("seed= is the request seed of the device noise source: open the session with device_noise=True or call "
+                         "pipe.enable_device_noise() first")
+    if device_noise:
+        if isinstance(eta, (list, tuple)) or not (math.isfinite(float(eta)) and float(eta) >= 0.0):
+            raise ValueError(f"eta must be one finite value >= 0 per request, got {eta!r}")
+        if float(eta) > 0.0 and scheduler is not None and not isinstance(scheduler, DDIMScheduler):
+            raise ValueError(f"eta > 0 is the stochastic DDIM step; this session's sampler is {type(scheduler).__name__}")
+        if seed is not None:
+            check_seed(seed)
     if shard_over_ranks:
         raise NotImplementedError("shard_over_ranks: a session lives on one rank (sessions over several ranks are a later change)")
     if (width is not None and int(width) != int(size[0])) or (height is not None and int(height) != int(size[1])):
@@ -94,9 +108,11 @@ def check_request(*, size, width=None, height=None, num_inference_steps, guidanc
 # ---- the plan ----
 class PlanRun:
     """One latent row's run: its own scheduler instance (``set_timesteps(n)``), history bookkeeping and position."""
-    __slots__ = ("scheduler", "ring", "timesteps", "steps", "i", "slot", "row", "in_scale", "ready", "payload")
+    __slots__ = ("scheduler", "ring", "timesteps", "steps", "i", "slot", "row", "in_scale", "ready", "payload", "seed", "image", "eta")
 
-    def __init__(self, scheduler, num_inference_steps: int, payload=None):
+    def __init__(self, scheduler, num_inference_steps: int, payload=None, seed: Optional[int] = None, image: int = 0, eta: float = 0.0):
+        # the noise key of the run (a plan with device_noise): the request's seed and the image index inside the request; eta: DDIM's
+        self.seed, self.image, self.eta = seed, int(image), float(eta)
         sch = copy.copy(scheduler)          # the class and configuration of the pipeline's scheduler; set_timesteps rebinds, never mutates
         sch.set_timesteps(int(num_inference_steps))
         self.scheduler = sch
@@ -143,10 +159,15 @@ class PlanRun:
             coefs = self.ring.coefs(self.scheduler.plan_fused(self.i))
             self.in_scale = coefs[ops.UNIPC_IN_SCALE]
             return coefs
-        row = self.scheduler.plan(self.i) if self.affine else ddim_row(self.scheduler, self.timesteps[self.i])
+        row = self.scheduler.plan(self.i) if self.affine else ddim_row(self.scheduler, self.timesteps[self.i], self.eta)
         coefs = self.ring.coefs(row)
         self.in_scale = coefs[11]
         return coefs
+
+    @property
+    def noisy(self) -> bool:
+        """its steps read the noise operand: Euler-ancestral, or DDIM with eta > 0"""
+        return bool(getattr(self.scheduler, "stochastic", False)) or (not self.affine and not self.unipc and self.eta > 0.0)
 
 
 class PlanStep:
@@ -154,11 +175,15 @@ class PlanStep:
     position) of every row that takes this step, ``finished`` = the runs for which it is the last.  And the same step seen by batch
     ROW: ``width`` rows ran, row r carried slot ``row_slot[r]`` (-1: idle) with the coefficient row ``coef_rows[r]`` and the timestep
     ``row_timesteps[r]``; ``repack`` = the rows were laid out anew before this step.  A plan that does not compact has width =
-    slots, row r = slot r and never repacks."""
-    __slots__ = ("rows", "timesteps", "running", "finished", "width", "row_slot", "repack", "coef_rows", "row_timesteps")
+    slots, row r = slot r and never repacks.  A plan with ``device_noise``: ``noise`` = (slot, seed, image, draw) of every running
+    row whose step reads noise and ``key_rows`` [slots][8] = the ``ops.noise_key_row`` of every SLOT for this step (inactive for
+    every other slot), whether the plan compacts or not; otherwise both are None."""
+    __slots__ = ("rows", "timesteps", "running", "finished", "width", "row_slot", "repack", "coef_rows", "row_timesteps", "noise", "key_rows")
 
-    def __init__(self, rows, timesteps, running, finished, width=None, row_slot=None, repack=False, coef_rows=None, row_timesteps=None):
+    def __init__(self, rows, timesteps, running, finished, width=None, row_slot=None, repack=False, coef_rows=None, row_timesteps=None,
+                 noise=None, key_rows=None):
         self.rows, self.timesteps, self.running, self.finished = rows, timesteps, running, finished
+        self.noise, self.key_rows = noise, key_rows
         self.width = len(rows) if width is None else width
         self.row_slot = list(range(len(rows))) if row_slot is None else row_slot
         self.repack = repack
@@ -193,10 +218,14 @@ def check_widths(slots: int, widths) -> tuple:
 
 
 class SessionPlan:
-    def __init__(self, slots: int, scheduler, compact: bool = False, widths=None):
+    def __init__(self, slots: int, scheduler, compact: bool = False, widths=None, *, device_noise: bool = False):
         if int(slots) < 1:
             raise ValueError(f"slots must be >= 1, got {slots}")
-        check_scheduler(scheduler)
+        check_scheduler(scheduler, device_noise=bool(device_noise))
+        self.device_noise = bool(device_noise)
+        # the step launch may be handed a noise operand: the session's sampler can be stochastic (Euler-ancestral, or DDIM -- eta is per request)
+        self.noisy = self.device_noise and not unipc_fused(scheduler) and (bool(getattr(scheduler, "stochastic", False))
+                                                                         or isinstance(scheduler, DDIMScheduler))
         self.S = int(slots)
         self.compact = bool(compact)
         if widths is not None and not self.compact:
@@ -216,11 +245,18 @@ class SessionPlan:
         self._laid: Optional[PlanLayout] = None
         self.repacks = 0
 
-    def submit(self, num_inference_steps: int, payload=None) -> PlanRun:
+    def submit(self, num_inference_steps: int, payload=None, *, seed: Optional[int] = None, image: int = 0, eta: float = 0.0) -> PlanRun:
+        """``seed`` / ``image`` (a plan with ``device_noise``): the noise key of the run; ``eta`` > 0: the stochastic DDIM step"""
         if unipc_fused(self.scheduler) != self.unipc:
             raise RuntimeError("the scheduler's fused-step switch changed since the session was opened: its buffers and its step kernel "
                                "were chosen for the other setting; open a new session")
-        run = PlanRun(self.scheduler, num_inference_steps, payload)
+        if float(eta) > 0.0 and not self.device_noise:
+            raise NotImplementedError("eta > 0: the stochastic DDIM step draws noise per step; a session runs the deterministic samplers")
+        if float(eta) > 0.0 and not isinstance(self.scheduler, DDIMScheduler):
+            raise ValueError(f"eta > 0 is the stochastic DDIM step; this session's sampler is {type(self.scheduler).__name__}")
+        run = PlanRun(self.scheduler, num_inference_steps, payload, seed=seed, image=image, eta=eta)
+        if self.noisy and run.noisy and seed is None:
+            raise ValueError("a run whose steps read noise needs its request's seed (DenoiseSession.submit resolves it)")
         self.queue.append(run)
         return run
 
@@ -292,6 +328,8 @@ class SessionPlan:
         lay = self.layout()
         self._laid = None
         rows, ts, running, finished = [], [], [], []
+        noise = [] if self.noisy else None          # (slot, seed, image, draw): draw 1 + i, i the step index of the run's own schedule
+        keys = [ops.noise_key_row(0, 0, 0, active=False) for _ in range(self.S)] if self.noisy else None
         for s, run in enumerate(self._slots):
             if run is None:
                 rows.append(list(self.idle_row))
@@ -299,6 +337,9 @@ class SessionPlan:
                 continue
             ts.append(run.timesteps[run.i])
             running.append((s, run, run.i))
+            if self.noisy and run.noisy:
+                noise.append((s, run.seed, run.image, step_draw(run.i)))
+                keys[s] = ops.noise_key_row(run.seed, run.image, step_draw(run.i))
             rows.append(self.coef_row(run.next_coefs(), active=True))
             run.i += 1
             if run.done:
@@ -306,9 +347,9 @@ class SessionPlan:
                 self._slots[s] = None
                 self._rows[run.row] = None
         if not self.compact:
-            return PlanStep(rows, ts, running, finished)
+            return PlanStep(rows, ts, running, finished, noise=noise, key_rows=keys)
         row_slot = [-1 if r is None else r.slot for r in lay.rows]
-        return PlanStep(rows, ts, running, finished, width=lay.width, row_slot=row_slot, repack=lay.repack,
+        return PlanStep(rows, ts, running, finished, width=lay.width, row_slot=row_slot, repack=lay.repack, noise=noise, key_rows=keys,
                         coef_rows=[list(self.idle_row) if s < 0 else rows[s] for s in row_slot],
                         row_timesteps=[None if s < 0 else ts[s] for s in row_slot])
 
@@ -344,6 +385,7 @@ class SessionTicket:
         self._output = None
         self.error: Optional[BaseException] = None
         self.latents: Optional[torch.Tensor] = None
+        self.seed: Optional[int] = None          # the request's noise seed (a session with device_noise)
 
     @property
     def done(self) -> bool:
@@ -411,9 +453,11 @@ class DenoiseSession:
     """``pipe.open_session(slots=S, width=W, height=H, compact=False, widths=None)``; a context manager.  See the module docstring."""
 
     def __init__(self, pipe, slots: int, width: int, height: int, controlnet_conditioning_scale: float = 1.0, with_controlnet: bool = False,
-                 compact: bool = False, widths=None):
+                 compact: bool = False, widths=None, device_noise: Optional[bool] = None):
         check_pipeline(pipe)
-        self.plan = SessionPlan(slots, pipe.scheduler, compact=compact, widths=widths)
+        # device_noise None: follow the pipeline's switch (enable_device_noise) as it stands when the session opens
+        self.device_noise = bool(getattr(pipe, "_device_noise", False)) if device_noise is None else bool(device_noise)
+        self.plan = SessionPlan(slots, pipe.scheduler, compact=compact, widths=widths, device_noise=self.device_noise)
         self.pipe = pipe
         self.compact = self.plan.compact
         vsf = pipe.vae_scale_factor
@@ -441,6 +485,10 @@ class DenoiseSession:
         self.rescale = torch.zeros(S, dtype=torch.float32, device=dev)
         self.rescale_rows = torch.zeros(S, dtype=torch.float32, device=dev) if self.compact else None
         self._rescale_seen = False          # a request with a non-zero value was admitted: repacks then clear the rows first
+        # device noise, where the sampler can be stochastic: both by SLOT in plain and compacting sessions alike (imd_sampler_step_rows_at
+        # reads noise by slot).  noise is ZERO-FILLED: a row with z_n = 0 multiplies it, so it must never hold uninitialised bytes
+        self.noise = torch.zeros(S, self.HW, 4, dtype=torch.float32, device=dev) if self.plan.noisy else None
+        self.key_rows = torch.zeros(S, ops.NOISE_ROW_WORDS, dtype=torch.int32, device=dev) if self.plan.noisy else None
         self.coef_rows = torch.zeros(S, self.plan.row_floats, dtype=torch.float32, device=dev)
         self.row_slot = torch.arange(S, dtype=torch.int32, device=dev)
         self._row_slot_host = list(range(S))
@@ -501,7 +549,7 @@ class DenoiseSession:
                 t.error = RuntimeError("the session was closed")
         self._tickets = []
         self.plan = None
-        for name in ("z", "x_in", "hist", "mask_rows", "guidance", "guidance_rows", "rescale", "rescale_rows", "coef_rows", "row_slot", "temb", "ctrl_img", "ehs",
+        for name in ("z", "x_in", "hist", "noise", "key_rows", "mask_rows", "guidance", "guidance_rows", "rescale", "rescale_rows", "coef_rows", "row_slot", "temb", "ctrl_img", "ehs",
                      "garment", "_views"):
             setattr(self, name, None)
 
@@ -515,15 +563,24 @@ class DenoiseSession:
                generator=None, output_type: Optional[str] = "pil", clip_skip: Optional[int] = None, prompt_embeds=None,
                negative_prompt_embeds=None, ref_clip_hidden_states=None, ref_image_latents=None, latents=None,
                width: Optional[int] = None, height: Optional[int] = None, eta: float = 0.0, shard_over_ranks: bool = False,
-               control_guidance_start: float = 0.0, control_guidance_end: float = 1.0, guidance_rescale: float = 0.0) -> SessionTicket:
+               control_guidance_start: float = 0.0, control_guidance_end: float = 1.0, guidance_rescale: float = 0.0,
+               seed: Optional[int] = None) -> SessionTicket:
         """Queue one request (the per-request arguments of the pipeline's ``__call__``, with ``num_inference_steps``, ``guidance_scale``,
         ``image_scale`` and ``guidance_rescale`` per request) and return its ticket.  Never blocks and launches nothing: the request is admitted at the
-        start of the first ``step()`` in which a slot is free.  ``num_images_per_prompt`` = n takes n slots."""
+        start of the first ``step()`` in which a slot is free.  ``num_images_per_prompt`` = n takes n slots.
+        A session with ``device_noise``: ``seed`` (an int in [0, 2^64); else ``generator.initial_seed()``, else 8 bytes of
+        ``os.urandom``; kept in ``ticket.seed``) keys the request's noise -- draw 0 its initial latents (unless ``latents`` is given),
+        draw 1 + i its step i -- and ``eta`` > 0 is the stochastic DDIM step of this request alone."""
         self._check_open()
         check_request(size=(self.image_width, self.image_height), width=width, height=height, num_inference_steps=num_inference_steps,
                       guidance_scale=guidance_scale, image_scale=image_scale, eta=eta, shard_over_ranks=shard_over_ranks,
                       control_guidance_start=control_guidance_start, control_guidance_end=control_guidance_end,
-                      num_images_per_prompt=num_images_per_prompt, slots=self.S, guidance_rescale=guidance_rescale)
+                      num_images_per_prompt=num_images_per_prompt, slots=self.S, guidance_rescale=guidance_rescale,
+                      device_noise=self.device_noise, scheduler=self.plan.scheduler, seed=seed)
+        if self.device_noise:
+            if isinstance(generator, (list, tuple)):
+                raise ValueError("generator: a session request has one seed; pass one generator or seed=")
+            seed = resolve_seeds(seed, generator, 1)[0]
         n = int(num_images_per_prompt)
         if self.controlnet is not None and pose_image is None:
             raise ValueError("pose_image: every request of a ControlNet session brings its pose image")
@@ -534,12 +591,13 @@ class DenoiseSession:
                              f"({self.image_width} x {self.image_height}, one geometry per session)")
         req = _Request(prompt=prompt, null_prompt=null_prompt, negative_prompt=negative_prompt, ref_image=ref_image, ref_clip_image=ref_clip_image,
                        pose_image=pose_image, guidance_scale=float(guidance_scale), image_scale=float(image_scale), guidance_rescale=float(guidance_rescale),
-                       n=n, generator=generator,
+                       n=n, generator=generator, seed=seed, eta=float(eta),
                        output_type=output_type, clip_skip=clip_skip, prompt_embeds=prompt_embeds, negative_prompt_embeds=negative_prompt_embeds,
                        ref_clip_hidden_states=ref_clip_hidden_states, ref_image_latents=ref_image_latents, latents=latents)
         ticket = SessionTicket(req)
+        ticket.seed = seed
         for j in range(n):
-            ticket._runs.append(self.plan.submit(num_inference_steps, payload=(ticket, j)))
+            ticket._runs.append(self.plan.submit(num_inference_steps, payload=(ticket, j), seed=seed, image=j, eta=float(eta)))
             ticket._latents.append(None)
         self._tickets.append(ticket)
         return ticket
@@ -567,6 +625,8 @@ class DenoiseSession:
                                  f"{(self.image_height, self.image_width)}")
             req.pose = img if (img.dim() == 4 and img.shape[-1] == 8 and img.dtype == dt) else nchw_to_nhwc8(img.to(dev), dt)
         lat = req.latents
+        if lat is None and self.device_noise:          # draw 0 of the request's seed, image j in row j: what the solo call draws
+            lat = RequestNoise([req.seed], req.n, dev).initial(self.h, self.w)
         if lat is None:
             lat = randn_tensor((req.n, 4, self.h, self.w), generator=req.generator, device=dev, dtype=torch.float32)
         req.z0 = (lat.to(device=dev, dtype=torch.float32) * run.scheduler.init_noise_sigma).permute(0, 2, 3, 1).reshape(req.n, self.HW, 4).contiguous()
@@ -710,11 +770,18 @@ class DenoiseSession:
         if any(run.payload[0]._request.guidance_rescale for _, run, _ in st.running):
             ops.guidance_rescale(eps.view(2 * B, self.HW, 4), guidance=v.guidance_rows if self.compact else self.guidance,
                                  rescale=v.rescale_rows if self.compact else self.rescale)
+        # device noise: the key rows of the slots whose step reads noise (every other slot inactive), ONE imd_noise_rows launch over all
+        # slots, and the noise operand of the step -- only while such a row runs: a deterministic step keeps its launches and its bits
+        kw = {}
+        if st.noise:
+            self.key_rows.copy_(ops.noise_key_rows(st.key_rows))
+            ops.noise_rows(self.noise, self.key_rows)
+            kw["noise"] = self.noise
         step_rows_at, step_rows = (ops.unipc_step_rows_at, ops.unipc_step_rows) if self.plan.unipc else (ops.sampler_step_rows_at, ops.sampler_step_rows)
         if self.compact:
-            step_rows_at(self.z, eps, v.x_flat, guidance=v.guidance_rows, coef_rows=v.coef_rows, row_slot=v.row_slot, hist=self.hist)
+            step_rows_at(self.z, eps, v.x_flat, guidance=v.guidance_rows, coef_rows=v.coef_rows, row_slot=v.row_slot, hist=self.hist, **kw)
         else:
-            step_rows(self.z, eps, v.x_flat, guidance=self.guidance, coef_rows=v.coef_rows, hist=self.hist)
+            step_rows(self.z, eps, v.x_flat, guidance=self.guidance, coef_rows=v.coef_rows, hist=self.hist, **kw)
         self.steps_run += 1
         self._last_width = B
         self.steps_at_width[B] = self.steps_at_width.get(B, 0) + 1

@@ -369,6 +369,28 @@ typedef struct imd_guidance_rescale_params {
     const float* rescale_rows;  /* NULL, or DEVICE [B] fp32, read instead of `rescale`; 0 = leave the row alone */
 } imd_guidance_rescale_params;
 
+/* Seeded standard-normal noise that belongs to a REQUEST (imd_noise_rows): the four channels of a latent pixel are a pure function
+ * of (seed, image, draw, pixel), whatever the batch, the row, the slot of a session or the launch that writes them:
+ *   (x0, x1, x2, x3) = Philox4x32-10(counter = (pixel, image, draw, 0), key = (seed_lo, seed_hi))     Salmon et al., SC'11:
+ *       multipliers M0 = 0xD2511F53, M1 = 0xCD9E8D57, Weyl constants 0x9E3779B9 / 0xBB67AE85 added to the key after each round; a round
+ *       maps (c0, c1, c2, c3) to (hi(M1 c2) ^ c1 ^ k0, lo(M1 c2), hi(M0 c0) ^ c3 ^ k1, lo(M0 c0))
+ *   u_j = ((x_j >> 9) + 0.5) 2^-23                          exact in fp32, in [2^-24, 1 - 2^-24]
+ *   r0 = sqrt(-2 ln u0), r1 = sqrt(-2 ln u2);   out = (r0 cos 2 pi u1, r0 sin 2 pi u1, r1 cos 2 pi u3, r1 sin 2 pi u3)      (Box-Muller)
+ * `pixel` is the NHWC pixel index inside the latent, in [0, HW).  |out| <= sqrt(2 ln 2^24) = 5.77: the tails beyond are cut (a mass of
+ * about 1e-8).  The values are fp32 and are NOT torch's stream.  Draw numbering of the pipelines: draw 0 is a request's initial noise
+ * (also the inpainting `noise`), draw 1 + i the variance noise of step index i of the request's full schedule; image j of
+ * num_images_per_prompt is counter word image = j.  A row whose `active` word is 0 is neither read nor written.  The launch goes in
+ * front of imd_sampler_step / _rows / _rows_at (their `noise` operand), none of which changes. */
+#define IMD_NOISE_ROW_WORDS 8   /* per row: [0] seed_lo [1] seed_hi [2] image [3] draw [4] active (0: the row is skipped) [5..7] reserved, 0 */
+#define IMD_NOISE_NORMAL 0      /* out: fp32 standard normals */
+#define IMD_NOISE_BITS   1      /* out: the four raw uint32 Philox words (for exact tests) */
+typedef struct imd_noise_params {
+    uint32_t struct_bytes; /* sizeof(imd_noise_params) in the caller's view; checked on entry */
+    void* out;             /* [rows, HW, 4] fp32 or uint32, 16-byte aligned */
+    const uint32_t* key_rows; /* DEVICE [rows][IMD_NOISE_ROW_WORDS], 16-byte aligned */
+    int rows, HW, kind;
+} imd_noise_params;
+
 /* Per-row LoRA with the low-rank path unfolded (imd_lora_expand_rows).  For a linear layer with LoRA,
  *   y = x W^T + s_row ((x D^T) U^T) = [x | s_row (x D^T)] [W | U]^T
  * so a scale that differs from row to row goes into the ACTIVATIONS and the augmented weight [W | U] (network_alpha / rank folded into
@@ -737,6 +759,11 @@ int imd_unipc_step_rows_at(const imd_unipc_params* p, const float* coef_rows /* 
  * without launching: null params, a foreign struct_bytes, eps NULL or not 16-byte aligned, guidance_rows or rescale_rows not 4-byte
  * aligned, B < 1 or HW < 1, a scalar rescale that is not finite or outside [0, 1], a scalar guidance that is not finite. */
 int imd_guidance_rescale(const imd_guidance_rescale_params* p, void* stream);
+/* Seeded normals (or the raw Philox words) of every active row as ONE launch (one 16-byte store per pixel, grid (pixels, rows)); see
+ * imd_noise_params.  The result depends on the key row and the pixel alone: not on rows, the row position, the grid or the other
+ * rows.  Errors without launching: null params, a foreign struct_bytes, out or key_rows NULL or not 16-byte aligned, rows < 1 (or
+ * more than 65535), HW < 1, an unknown kind. */
+int imd_noise_rows(const imd_noise_params* p, void* stream);
 
 /* Augmented activation rows [x | s_row (x D^T)] of a per-row-scaled LoRA layer; see imd_lora_rows_params (lora_rows.hip).  Errors
  * without launching: a foreign struct_bytes, a null pointer, an unknown dtype, C or T not a multiple of 16, C outside 64..1280, T
