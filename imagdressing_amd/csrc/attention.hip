@@ -26,46 +26,11 @@
 // (running max m, running sum l) are per-lane scalars because a lane owns one query column in
 // both MFMAs; the two half-waves that share a query exchange one value per tile (max) and one
 // per phase (sum).
-#include "common.h"
-#include "imd_kernels.h"
+#include "attn_common.h"
 
 namespace {
 
-constexpr int KT = 64;                 // keys per tile
-constexpr int VSTR = KT * 2 + 16;      // bytes per V^T LDS row (9 x 16 B: conflict-free b128 reads)
-
-template <int D> struct AttnCfg {
-    static constexpr int DPK = (D + 15) / 16 * 16;
-    static constexpr int DPV = (D + 31) / 32 * 32;
-    static constexpr int NKT = DPK / 16;
-    static constexpr int NDT = DPV / 32;
-    static constexpr int KSTR = DPK * 2 + 16;
-    // V^T rows kept in LDS: the D real rows plus (when D < DPV) the all-ones row D that yields the softmax denominator.
-    // The remaining pad rows of the last 32-row MFMA block are NOT stored: their fragment reads run into the K tile
-    // that follows (finite garbage in, accumulator rows nobody reads out) -- 26 KB instead of 32 KB per workgroup for
-    // d = 40, i.e. 6 resident workgroups per CU instead of 5.
-    static constexpr int VROWS = DPV > D ? D + 1 : DPV;
-    static constexpr int VBYTES = VROWS * VSTR;
-    static constexpr int BUF = VBYTES + KT * KSTR;               // [V^T rows][K rows]
-    static_assert((DPV - VROWS) * VSTR <= KT * KSTR, "phantom V^T rows must stay inside the K tile");
-    static constexpr int KVECS = (KT * (DPK / 8) + 255) / 256;
-    static constexpr int VVECS = (D * (KT / 8) + 255) / 256;
-};
-
-typedef __attribute__((__vector_size__(4 * sizeof(uint32_t)))) uint32_t v4u;
-__device__ __forceinline__ uint4 buf_load16(const __amdgpu_buffer_rsrc_t& rs, uint32_t byte_off) {
-    const v4u v = __builtin_amdgcn_raw_buffer_load_b128(rs, (int)byte_off, 0, 0);
-    return make_uint4(v[0], v[1], v[2], v[3]);
-}
-constexpr uint32_t OOB = 0xffffffffu;
-
-// packed 3-input maximum of two fp16 lanes: on non-negative 16-bit float patterns (fp16 OR bf16) it is the maximum of
-// the patterns as integers, with inf / NaN patterns propagating
-__device__ __forceinline__ uint32_t pk_max3_f16(uint32_t a, uint32_t b, uint32_t c) {
-    uint32_t d;
-    asm("v_pk_maximum3_f16 %0, %1, %2, %3" : "=v"(d) : "v"(a), "v"(b), "v"(c));
-    return d;
-}
+constexpr int KT = AttnTile::KT, VSTR = AttnTile::VSTR;      // keys per tile, bytes per V^T LDS row
 
 template <bool F16, int D, int QW, int MINW, int KB, bool SPEC, int SCHED>
 __global__ __launch_bounds__(256, MINW) void attn_kernel(const AttnParams p) {
@@ -80,10 +45,8 @@ __global__ __launch_bounds__(256, MINW) void attn_kernel(const AttnParams p) {
     // row's tile maximum exceeds it by more than OFFS_THR (base-2 units), which keeps P <= 2^OFFS_THR.
     constexpr bool OFFS = C::DPK > D;
     constexpr float OFFS_THR = 8.0f;
-    constexpr int QPAD_T = D / 16;                    // Q fragment that holds pad slot D ...
-    constexpr int QPAD_HI = (D % 16) / 8;             // ... in the lanes of this half-wave ...
-    static_assert(!OFFS || (D % 8) == 0, "pad slot must start a 16-bit pair");   // ... as element 0 of the fragment
-    constexpr int L_DT = D / 32, L_REG = ((D % 32) & 3) + 4 * (((D % 32) >> 3)), L_HI = ((D % 32) >> 2) & 1;
+    using PS = AttnPad<D>;                            // pad slot D: the Q fragment / accumulator register that holds it
+    constexpr int QPAD_T = PS::QPAD_T, QPAD_HI = PS::QPAD_HI, L_DT = PS::L_DT, L_REG = PS::L_REG, L_HI = PS::L_HI;
     extern __shared__ __attribute__((aligned(16))) char smem[];
 
     const int tid = threadIdx.x;
@@ -91,24 +54,8 @@ __global__ __launch_bounds__(256, MINW) void attn_kernel(const AttnParams p) {
     const int wave = tid >> 6;
     const int hi = lane >> 5;
     const int col = lane & 31;
-    // XCD-aware work mapping: hardware block L runs on XCD L % 8 (private 4 MiB L2 each).  Give every XCD a
-    // contiguous slice of the (batch, head, q-tile) work list so that all q-tiles of one (batch, head) -- which
-    // re-read the same K / V^T -- hit the same L2 instead of pulling it through all eight.
     int wx, h, b;
-    {
-        const unsigned gx = gridDim.x, gy = gridDim.y, total = gridDim.x * gridDim.y * gridDim.z;
-        const unsigned L = blockIdx.x + gx * (blockIdx.y + gy * blockIdx.z);
-        const unsigned xcd = L & 7u, slot = L >> 3;
-        const unsigned q8 = total >> 3, r8 = total & 7u;          // bijective also when total % 8 != 0
-        unsigned w = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + slot;
-        if (p.flags & 1) w = L;                                    // tuning: plain dispatch order
-        // work list order: q-tile fastest, then BATCH, then head -- an XCD's slice then holds whole heads across
-        // all batch rows, i.e. the same mix of 2-phase (garment) and 1-phase rows as every other XCD
-        const unsigned gz = gridDim.z;
-        wx = (int)(w % gx);
-        b = (int)((w / gx) % gz);
-        h = (int)(w / (gx * gz));
-    }
+    attn_work_item<WORK_KNOB>(p, wx, h, b);          // XCD-aware work list; flags & 1 (tuning): plain dispatch order
     // phase-split launch (imd_attn_params.phase2_rows): batch entries >= B run the SECOND softmax of row b - B only (fp32 result to phase2_out, added to the
     // first by a follow-up elementwise launch), entries < B the first one only
     const bool split = p.phase2_rows > 0;
@@ -116,17 +63,10 @@ __global__ __launch_bounds__(256, MINW) void attn_kernel(const AttnParams p) {
     if (second_only) b -= p.B;
     const int q0 = (wx * 4 + wave) * (QW * 32);
 
-    // V^T row D (the all-ones row) of both LDS buffers, written once and never restaged
-    if (C::DPV > D) {
-        constexpr int PADV = VSTR / 16;
-        const uint32_t one2 = E::pack2(1.0f, 1.0f);
-        for (int v = tid; v < 2 * PADV; v += 256) {
-            const int bufi = v / PADV, r = v % PADV;
-            *reinterpret_cast<uint4*>(smem + bufi * C::BUF + D * VSTR + r * 16) = make_uint4(one2, one2, one2, one2);
-        }
-    }
+    // V^T row D (the all-ones row) of both LDS buffers
+    if (C::DPV > D) attn_const_row<2, C::BUF, D * VSTR, VSTR, 256>(smem, tid, E::pack2(1.0f, 1.0f));
 
-    // ---- Q fragments (B operand of S^T = K Q^T): lane = query column, 8 head-dim values ----
+    // Q fragments (B operand of S^T = K Q^T): lane = query column, 8 head-dim values, zero past N (inline here and in attention_d40.hip: 1,449 .. 21,331 lines differ)
     uint4 qf[QW][C::NKT];
 #pragma unroll
     for (int qb = 0; qb < QW; ++qb) {
@@ -157,6 +97,7 @@ __global__ __launch_bounds__(256, MINW) void attn_kernel(const AttnParams p) {
 #pragma unroll
                 for (int r = 0; r < 16; ++r) o[qb][dt][r] = 0.f;
         }
+        // operands of this phase: key count, padded V^T row length, kv batch entry b / kv_bdiv, K / V^T bases (inline in the three two-phase kernels: 1,449 lines differ)
         const int L = ph ? p.L2 : p.L1;
         const int LP = ph ? p.L2P : p.L1P;
         const int kvb = ph ? (b / p.kv2_bdiv) : (b / p.kv1_bdiv);
@@ -468,18 +409,19 @@ int launch_attn(const AttnParams& p, hipStream_t s) {
 
 }  // namespace
 
-// head-dim-40 kernel variant (tuning knob 0, imd_set_tuning(0, v)); all variants give the same result up to fp32 order:
-//   13 (default): 12 with the overflow test of the deferred maximum only on the first and last steps of a phase and a check of the
-//      softmax denominators when the phase is done (a workgroup that finds one not finite runs again as variant 12); fp16
-//      operands (round 5) with the phase's reference maximum biased by 2^4 so that P = inf needs a score 20 base-2 units above the first
-//      block's maximum; the fused out-projection runs 12;  12: 10 with the main loop unrolled over the three ring slots
-//      (compile-time LDS addresses, three-instruction staging pieces) and the order inside every MFMA slot pinned;
-//   10 (the round-3 default): attention_d40.hip, software-pipelined steps with the MFMA / VALU interleave written out (N >= 512; shorter
-//      sequences and the causal mask fall through to variant 4 below), head-dim rows 32..40 of P.V on v_mfma_f32_16x16x32,
-//      K / V^T staged by LDS-DMA when the caller guarantees K's pad column (imd_attn_params.k_pad_one), through registers
-//      otherwise;  11: as 10, always through registers;  9 / 7: the round-2 kernel (P.V as two 32x32x16 row blocks) with the
-//      same two staging rules;  6: as 7 without the pinned interleave;  8: as 7 with the deferred-maximum bound 2^12;
-//      20..39: timing ablations, -DIMD_ABLATIONS builds only
+// head-dim-40 kernel variant (tuning knob 0, imd_set_tuning(0, v)); all variants give the same result up to fp32 order.  6 .. 13 are
+// attention_d40.hip (N >= 512 and no causal mask; otherwise variant 4 below), named here by the variant bits listed there:
+//   13 (default): 12 + V_UNCHECKED -- the overflow test of the deferred maximum only on the first and last steps of a phase and a check of the
+//      softmax denominators when the phase is done (a workgroup that finds one not finite runs again as variant 12); fp16 operands (round 5)
+//      with the phase's reference maximum biased by 2^4 so that P = inf needs a score 20 base-2 units above the first block's maximum;
+//      the fused out-projection runs 10 + V_PROJ;
+//   12: 10 + V_STATIC_RING -- the main loop unrolled over the three ring slots (compile-time LDS addresses, three-instruction staging
+//      pieces) and the order inside every MFMA slot pinned; needs k_pad_one, else it runs as 10;  with out_dup 12 and 13 add V_DUP;
+//   10 (the round-3 default): V_PINNED | V_TAIL -- software-pipelined steps with the MFMA / VALU interleave written out, head-dim rows
+//      32..40 of P.V on v_mfma_f32_16x16x32 -- plus V_DMA (K / V^T staged by LDS-DMA) when the caller guarantees K's pad column
+//      (imd_attn_params.k_pad_one), through registers otherwise;  11: as 10, always through registers;
+//   9 / 7: V_PINNED alone, the round-2 kernel (P.V as two 32x32x16 row blocks), with the same two staging rules;  6: as 7 without V_PINNED;
+//      8: as 7 with the deferred-maximum bound 2^12;  20..54: ablation bits, -DIMD_ABLATIONS builds only
 //   5: as 2 with the next tile's loads issued unconditionally (+7 % over 2)
 //   2: 2 query blocks per wave, 32-key softmax blocks, speculative exp (round-1 default)
 //   4: 1 query block per wave, 32-key blocks, speculative exp      3: 1 query block, 64-key blocks, exact max every block

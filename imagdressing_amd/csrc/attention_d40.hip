@@ -24,24 +24,17 @@
 //   * the phase-0 (self) result of a two-phase row is parked in LDS (16-bit, the rounding the reference's first SDPA
 //     output has), not in the output buffer: no HBM round trip, no store -> load dependency at the phase boundary.
 #include <type_traits>
-#include "lds_dma.h"
-
-#include "common.h"
-#include "imd_kernels.h"
+#include "attn_common.h"
 
 namespace {
 
-constexpr int D = 40, DPK = 48, DPV = 64, NKT = 3;
-constexpr int KT = 64;                      // keys per staged unit (two 32-key steps)
-constexpr int KSTR = DPK * 2 + 16;          // 112 B per K row in LDS  (7 x 16 B: conflict-free b128 fragment reads)
-constexpr int VSTR = KT * 2 + 16;           // 144 B per V^T row       (9 x 16 B)
-constexpr int VROWS = D + 1;                // 40 head-dim rows + the all-ones row that yields the softmax denominator
-constexpr int VBYTES = VROWS * VSTR;        // rows 41..63 of the second 32-row MFMA block are NOT stored: their fragment
-constexpr int BUF = VBYTES + KT * KSTR;     // reads run into the K rows behind (finite garbage into accumulator rows nobody reads)
+// register-staged layout: attn_common.h::AttnCfg<40> (112-byte K rows, 144-byte V^T rows, 41 V^T rows stored, phantom rows in the K rows)
+using C40 = AttnCfg<40>;
+constexpr int D = 40, DPK = C40::DPK, DPV = C40::DPV, NKT = C40::NKT, KT = C40::KT;      // KT: keys per staged unit (two 32-key steps)
+constexpr int KSTR = C40::KSTR, VSTR = C40::VSTR, VROWS = C40::VROWS, VBYTES = C40::VBYTES, BUF = C40::BUF;
 constexpr int PARK = 4 * 5 * 1024;          // phase-0 result: 4 waves x 20 packed dwords per lane
-constexpr int PARK_T = 4 * 6 * 1024;        // ... x 24 packed dwords per lane with the 16x16x32 tail (VAR & 8192)
-static_assert((DPV - VROWS) * VSTR <= KT * KSTR, "phantom V^T rows must stay inside the K rows");
-// LDS-DMA staging (VAR & 128): `buffer_load ... lds` writes lane-linear (wave-uniform base + lane * 16 B), so rows cannot be
+constexpr int PARK_T = 4 * 6 * 1024;        // ... x 24 packed dwords per lane with the 16x16x32 tail (V_TAIL)
+// LDS-DMA staging (V_DMA): `buffer_load ... lds` writes lane-linear (wave-uniform base + lane * 16 B), so rows cannot be
 // padded; bank conflicts are avoided by choosing WHICH 16-byte piece of global memory a lane fetches instead:
 //   K  : 96-byte rows back to back; the six pieces of rows 8..15 (mod 16) are stored rotated by three
 //   V^T: 128-byte rows back to back; piece c of row d is stored at position c ^ ((d >> 1) & 7)
@@ -49,26 +42,52 @@ static_assert((DPV - VROWS) * VSTR <= KT * KSTR, "phantom V^T rows must stay ins
 constexpr int KSTR_D = DPK * 2, VSTR_D = KT * 2, VBYTES_D = VROWS * VSTR_D, BUF_D = VBYTES_D + KT * KSTR_D;
 constexpr int NRING = 3;                    // LDS-DMA ring: unit u + 2 is in flight while unit u is consumed (an L2 miss served by the
                                             // Infinity Cache takes about as long as one iteration: one unit of lead was not enough)
-// LDS per workgroup (LDS-DMA variants): NRING * BUF_D + park + 1 KB dump for the fourth wave's third (empty) DMA piece
-static_assert((DPV - VROWS) * VSTR_D <= KT * KSTR_D, "phantom V^T rows must stay inside the K rows");
+static_assert(phantom_rows_fit(DPV, VROWS, VSTR_D, KT * KSTR_D), "phantom V^T rows must stay inside the K rows");
 
-typedef __attribute__((__vector_size__(4 * sizeof(uint32_t)))) uint32_t v4u;
-__device__ __forceinline__ uint4 buf_load16(const __amdgpu_buffer_rsrc_t& rs, uint32_t byte_off) {
-    const v4u v = __builtin_amdgcn_raw_buffer_load_b128(rs, (int)byte_off, 0, 0);
-    return make_uint4(v[0], v[1], v[2], v[3]);
-}
-constexpr uint32_t OOB = 0xffffffffu;
-
-// packed 3-input maximum: on non-negative 16-bit float patterns (fp16 OR bf16) it is the maximum of the patterns as
-// integers, with inf / NaN patterns propagating
-typedef _Float16 h2_t __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ uint32_t pk_max3(uint32_t a, uint32_t b, uint32_t c) {      // -> one v_pk_maximum3_f16
-    const h2_t x = __builtin_bit_cast(h2_t, a), y = __builtin_bit_cast(h2_t, b), z = __builtin_bit_cast(h2_t, c);
-    return __builtin_bit_cast(uint32_t, __builtin_elementwise_maximum(__builtin_elementwise_maximum(x, y), z));
-}
+// ---- the variant word VAR of attn40_kernel<F16, THR, VAR>: one bit per choice, values fixed (they are part of the kernel symbols) ----
+enum : int {
+    // product bits (the variants imd_launch_attention_d40 routes to in every build)
+    V_PINNED = 1,               // MFMA / VALU interleave of a step written out slot by slot and pinned with sched_barrier
+    V_DMA = 128,                // K / V^T staged by LDS-DMA into a ring of three units (needs imd_attn_params.k_pad_one); else through registers
+    V_TAIL = 8192,              // head-dim rows 32..40 of P.V on v_mfma_f32_16x16x32 (see above attn40_body)
+    V_PROJ = 1048576,           // out-projection fused: O tiles stored write-through, the last head of a row block projects (attn_out_proj)
+    V_STATIC_RING = 2097152,    // main loop unrolled over the three ring slots: compile-time LDS addresses, three-instruction DMA pieces (STAT in the body)
+    V_UNCHECKED = 4194304,      // (with V_STATIC_RING) interior steps without the overflow test; denominators checked per phase, checked re-run (attn40_kernel)
+    V_DUP = 8388608,            // the phase-0 result of every row is also stored to p.out_dup (DUP in the body)
+    // bits that exist only under -DIMD_ABLATIONS.  Correct results, measured no faster:
+    V_PLAIN_ORDER = 2,          // plain (not XCD-aware) work order, whatever p.flags says (no variant sets it)
+    V_WAVES8 = 32768,           // 8 waves = 512 queries per workgroup, one workgroup per CU (V_DMA only; see above attn40_body)
+    V_DMA_NONOP = 65536,        // the loop's DMA pieces without their five leading wait states
+    V_PD3 = 131072,             // (V_TAIL) LDS fragment reads three fragments ahead of their use instead of two
+    V_PD4 = 262144,             // ... four fragments ahead
+    // timing experiments, results are WRONG:
+    V_NO_EXP = 4,               // exp2 replaced by a move
+    V_NO_BARRIER = 8,           // no barrier in the loop
+    V_NO_STAGING = 16,          // no global loads / LDS stores in the loop
+    V_NO_PV = 32,               // no P.V MFMAs
+    V_NO_QK = 64,               // 2 of 6 QK^T MFMAs
+    V_ONE_FRAG = 256,           // one LDS fragment read per step
+    V_LDS_100K = 512,           // 100 KB of LDS per workgroup (one workgroup = one wave per SIMD)
+    V_NO_MAX = 2048,            // no packed-max / overflow test
+    V_CYCLES = 4096,            // s_memtime instrumentation (per-phase cycle sums of every wave's loop, added into the first words of `out`)
+};
+// what follows from VAR, each in one place: the body, the kernel's launch bounds and the launcher read it here
+template <int VAR> struct Var40 {
+    static constexpr bool DMA = (VAR & V_DMA) != 0, TAIL = (VAR & V_TAIL) != 0, PROJ = (VAR & V_PROJ) != 0;
+    static constexpr bool STAT = (VAR & V_STATIC_RING) != 0, UNCHK = (VAR & V_UNCHECKED) != 0, DUP = (VAR & V_DUP) != 0;
+    static constexpr int NW = (VAR & V_WAVES8) ? 8 : 4, NT = NW * 64;                // waves / threads per workgroup
+    static constexpr int PARKW = (TAIL ? PARK_T : PARK) / 4, PARKB = NW * PARKW;     // phase-0 park bytes per wave / workgroup
+    static constexpr int BUFB = DMA ? BUF_D : BUF, VBY = DMA ? VBYTES_D : VBYTES;
+    // LDS per workgroup.  LDS-DMA variants: NRING * BUF_D + park + 1 KB dump for the fourth wave's third (empty) DMA piece
+    static constexpr int LDS_BYTES = (VAR & V_LDS_100K) ? 100 * 1024 : DMA ? NRING * BUF_D + PARKB + 1024 : 2 * BUF + PARKB;
+    static_assert(NW == 4 || DMA, "the 8-wave workgroup exists for the LDS-DMA staging only");
+    static_assert(!STAT || (DMA && TAIL && NW == 4), "the static-ring loop exists for the 4-wave LDS-DMA kernel with the 16x16x32 tail");
+    static_assert(!PROJ || (TAIL && NW == 4), "the fused out-projection lives in the 4-wave kernel with the 16x16x32 tail");
+    static_assert(!DUP || (STAT && !PROJ), "the duplicated phase-0 store lives in the static-ring kernel without the fused out-projection");
+};
 
 // ------------------------------------------------------------------------------------------------------------------------------
-// PROJ (VAR & 1048576, round 3): the block's out-projection (to_out[0] + bias + residual, attention_processor.py:614-617) inside the
+// PROJ (V_PROJ, round 3): the block's out-projection (to_out[0] + bias + residual, attention_processor.py:614-617) inside the
 // attention launch -- the level-0 hybrid block becomes two launches (norm1 + q/k/v projection, this one).  The projection needs
 // all 8 heads of a row, a workgroup owns one head of 256 rows, and the heads of a row block run on different XCDs (private,
 // non-coherent L2s), so the heads are joined the way gemm_common.h joins K slices: every workgroup stores its O tile WRITE-THROUGH
@@ -199,59 +218,63 @@ __device__ __forceinline__ void attn_out_proj(const AttnParams& p, int b, int ro
     }
 }
 
-// VAR bit 0: MFMA / VALU interleave written out and pinned   bit 1: plain (not XCD-aware) work order
-//   8192 (TAIL): head-dim rows 32..40 of O^T += V^T P^T (+ the all-ones row 40 that yields the softmax denominator) on
+// Source of an LDS-DMA piece: the byte offset inside K / V^T, for unit 0, of the 16 bytes that land at LDS slot `sl` (= 64 * wave-instruction + lane)
+// of a unit's K rows / V^T rows -- the source-side swizzles of the layout above.  K: slot sl = piece cs of row r, fetched from piece (cs - 3) mod 6 in
+// rows 8..15 (mod 16).  V^T: slot sl = position sl & 7 of row dd, fetched from chunk ch = position ^ swizzle; under TAIL rows 32.. carry the swizzle
+// the 16x16x32 fragment read wants (tfd in the body).  r / ch come back too: the run-time ring tells from them what lies before the operand's start.
+// (Straight-line on purpose: one helper holding the K / V^T branch changed 86,436 lines of the file's assembly at the run-time ring, 2,908 at the static one.)
+__device__ __forceinline__ int k_piece_src(int sl, int& r) {
+    r = sl / 6;
+    const int cs = sl % 6, c = (cs + 6 - 3 * ((r >> 3) & 1)) % 6;
+    return (32 + r) * (DPK * 2) + c * 16;
+}
+template <bool TAIL>
+__device__ __forceinline__ int v_piece_src(int sl, int LP, int& ch) {
+    const int dd = sl >> 3, rt = dd - 32;
+    const int sw = (TAIL && dd >= 32) ? (((rt >> 1) & 7) ^ ((rt >= 4 && rt < 12) ? 2 : 0)) : ((dd >> 1) & 7);
+    ch = (sl & 7) ^ sw;
+    return (dd * LP + ch * 8 - 32) * 2;
+}
+
+// V_TAIL: head-dim rows 32..40 of O^T += V^T P^T (+ the all-ones row 40 that yields the softmax denominator) on
 //   v_mfma_f32_16x16x32 instead of a second 32x32x16 row block: 16 padded rows instead of 32, i.e. 6 instead of 7
 //   MFMA-equivalents per query block and 32-key step (issued / algorithmic matrix work 1.41 -> 1.21).  The packed P registers
 //   of a 32x32 S^T tile hold one query per LANE COLUMN (l & 31); the 16x16x32 B operand wants one query per l & 15 with the
 //   four 16-lane rows carrying four 8-key slot groups: ONE v_permlane16_swap_b32 per register pair (g = 0 word, g = 1 word)
 //   turns them into the operands of the two 16-query halves (lane row k then carries keys {0..7, 16..23, 8..15, 24..31}[k]
 //   of the step; the V^T fragment is read in the same slot order).  Accumulators: 2 x (16 + 2 x 4) instead of 2 x 32.
-// ABLATION bits (timing experiments only, results are WRONG): 4: exp2 replaced by a move   8: no barrier in the loop
-//   16: no global loads / LDS stores in the loop   32: no P.V MFMAs   64: no QK^T MFMAs   256: one LDS fragment read per step
-//   512: 100 KB of LDS per workgroup (one workgroup = one wave per SIMD)   2048: no packed-max / overflow test
-//   4096: s_memtime instrumentation (per-phase cycle sums of every wave's loop, added into the first words of `out`)
-//   32768 (WG512): 8 waves = 512 queries per workgroup (one workgroup per CU instead of two): a staged K / V^T unit serves twice
+// V_WAVES8: 8 waves = 512 queries per workgroup (one workgroup per CU instead of two): a staged K / V^T unit serves twice
 //   the queries, i.e. every wave issues 2 instead of 3 LDS-DMA pieces per 64 keys (the DMA issue sequence costs ~15 % of the
 //   4-wave kernel: profiles/r3b_attn_ablations.jsonl) and there is one barrier domain per CU.  LDS-DMA staging only.
 template <bool F16, int THR, int VAR>
 __device__ __attribute__((always_inline)) bool attn40_body(const AttnParams& p) {
     using E = El<F16>;
-    constexpr bool DMA = (VAR & 128) != 0;
-    constexpr bool TAIL = (VAR & 8192) != 0;
-    constexpr bool PROJ = (VAR & 1048576) != 0;            // out-projection fused: O tiles stored write-through, last head of a row block projects
-    // STAT (VAR & 2097152, round 4): the main loop unrolled over the three ring slots, so that every LDS address of an iteration -- fragment
+    using V = Var40<VAR>;
+    constexpr bool DMA = V::DMA, TAIL = V::TAIL, PROJ = V::PROJ;
+    // STAT (V_STATIC_RING, round 4): the main loop unrolled over the three ring slots, so that every LDS address of an iteration -- fragment
     // reads AND the LDS-DMA destinations -- is a compile-time offset; the staging sequence of a piece shrinks from ~15 instructions (ring
     // arithmetic, out-of-range selects compiled to branches, M0 save / restore, five wait states) to three (s_add m0 / s_nop / buffer_load)
     // plus one running-offset add.  The issue-mix probe (tools/probes/issue_mix_probe.hip) puts this kernel's step within 15 % of what its
     // MFMA + VALU + LDS + DMA mix costs in isolation; what is left above that is scalar / address bookkeeping like this.
-    constexpr bool STAT = (VAR & 2097152) != 0;
-    constexpr bool UNCHK = (VAR & 4194304) != 0;          // (with STAT) interior steps without the overflow test: experiment, see variant 13
-    // DUP (VAR & 8388608, round 6): the phase-0 (self-attention) result of every row is ALSO stored to p.out_dup -- the first hybrid block of
+    constexpr bool STAT = V::STAT, UNCHK = V::UNCHK;      // UNCHK: interior steps without the overflow test, see attn40_kernel
+    // DUP (V_DUP, round 6): the phase-0 (self-attention) result of every row is ALSO stored to p.out_dup -- the first hybrid block of
     // the CFG batch: cond and uncond rows of an image have bit-identical Q / K / V there (same latent, same timestep, nothing text- or
     // garment-dependent upstream), so the uncond row's whole output IS the cond row's first phase.  The launch runs the cond rows only
     // (8 instead of 12 phase units at batch 4) and writes both: out = O1/l1 + s2 O2/l2 (cond), out_dup = O1/l1 (uncond) -- the same
     // 16-bit rounding of O1/l1 the one-phase row stores and the two-phase row parks, hence bit-identical to the 2B-row launch.
-    constexpr bool DUP = (VAR & 8388608) != 0;
-    static_assert(!DUP || (STAT && !PROJ), "the duplicated phase-0 store lives in the static-ring kernel without the fused out-projection");
+    constexpr bool DUP = V::DUP;
     // fp16 under UNCHK (round 5): the phase's reference maximum is the first block's maximum PLUS this bias, i.e. P = 2^(s - m_first - 4):
     // the first block's largest P is 2^-4 and fp16's 65504 is reached only by a score 20 base-2 units (a factor 10^6 in weight) above the
     // first 32 keys' maximum -- the end-of-phase denominator test (inf / NaN) then re-runs the workgroup checked.  The price is at the
     // other end: P below 2^-14 is an fp16 subnormal (the MFMA keeps subnormal inputs, tools/probes/mfma_subnormal_probe.hip), below
     // 2^-25 it is 0 -- keys more than 21 units below the first maximum (weight < 5e-7 each) instead of 25 in the checked kernel.
     constexpr float FIRST_BIAS = (F16 && UNCHK) ? 4.0f : 0.0f;
-    static_assert(!STAT || ((VAR & 128) && (VAR & 8192) && !(VAR & 32768)), "the static-ring loop exists for the 4-wave LDS-DMA kernel with the 16x16x32 tail");
-    static_assert(!PROJ || (TAIL && !(VAR & 32768)), "the fused out-projection lives in the 4-wave kernel with the 16x16x32 tail");
-    constexpr int NW = (VAR & 32768) ? 8 : 4;              // waves per workgroup
-    constexpr int NT = NW * 64;
+    constexpr int NW = V::NW, NT = V::NT;
     constexpr int NPIECE = (11 + NW - 1) / NW;             // LDS-DMA pieces every wave issues per unit (dummies included)
-    static_assert(NW == 4 || DMA, "the 8-wave workgroup exists for the LDS-DMA staging only");
-    constexpr int PARKW = (TAIL ? PARK_T : PARK) / 4;      // phase-0 park bytes per wave
-    constexpr int PARKB = NW * PARKW;
-    constexpr int BUFB = DMA ? BUF_D : BUF, VBY = DMA ? VBYTES_D : VBYTES;
+    constexpr int PARKW = V::PARKW, PARKB = V::PARKB, BUFB = V::BUFB, VBY = V::VBY;
     constexpr float OFFS_THR = (float)THR;                 // deferred maximum: P <= 2^THR (base-2 units)
-    constexpr int QPAD_T = D / 16, QPAD_HI = (D % 16) / 8;  // Q fragment / half-wave holding pad slot 40 (element 0 of the fragment)
-    constexpr int L_DT = D / 32, L_REG = ((D % 32) & 3) + 4 * ((D % 32) >> 3), L_HI = ((D % 32) >> 2) & 1;   // accumulator row 40
+    using PS = AttnPad<D>;                                 // pad slot 40: the Q fragment / accumulator register that holds it
+    constexpr int QPAD_T = PS::QPAD_T, QPAD_HI = PS::QPAD_HI, L_DT = PS::L_DT, L_REG = PS::L_REG, L_HI = PS::L_HI;
     extern __shared__ __attribute__((aligned(16))) char smem[];
 
     const int tid = threadIdx.x;
@@ -259,32 +282,17 @@ __device__ __attribute__((always_inline)) bool attn40_body(const AttnParams& p) 
     const int wave = tid >> 6;
     const int hi = lane >> 5;
     const int col = lane & 31;
-    // XCD-aware work list (hardware block L runs on XCD L % 8): q-tile fastest, then batch, then head; every XCD gets a
-    // contiguous slice, i.e. all q-tiles that re-read one (batch, head)'s K / V^T share one L2, and every XCD sees the same mix
-    // of two-phase (garment) and one-phase rows
     int wx, h, b;
     {
-        const unsigned gx = gridDim.x, gy = gridDim.y, gz = gridDim.z, total = gx * gy * gz;
-        const unsigned Lb = blockIdx.x + gx * (blockIdx.y + gy * blockIdx.z);
-        const unsigned xcd = Lb & 7u, slot = Lb >> 3;
-        const unsigned q8 = total >> 3, r8 = total & 7u;          // bijective also when total % 8 != 0
-        unsigned w = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + slot;
-        if ((VAR & 2) || (p.flags & 1)) w = Lb;
-        wx = (int)(w % gx);
-        b = (int)((w / gx) % gz);
-        h = (int)(w / (gx * gz));
+        const unsigned w = attn_work_index<(VAR & V_PLAIN_ORDER) ? WORK_PLAIN : WORK_KNOB>(p);      // XCD-aware work list (attn_work_item: 112 lines differ)
+        attn_work_split(w, wx, h, b);
     }
     const int q0 = (wx * NW + wave) * 64;
 
-    // V^T row 40 (all ones) of both buffers: written once, never restaged
-    {
-        constexpr int PADV = (DMA ? VSTR_D : VSTR) / 16;
-        const uint32_t one2 = E::pack2(1.0f, 1.0f);
-        for (int v = tid; v < (DMA ? NRING : 2) * PADV; v += NT)
-            *reinterpret_cast<uint4*>(smem + (v / PADV) * BUFB + D * (DMA ? VSTR_D : VSTR) + (v % PADV) * 16) = make_uint4(one2, one2, one2, one2);
-    }
+    // V^T row 40 (all ones) of every buffer
+    attn_const_row<DMA ? NRING : 2, BUFB, D * (DMA ? VSTR_D : VSTR), DMA ? VSTR_D : VSTR, NT>(smem, tid, E::pack2(1.0f, 1.0f));
 
-    // Q fragments (B operand of S^T = K Q^T): lane = query column, 8 head-dim values per fragment
+    // Q fragments (B operand of S^T = K Q^T): lane = query column, 8 head-dim values per fragment (inline as in attention.hip: 32,640 .. 97,866 lines differ)
     uint4 qf[2][NKT];
 #pragma unroll
     for (int qb = 0; qb < 2; ++qb) {
@@ -328,7 +336,7 @@ __device__ __attribute__((always_inline)) bool attn40_body(const AttnParams& p) 
     const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
     const f32x16 zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
 
-    unsigned long long tm_slots = 0, tm_check = 0, tm_sync = 0, tm_loop = 0, tm_steps = 0;      // VAR & 4096 only
+    unsigned long long tm_slots = 0, tm_check = 0, tm_sync = 0, tm_loop = 0, tm_steps = 0;      // VAR & V_CYCLES only
     bool bad = false;               // UNCHK: a softmax denominator of this lane is not finite
     for (int ph = 0; ph < nph; ++ph) {
         f32x16 o[2][2];
@@ -344,6 +352,7 @@ __device__ __attribute__((always_inline)) bool attn40_body(const AttnParams& p) 
                 ot[qb][0] = zero4; ot[qb][1] = zero4;
             }
         };
+        // operands of this phase (inline as in attention.hip: through a shared helper 366 lines of this file's assembly differ)
         const int L = ph ? p.L2 : p.L1;
         const int LP = ph ? p.L2P : p.L1P;
         const int kvb = ph ? (b / p.kv2_bdiv) : (b / p.kv1_bdiv);
@@ -392,14 +401,12 @@ __device__ __attribute__((always_inline)) bool attn40_body(const AttnParams& p) 
             if (qi >= 11) {
                 dsrc[i] = 0; dneg[i] = true;
             } else if (qi < 6) {
-                const int sl = 64 * qi + lane, r = sl / 6, cs = sl % 6, c = (cs + 6 - 3 * ((r >> 3) & 1)) % 6;
-                dsrc[i] = (32 + r) * (DPK * 2) + c * 16;
+                int r;
+                dsrc[i] = k_piece_src(64 * qi + lane, r);
                 dneg[i] = r < 32;                                // unit -1: rows 64 u + 32 + r = r - 32
             } else {
-                const int sl = 64 * (qi - 6) + lane, dd = sl >> 3, rt = dd - 32;
-                const int sw = (TAIL && dd >= 32) ? (((rt >> 1) & 7) ^ ((rt >= 4 && rt < 12) ? 2 : 0)) : ((dd >> 1) & 7);
-                const int ch = (sl & 7) ^ sw;
-                dsrc[i] = (dd * LP + ch * 8 - 32) * 2;
+                int ch;
+                dsrc[i] = v_piece_src<TAIL>(64 * (qi - 6) + lane, LP, ch);
                 dneg[i] = ch < 4;                                // unit 0: columns ch * 8 - 32 .. < 0
             }
         }
@@ -415,15 +422,9 @@ __device__ __attribute__((always_inline)) bool attn40_body(const AttnParams& p) 
             for (int i = 0; i < NPIECE; ++i) {
                 const int qi = min(wv + NW * i, 10);
                 const bool isk = qi < 6;
-                int src;
-                if (isk) {
-                    const int sl = 64 * qi + lane, r = sl / 6, cs = sl % 6, c = (cs + 6 - 3 * ((r >> 3) & 1)) % 6;
-                    src = (32 + r) * (DPK * 2) + c * 16;
-                } else {
-                    const int sl = 64 * (qi - 6) + lane, dd = sl >> 3, rt = dd - 32;
-                    const int sw = (dd >= 32) ? (((rt >> 1) & 7) ^ ((rt >= 4 && rt < 12) ? 2 : 0)) : ((dd >> 1) & 7);
-                    src = (dd * LP + ((sl & 7) ^ sw) * 8 - 32) * 2;
-                }
+                int src, rc;                                                 // (rc: row / chunk, not needed here; STAT implies TAIL)
+                if (isk) src = k_piece_src(64 * qi + lane, rc);
+                else src = v_piece_src<true>(64 * (qi - 6) + lane, LP, rc);
                 sstr[i] = isk ? (uint32_t)(KT * DPK * 2) : (uint32_t)(KT * 2);
                 scur[i] = (uint32_t)src + 2u * sstr[i];                      // the loop's first staged unit is unit 2
                 sdst[i] = smem_base + (uint32_t)(isk ? VBYTES_D + 1024 * qi : 1024 * (qi - 6));
@@ -448,7 +449,7 @@ __device__ __attribute__((always_inline)) bool attn40_body(const AttnParams& p) 
                 const uint32_t off = bad ? OOB : (uint32_t)(dsrc[i] + u * (isk ? KT * DPK * 2 : KT * 2));
                 const uint32_t dst = none ? smem_base + NRING * BUF_D + PARKB
                                           : smem_base + bufi * BUF_D + (isk ? VBYTES_D + 1024 * qi : 1024 * (qi - 6));
-                if ((VAR & 65536) && u >= 2) dma16_nonop(isk ? ds_k : ds_v, dst, off);      // (loop pieces: SGPR operands are loop-carried SALU values)
+                if ((VAR & V_DMA_NONOP) && u >= 2) dma16_nonop(isk ? ds_k : ds_v, dst, off);      // (loop pieces: SGPR operands are loop-carried SALU values)
                 else dma16(isk ? ds_k : ds_v, dst, off);
             }
         };
@@ -464,13 +465,13 @@ __device__ __attribute__((always_inline)) bool attn40_body(const AttnParams& p) 
 
         // ---- one 32-key step: S_n = QK^T(block j+1), O += V^T P^T(block j-1), P_c = exp2(S_c) (block j) ----
         // 14 MFMAs (fragment f = 0..2: K chunks -> S_n, f = 3..6: V^T (dt, g) -> O; two query blocks each), 16 "pairs" of
-        // scores (2 exp2 + 1 pack each) and 8 packed max3.  VAR & 1: the interleave is written out slot by slot -- MFMA i,
+        // scores (2 exp2 + 1 pack each) and 8 packed max3.  VAR & V_PINNED: the interleave is written out slot by slot -- MFMA i,
         // then the exp2 of pair i+1, the pack of pair i and every other slot a max3 -- and pinned with sched_barrier, with
         // the LDS fragment reads issued two fragments (four MFMAs) ahead.  Otherwise the three streams are emitted one
         // after the other and hipcc's scheduler decides.
         // TAIL schedule: fragment reads run PD fragments (2 PD MFMA slots) ahead of their use, ring of PD + 1 registers
-        // (VAR & 131072: PD = 3, VAR & 262144: PD = 4; default 2)
-        constexpr int PD = (VAR & 262144) ? 4 : (VAR & 131072) ? 3 : 2;
+        // (VAR & V_PD3: PD = 3, VAR & V_PD4: PD = 4; default 2)
+        constexpr int PD = (VAR & V_PD4) ? 4 : (VAR & V_PD3) ? 3 : 2;
         constexpr int NFR = TAIL ? PD + 1 : 3;
         uint4 fr[NFR];               // LDS fragment ring: fragment f of a step lives in fr[(R0 + f) % 3]  (TAIL: (R0T + f) % (PD + 1))
         auto step = [&](const char* Vs, auto second_c, int j, f32x16 (&sc)[2], f32x16 (&sn)[2], uint4 (&pc)[2][2],
@@ -482,7 +483,7 @@ __device__ __attribute__((always_inline)) bool attn40_body(const AttnParams& p) 
             constexpr int KB = SECOND ? 1 : 0, G0 = SECOND ? 2 : 0, R0 = SECOND ? 1 : 0;
             const char* Ks = Vs + VBY;
             auto frag = [&](int f, int kb, int g0) -> uint4 {
-                if ((VAR & 256) && f > 0) f = 0;
+                if ((VAR & V_ONE_FRAG) && f > 0) f = 0;
                 if (DMA)
                     return f < 3 ? *reinterpret_cast<const uint4*>(Ks + kb * 32 * KSTR_D + kfd[f])
                                  : *reinterpret_cast<const uint4*>(Vs + ((f - 3) >> 1) * 32 * VSTR_D + vfd[g0 + ((f - 3) & 1)]);
@@ -491,12 +492,12 @@ __device__ __attribute__((always_inline)) bool attn40_body(const AttnParams& p) 
             };
             auto mma = [&](int i, const uint4& fa) {
                 const int f = i >> 1, qb = i & 1;
-                if (f < 3) { if (!(VAR & 64) || f == 0) sn[qb] = E::mfma(fa, qf[qb][f], f == 0 ? zero16 : sn[qb]); }
-                else if (!(VAR & 32)) o[qb][(f - 3) >> 1] = E::mfma(fa, pp[qb][(f - 3) & 1], o[qb][(f - 3) >> 1]);
+                if (f < 3) { if (!(VAR & V_NO_QK) || f == 0) sn[qb] = E::mfma(fa, qf[qb][f], f == 0 ? zero16 : sn[qb]); }
+                else if (!(VAR & V_NO_PV)) o[qb][(f - 3) >> 1] = E::mfma(fa, pp[qb][(f - 3) & 1], o[qb][(f - 3) >> 1]);
             };
             auto exp_pair = [&](int pr) {
                 const int qb = pr >> 3, r0 = 2 * (pr & 7);
-                if (VAR & 4) return;
+                if (VAR & V_NO_EXP) return;
                 sc[qb][r0] = __builtin_amdgcn_exp2f(sc[qb][r0]);
                 sc[qb][r0 + 1] = __builtin_amdgcn_exp2f(sc[qb][r0 + 1]);
             };
@@ -515,7 +516,7 @@ __device__ __attribute__((always_inline)) bool attn40_body(const AttnParams& p) 
                 // 10..13 the four 16x16x32 tail MFMAs (query block, 16-query half) on P swapped in place during slots 4..11.
                 auto fragT = [&](int sq, int sec) -> uint4 {
                     const int g0 = sec ? 2 : 0;
-                    if ((VAR & 256) && sq > 0) sq = 0;
+                    if ((VAR & V_ONE_FRAG) && sq > 0) sq = 0;
                     if (sq < 2) return DMA ? *reinterpret_cast<const uint4*>(Vs + vfd[g0 + sq])
                                            : *reinterpret_cast<const uint4*>(Vs + vfrag + (g0 + sq) * 32);
                     if (sq < 5) return DMA ? *reinterpret_cast<const uint4*>(Ks + sec * 32 * KSTR_D + kfd[sq - 2])
@@ -558,7 +559,7 @@ __device__ __attribute__((always_inline)) bool attn40_body(const AttnParams& p) 
                     if (STAT) __builtin_amdgcn_sched_barrier(0);
                     cvt_pair(i);
                     if (STAT) __builtin_amdgcn_sched_barrier(0);
-                    if ((i & 1) && !(VAR & 2048) && CHK) mq[0] = pk_max3(mq[0], word(i - 1), word(i));
+                    if ((i & 1) && !(VAR & V_NO_MAX) && CHK) mq[0] = pk_max3(mq[0], word(i - 1), word(i));
                     if (i >= 4 && i < 12) swapT(i - 4);
                     if (STAT) { __builtin_amdgcn_sched_barrier(0); mmaT(i); }
                     __builtin_amdgcn_sched_barrier(0);
@@ -566,8 +567,8 @@ __device__ __attribute__((always_inline)) bool attn40_body(const AttnParams& p) 
                 exp_pair(15);
                 cvt_pair(14);
                 cvt_pair(15);
-                if (!(VAR & 2048) && CHK) mq[0] = pk_max3(mq[0], word(14), word(15));
-            } else if (VAR & 1) {
+                if (!(VAR & V_NO_MAX) && CHK) mq[0] = pk_max3(mq[0], word(14), word(15));
+            } else if (VAR & V_PINNED) {
                 if (!SECOND) {       // (the second step's first two fragments were read during the first step's last slots)
                     fr[0] = frag(0, KB, G0);
                     fr[1] = frag(1, KB, G0);
@@ -584,13 +585,13 @@ __device__ __attribute__((always_inline)) bool attn40_body(const AttnParams& p) 
                     mma(i, fr[(R0 + (i >> 1)) % 3]);
                     exp_pair(i + 1);
                     cvt_pair(i);
-                    if ((i & 1) && !(VAR & 2048)) mq[0] = pk_max3(mq[0], word(i - 1), word(i));
+                    if ((i & 1) && !(VAR & V_NO_MAX)) mq[0] = pk_max3(mq[0], word(i - 1), word(i));
                     __builtin_amdgcn_sched_barrier(0);
                 }
                 exp_pair(15);
                 cvt_pair(14);
                 cvt_pair(15);
-                if (!(VAR & 2048)) mq[0] = pk_max3(mq[0], word(14), word(15));
+                if (!(VAR & V_NO_MAX)) mq[0] = pk_max3(mq[0], word(14), word(15));
             } else {
 #pragma unroll
                 for (int i = 0; i < 14; ++i) mma(i, frag(i >> 1, KB, G0));
@@ -672,7 +673,7 @@ __device__ __attribute__((always_inline)) bool attn40_body(const AttnParams& p) 
                 }
             }
             }       // CHK
-            if (VAR & 4096) tm_steps += 1;
+            if (VAR & V_CYCLES) tm_steps += 1;
         };
 
         {
@@ -709,11 +710,11 @@ __device__ __attribute__((always_inline)) bool attn40_body(const AttnParams& p) 
         const int NUF = DMA ? (J >> 1) : NU;
         auto iteration_sync = [&]() __attribute__((always_inline)) {
             if (DMA) { if (NPIECE == 3) dma_wait_keep_n<3>(); else dma_wait_keep_n<2>(); }   // this wave's pieces of unit u + 1 have landed (u + 2 stays in flight) ...
-            if (!(VAR & 8)) __syncthreads();                        // ... and so have everybody else's
+            if (!(VAR & V_NO_BARRIER)) __syncthreads();                        // ... and so have everybody else's
         };
         int ring = 0;                                               // u % NRING
         unsigned long long t_loop0 = 0;
-        if (VAR & 4096) t_loop0 = __builtin_amdgcn_s_memtime();
+        if (VAR & V_CYCLES) t_loop0 = __builtin_amdgcn_s_memtime();
         if (STAT && !(UNCHK && checked_run)) {
             auto body = [&](auto slot_c, int u, auto chk_c) __attribute__((always_inline)) {      // iteration u on ring slot u % 3 = slot_c (compile-time)
                 constexpr int SLOT = decltype(slot_c)::value;
@@ -747,19 +748,19 @@ __device__ __attribute__((always_inline)) bool attn40_body(const AttnParams& p) 
         } else
         for (int u = 0; u < NUF; ++u) {
             if (DMA) {
-                if (!(VAR & 16)) dma_unit(u + 2, ring == 0 ? 2 : ring - 1);      // buffer (u+2) % 3 was last read in iteration u-1
-            } else if (!(VAR & 16)) load_unit(u + 1);
+                if (!(VAR & V_NO_STAGING)) dma_unit(u + 2, ring == 0 ? 2 : ring - 1);      // buffer (u+2) % 3 was last read in iteration u-1
+            } else if (!(VAR & V_NO_STAGING)) load_unit(u + 1);
             const char* Vs = smem + (DMA ? ring : (u & 1)) * BUFB;
             ring = ring == NRING - 1 ? 0 : ring + 1;
             step(Vs, std::false_type{}, 2 * u, sa, sb, pa, pb, std::true_type{});
             step(Vs, std::true_type{}, 2 * u + 1, sb, sa, pb, pa, std::true_type{});
-            if (!DMA && !(VAR & 16)) store_unit((u + 1) & 1);
+            if (!DMA && !(VAR & V_NO_STAGING)) store_unit((u + 1) & 1);
             unsigned long long t_s = 0;
-            if (VAR & 4096) t_s = __builtin_amdgcn_s_memtime();
+            if (VAR & V_CYCLES) t_s = __builtin_amdgcn_s_memtime();
             iteration_sync();
-            if (VAR & 4096) tm_sync += __builtin_amdgcn_s_memtime() - t_s;
+            if (VAR & V_CYCLES) tm_sync += __builtin_amdgcn_s_memtime() - t_s;
         }
-        if (VAR & 4096) tm_loop += __builtin_amdgcn_s_memtime() - t_loop0;
+        if (VAR & V_CYCLES) tm_loop += __builtin_amdgcn_s_memtime() - t_loop0;
         if (DMA) {
             const char* Vs = smem + ring * BUFB;                     // unit NUF
             auto drain = [&](int g0, uint4 (&pp)[2][2]) {      // O += V^T P^T of the last block; nothing left to score
@@ -929,7 +930,7 @@ __device__ __attribute__((always_inline)) bool attn40_body(const AttnParams& p) 
                     *reinterpret_cast<uint2*>(park + (qb * 5 + jj) / 2 * 1024 + ((qb * 5 + jj) & 1) * 8) = make_uint2(pk[2 * jj], pk[2 * jj + 1]);
             } else {
                 const int q = q0 + qb * 32 + col;
-                if (q < p.N && !(VAR & 4096)) {
+                if (q < p.N && !(VAR & V_CYCLES)) {
                     bf16_t* orow = p.out + ((size_t)b * p.N + q) * p.out_ld + h * D;
 #pragma unroll
                     for (int jj = 0; jj < 5; ++jj)
@@ -953,7 +954,7 @@ __device__ __attribute__((always_inline)) bool attn40_body(const AttnParams& p) 
 #endif
         }
     }
-    if ((VAR & 4096) && lane == 0) {       // (the kernel's real output is garbage in this variant: the counters overwrite its head)
+    if ((VAR & V_CYCLES) && lane == 0) {       // (the kernel's real output is garbage in this variant: the counters overwrite its head)
         unsigned long long* dbg = reinterpret_cast<unsigned long long*>(p.out);
         atomicAdd(dbg + 0, tm_loop); atomicAdd(dbg + 1, tm_slots); atomicAdd(dbg + 2, tm_check); atomicAdd(dbg + 3, tm_sync);
         atomicAdd(dbg + 4, tm_steps); atomicAdd(dbg + 5, 1ull);
@@ -968,9 +969,9 @@ __device__ __attribute__((always_inline)) bool attn40_body(const AttnParams& p) 
 // overwrites its output (exact, slow, never seen on real data).  The two runs share nothing but the kernel arguments, so the cold
 // checked body costs the hot one no registers (a retry loop around the phase did: 244 SGPR + 63 VGPR spills, +6 % time).
 template <bool F16, int THR, int VAR>
-__global__ __launch_bounds__((VAR & 32768) ? 512 : 256, 2) void attn40_kernel(const AttnParams p) {
-    if constexpr ((VAR & 4194304) != 0) {
-        if (attn40_body<F16, THR, VAR>(p)) attn40_body<F16, THR, VAR & ~4194304>(p);
+__global__ __launch_bounds__(Var40<VAR>::NT, 2) void attn40_kernel(const AttnParams p) {
+    if constexpr (Var40<VAR>::UNCHK) {
+        if (attn40_body<F16, THR, VAR>(p)) attn40_body<F16, THR, VAR & ~V_UNCHECKED>(p);
     } else {
         attn40_body<F16, THR, VAR>(p);
     }
@@ -979,110 +980,94 @@ __global__ __launch_bounds__((VAR & 32768) ? 512 : 256, 2) void attn40_kernel(co
 template <bool F16, int THR, int VAR>
 int launch_attn40(const AttnParams& p, hipStream_t s) {
     auto kern = attn40_kernel<F16, THR, VAR>;
-    constexpr int NW = (VAR & 32768) ? 8 : 4;
-    constexpr int PARKB = NW * ((VAR & 8192) ? PARK_T : PARK) / 4;
-    constexpr int LDS_BYTES = (VAR & 512) ? 100 * 1024 : (VAR & 128) ? NRING * BUF_D + PARKB + 1024 : 2 * BUF + PARKB;
-    static_assert(!(VAR & 1048576) || LDS_BYTES >= PJ_LDS, "the out-projection's chunk buffers must fit the loop's LDS");
+    constexpr int NW = Var40<VAR>::NW, LDS_BYTES = Var40<VAR>::LDS_BYTES;
+    static_assert(!Var40<VAR>::PROJ || LDS_BYTES >= PJ_LDS, "the out-projection's chunk buffers must fit the loop's LDS");
     if (int rc_attr = imd_lds_attr(reinterpret_cast<const void*>(kern), LDS_BYTES, "attention(d=40)")) return rc_attr;
     dim3 grid((p.N + NW * 64 - 1) / (NW * 64), p.H, p.B);
     hipLaunchKernelGGL(kern, grid, dim3(NW * 64), LDS_BYTES, s, p);
     return imd_check_launch("attention(d=40)");
 }
 
+// The dispatcher's one step from a variant word to a launch: picks the element type.  With DMA_BITS the variant is staged by LDS-DMA (VAR | DMA_BITS) when
+// the caller guarantees that K's pad column holds 1.0 (imd_attn_params.k_pad_one), through registers (VAR) otherwise.  (The dispatcher names its kernels,
+// all through here or launch40_bf16, in the order the file always had them: that order is the order of the kernels in the object.)
+template <int THR, int VAR, int DMA_BITS = 0>
+int launch40(const AttnParams& p, hipStream_t s) {
+    const bool h = p.dtype == IMD_DTYPE_F16;
+    if constexpr (DMA_BITS != 0) {
+        if (p.k_pad_one) return h ? launch_attn40<true, THR, VAR | DMA_BITS>(p, s) : launch_attn40<false, THR, VAR | DMA_BITS>(p, s);
+    }
+    return h ? launch_attn40<true, THR, VAR>(p, s) : launch_attn40<false, THR, VAR>(p, s);
+}
+template <int VAR> int launch40_bf16(const AttnParams& p, hipStream_t s) { return launch_attn40<false, 8, VAR>(p, s); }      // timing ablations: bf16 only
+
+constexpr int V_R2 = V_PINNED;                              // the round-2 kernel (P.V as two 32x32x16 row blocks), register staging
+constexpr int V_R3 = V_PINNED | V_TAIL;                     // the round-3 kernel (16x16x32 tail), register staging
+constexpr int V_R4 = V_R3 | V_DMA | V_STATIC_RING;          // the round-4 kernel: LDS-DMA staging, main loop unrolled over the three ring slots
+
 }  // namespace
 
-// variant: 10 (default) = software-pipelined kernel, pinned MFMA / VALU interleave, head-dim rows 32..40 of P.V on
-//          v_mfma_f32_16x16x32 (VAR & 8192), K / V^T staged by LDS-DMA when the caller guarantees K's pad column
-//          (imd_attn_params.k_pad_one), through registers otherwise;
-//          9 = round-2 default (P.V as two 32x32x16 row blocks), same staging rule;  7 = 9 with register staging always;
-//          6 = 7 with the compiler's own interleave;  8 = 7 with the deferred-maximum bound 2^12 instead of 2^8
-//          20..49 (only when built with -DIMD_ABLATIONS): timing ablations with WRONG results (tools/attn_bench.py);
-//          50..54 (same builds): correct variants measured no faster -- 8-wave workgroups, DMA pieces without their leading wait
-//          states, LDS fragment reads 3 / 4 fragments ahead
+// variant = tuning knob 0; the list of what each number means is above g_attn_qw40 in attention.hip.  Here: V_R2 / V_R3 / V_R4 are the kernels of rounds
+// 2 / 3 / 4; a third argument of launch40 is what k_pad_one adds; 13 and 12 fall through to the kernel of 10 when k_pad_one or proj_w rule them out;
+// 20..48 (only when built with -DIMD_ABLATIONS) are timing ablations with WRONG results (tools/attn_bench.py), 50..54 correct but no faster.
 int imd_launch_attention_d40(const AttnParams& p, int variant, hipStream_t s) {
-    const bool h = p.dtype == IMD_DTYPE_F16;
     switch (variant) {
-        case 6: return h ? launch_attn40<true, 8, 0>(p, s) : launch_attn40<false, 8, 0>(p, s);
-        case 8: return h ? launch_attn40<true, 12, 1>(p, s) : launch_attn40<false, 12, 1>(p, s);
-        case 9:             // LDS-DMA staging: needs the caller's guarantee that K's pad column holds 1.0
-            if (p.k_pad_one) return h ? launch_attn40<true, 8, 1 | 128>(p, s) : launch_attn40<false, 8, 1 | 128>(p, s);
-            return h ? launch_attn40<true, 8, 1>(p, s) : launch_attn40<false, 8, 1>(p, s);
-        case 7: return h ? launch_attn40<true, 8, 1>(p, s) : launch_attn40<false, 8, 1>(p, s);
-        case 11:            // the 16x16x32 tail with register staging always
-            return h ? launch_attn40<true, 8, 1 | 8192>(p, s) : launch_attn40<false, 8, 1 | 8192>(p, s);
+        case 6: return launch40<8, 0>(p, s);
+        case 8: return launch40<12, V_R2>(p, s);
+        case 9: return launch40<8, V_R2, V_DMA>(p, s);
+        case 7: return launch40<8, V_R2>(p, s);
+        case 11: return launch40<8, V_R3>(p, s);
 #ifdef IMD_ABLATIONS
         // timing ablations of variant 7 (WRONG results; tools/attn_bench.py --variants ...)
-        case 20: return launch_attn40<false, 8, 1 | 4>(p, s);         // no exp2
-        case 21: return launch_attn40<false, 8, 1 | 8>(p, s);         // no loop barrier
-        case 22: return launch_attn40<false, 8, 1 | 16>(p, s);        // no loads / LDS stores in the loop
-        case 23: return launch_attn40<false, 8, 1 | 32>(p, s);        // no P.V MFMAs
-        case 24: return launch_attn40<false, 8, 1 | 64>(p, s);        // 2 of 6 QK^T MFMAs
-        case 25: return launch_attn40<false, 8, 1 | 8 | 16>(p, s);    // no barrier, no staging
-        case 26: return launch_attn40<false, 8, 1 | 256>(p, s);       // one LDS fragment read per step
-        case 27: return launch_attn40<false, 8, 1 | 512>(p, s);       // one workgroup per CU
-        case 28: return launch_attn40<false, 8, 1 | 4 | 16 | 256>(p, s);   // MFMAs + pack only
-        case 29: return launch_attn40<false, 8, 1 | 32 | 64 | 16>(p, s);   // 2 MFMAs per step, everything else
-        case 30: return launch_attn40<false, 8, 1 | 128 | 2048>(p, s);     // LDS-DMA variant without the packed-max / overflow test
-        case 31: return launch_attn40<false, 8, 1 | 128 | 4096>(p, s);     // cycle counters (tools/attn_bench.py --cycles)
-        case 32: return launch_attn40<false, 8, 1 | 128 | 4096 | 512>(p, s);   // ... with one workgroup per CU
+        case 20: return launch40_bf16<V_R2 | V_NO_EXP>(p, s);
+        case 21: return launch40_bf16<V_R2 | V_NO_BARRIER>(p, s);
+        case 22: return launch40_bf16<V_R2 | V_NO_STAGING>(p, s);
+        case 23: return launch40_bf16<V_R2 | V_NO_PV>(p, s);
+        case 24: return launch40_bf16<V_R2 | V_NO_QK>(p, s);
+        case 25: return launch40_bf16<V_R2 | V_NO_BARRIER | V_NO_STAGING>(p, s);
+        case 26: return launch40_bf16<V_R2 | V_ONE_FRAG>(p, s);
+        case 27: return launch40_bf16<V_R2 | V_LDS_100K>(p, s);
+        case 28: return launch40_bf16<V_R2 | V_NO_EXP | V_NO_STAGING | V_ONE_FRAG>(p, s);      // MFMAs + pack only
+        case 29: return launch40_bf16<V_R2 | V_NO_PV | V_NO_QK | V_NO_STAGING>(p, s);          // 2 MFMAs per step, everything else
+        case 30: return launch40_bf16<V_R2 | V_DMA | V_NO_MAX>(p, s);
+        case 31: return launch40_bf16<V_R2 | V_DMA | V_CYCLES>(p, s);                          // tools/attn_bench.py --cycles
+        case 32: return launch40_bf16<V_R2 | V_DMA | V_CYCLES | V_LDS_100K>(p, s);
         // one workgroup per CU (a lone wave per SIMD): what is that wave's step made of
-        case 33: return launch_attn40<false, 8, 1 | 128 | 512>(p, s);
-        case 34: return launch_attn40<false, 8, 1 | 128 | 512 | 4>(p, s);              // no exp2
-        case 35: return launch_attn40<false, 8, 1 | 128 | 512 | 16>(p, s);             // no staging
-        case 36: return launch_attn40<false, 8, 1 | 128 | 512 | 32>(p, s);             // no P.V MFMAs
-        case 37: return launch_attn40<false, 8, 1 | 128 | 512 | 32 | 64>(p, s);        // 2 MFMAs per step
-        case 38: return launch_attn40<false, 8, 1 | 128 | 512 | 4 | 16 | 2048>(p, s);  // MFMAs, packs and fragment reads only
-        case 39: return launch_attn40<false, 8, 1 | 128 | 512 | 8>(p, s);              // no barrier
-        // ablations of the default kernel (variant 10: 16x16x32 tail + LDS-DMA staging)
-        case 40: return launch_attn40<false, 8, 1 | 128 | 8192 | 2048>(p, s);          // no packed-max / overflow test
-        case 41: return launch_attn40<false, 8, 1 | 128 | 8192 | 8>(p, s);             // no loop barrier
-        case 42: return launch_attn40<false, 8, 1 | 128 | 8192 | 16>(p, s);            // no staging in the loop
-        case 43: return launch_attn40<false, 8, 1 | 128 | 8192 | 4>(p, s);             // exp2 -> move
-        case 44: return launch_attn40<false, 8, 1 | 128 | 8192 | 256>(p, s);           // one LDS fragment read per step
-        case 45: return launch_attn40<false, 8, 1 | 128 | 8192 | 8 | 16>(p, s);        // no barrier, no staging
-        case 46: return launch_attn40<false, 8, 1 | 128 | 8192 | 8 | 16 | 2048>(p, s); // ... and no overflow test
-        case 47: return launch_attn40<false, 8, 1 | 128 | 8192 | 8 | 16 | 2048 | 256>(p, s);   // ... and one fragment read
-        case 48: return launch_attn40<false, 8, 1 | 128 | 8192 | 512>(p, s);           // one workgroup per CU
+        case 33: return launch40_bf16<V_R2 | V_DMA | V_LDS_100K>(p, s);
+        case 34: return launch40_bf16<V_R2 | V_DMA | V_LDS_100K | V_NO_EXP>(p, s);
+        case 35: return launch40_bf16<V_R2 | V_DMA | V_LDS_100K | V_NO_STAGING>(p, s);
+        case 36: return launch40_bf16<V_R2 | V_DMA | V_LDS_100K | V_NO_PV>(p, s);
+        case 37: return launch40_bf16<V_R2 | V_DMA | V_LDS_100K | V_NO_PV | V_NO_QK>(p, s);    // 2 MFMAs per step
+        case 38: return launch40_bf16<V_R2 | V_DMA | V_LDS_100K | V_NO_EXP | V_NO_STAGING | V_NO_MAX>(p, s);      // MFMAs, packs and fragment reads only
+        case 39: return launch40_bf16<V_R2 | V_DMA | V_LDS_100K | V_NO_BARRIER>(p, s);
+        // ablations of variant 10 (16x16x32 tail + LDS-DMA staging)
+        case 40: return launch40_bf16<V_R3 | V_DMA | V_NO_MAX>(p, s);
+        case 41: return launch40_bf16<V_R3 | V_DMA | V_NO_BARRIER>(p, s);
+        case 42: return launch40_bf16<V_R3 | V_DMA | V_NO_STAGING>(p, s);
+        case 43: return launch40_bf16<V_R3 | V_DMA | V_NO_EXP>(p, s);
+        case 44: return launch40_bf16<V_R3 | V_DMA | V_ONE_FRAG>(p, s);
+        case 45: return launch40_bf16<V_R3 | V_DMA | V_NO_BARRIER | V_NO_STAGING>(p, s);
+        case 46: return launch40_bf16<V_R3 | V_DMA | V_NO_BARRIER | V_NO_STAGING | V_NO_MAX>(p, s);
+        case 47: return launch40_bf16<V_R3 | V_DMA | V_NO_BARRIER | V_NO_STAGING | V_NO_MAX | V_ONE_FRAG>(p, s);
+        case 48: return launch40_bf16<V_R3 | V_DMA | V_LDS_100K>(p, s);
         // round-3 variants that compute CORRECT results and measured no faster than 10 (profiles/r3c_*, r3d_*): the kernel is power-capped
-        case 50:            // 10 with 8-wave (512-query) workgroups
-            if (p.k_pad_one) return h ? launch_attn40<true, 8, 1 | 128 | 8192 | 32768>(p, s) : launch_attn40<false, 8, 1 | 128 | 8192 | 32768>(p, s);
-            return h ? launch_attn40<true, 8, 1 | 8192>(p, s) : launch_attn40<false, 8, 1 | 8192>(p, s);
-        case 51:            // 50 without the five leading wait states of the loop's DMA pieces
-            if (p.k_pad_one) return h ? launch_attn40<true, 8, 1 | 128 | 8192 | 32768 | 65536>(p, s) : launch_attn40<false, 8, 1 | 128 | 8192 | 32768 | 65536>(p, s);
-            return h ? launch_attn40<true, 8, 1 | 8192>(p, s) : launch_attn40<false, 8, 1 | 8192>(p, s);
-        case 52:            // 10 without them
-            if (p.k_pad_one) return h ? launch_attn40<true, 8, 1 | 128 | 8192 | 65536>(p, s) : launch_attn40<false, 8, 1 | 128 | 8192 | 65536>(p, s);
-            return h ? launch_attn40<true, 8, 1 | 8192>(p, s) : launch_attn40<false, 8, 1 | 8192>(p, s);
-        case 53:            // 10 with fragment reads three fragments ahead
-            if (p.k_pad_one) return h ? launch_attn40<true, 8, 1 | 128 | 8192 | 131072>(p, s) : launch_attn40<false, 8, 1 | 128 | 8192 | 131072>(p, s);
-            return h ? launch_attn40<true, 8, 1 | 8192>(p, s) : launch_attn40<false, 8, 1 | 8192>(p, s);
-        case 54:            // ... four fragments ahead
-            if (p.k_pad_one) return h ? launch_attn40<true, 8, 1 | 128 | 8192 | 262144>(p, s) : launch_attn40<false, 8, 1 | 128 | 8192 | 262144>(p, s);
-            return h ? launch_attn40<true, 8, 1 | 8192>(p, s) : launch_attn40<false, 8, 1 | 8192>(p, s);
+        case 50: return launch40<8, V_R3, V_DMA | V_WAVES8>(p, s);
+        case 51: return launch40<8, V_R3, V_DMA | V_WAVES8 | V_DMA_NONOP>(p, s);
+        case 52: return launch40<8, V_R3, V_DMA | V_DMA_NONOP>(p, s);
+        case 53: return launch40<8, V_R3, V_DMA | V_PD3>(p, s);
+        case 54: return launch40<8, V_R3, V_DMA | V_PD4>(p, s);
 #endif
-        case 10:            // the round-3 default: one loop body, ring slot and staging bookkeeping at run time
-            if (p.proj_w == nullptr) {
-                if (p.k_pad_one) return h ? launch_attn40<true, 8, 1 | 128 | 8192>(p, s) : launch_attn40<false, 8, 1 | 128 | 8192>(p, s);
-                return h ? launch_attn40<true, 8, 1 | 8192>(p, s) : launch_attn40<false, 8, 1 | 8192>(p, s);
-            }
+        case 10:
+            if (p.proj_w == nullptr) return launch40<8, V_R3, V_DMA>(p, s);
             [[fallthrough]];
-        case 13:            // round 4 (default): 12 without the per-step overflow test on interior steps; fp16 (round 5) with the reference maximum biased by 2^4 (FIRST_BIAS)
-            if (p.out_dup != nullptr)       // (validated by imd_launch_attention: k_pad_one, no fused out-projection)
-                return h ? launch_attn40<true, 8, 1 | 128 | 8192 | 2097152 | 4194304 | 8388608>(p, s) : launch_attn40<false, 8, 1 | 128 | 8192 | 2097152 | 4194304 | 8388608>(p, s);
-            if (p.proj_w == nullptr && p.k_pad_one)
-                return h ? launch_attn40<true, 8, 1 | 128 | 8192 | 2097152 | 4194304>(p, s) : launch_attn40<false, 8, 1 | 128 | 8192 | 2097152 | 4194304>(p, s);
+        case 13:
+            if (p.out_dup != nullptr) return launch40<8, V_R4 | V_UNCHECKED | V_DUP>(p, s);      // (validated by imd_launch_attention: k_pad_one, no fused out-projection)
+            if (p.proj_w == nullptr && p.k_pad_one) return launch40<8, V_R4 | V_UNCHECKED>(p, s);
             [[fallthrough]];
-        case 12:            // round 4: the LDS-DMA kernel with the main loop unrolled over the three ring slots -- compile-time LDS
-        default:            // addresses, three-instruction staging pieces, no first / ragged-block test on interior steps
-            if (p.out_dup != nullptr)
-                return h ? launch_attn40<true, 8, 1 | 128 | 8192 | 2097152 | 8388608>(p, s) : launch_attn40<false, 8, 1 | 128 | 8192 | 2097152 | 8388608>(p, s);
-            if (p.proj_w == nullptr && p.k_pad_one)
-                return h ? launch_attn40<true, 8, 1 | 128 | 8192 | 2097152>(p, s) : launch_attn40<false, 8, 1 | 128 | 8192 | 2097152>(p, s);
-            if (p.proj_w != nullptr) {      // fused out-projection (validated by imd_launch_attention)
-                if (p.k_pad_one) return h ? launch_attn40<true, 8, 1 | 128 | 8192 | 1048576>(p, s) : launch_attn40<false, 8, 1 | 128 | 8192 | 1048576>(p, s);
-                return h ? launch_attn40<true, 8, 1 | 8192 | 1048576>(p, s) : launch_attn40<false, 8, 1 | 8192 | 1048576>(p, s);
-            }
-            if (p.k_pad_one) return h ? launch_attn40<true, 8, 1 | 128 | 8192>(p, s) : launch_attn40<false, 8, 1 | 128 | 8192>(p, s);
-            return h ? launch_attn40<true, 8, 1 | 8192>(p, s) : launch_attn40<false, 8, 1 | 8192>(p, s);
+        case 12: default:
+            if (p.out_dup != nullptr) return launch40<8, V_R4 | V_DUP>(p, s);
+            if (p.proj_w == nullptr && p.k_pad_one) return launch40<8, V_R4>(p, s);
+            if (p.proj_w != nullptr) return launch40<8, V_R3 | V_PROJ, V_DMA>(p, s);            // fused out-projection (validated by imd_launch_attention)
+            return launch40<8, V_R3, V_DMA>(p, s);
     }
 }

@@ -29,8 +29,7 @@
 // on even steps, P.V of the previous 64-key group, next to the softmax of block j; K / V^T units of 64 keys are staged
 // through registers into a double-buffered LDS tile (80-byte rows: conflict-free 2 x b128 fragment reads), one barrier per
 // unit; the phase-0 result of a two-phase row is parked in LDS.
-#include "common.h"
-#include "imd_kernels.h"
+#include "attn_common.h"
 
 namespace {
 
@@ -42,15 +41,9 @@ constexpr int KBYTES = 64 * RS;              // 5120
 constexpr int BUF = VBYTES + KBYTES;         // 8400
 constexpr int PARK = 4 * 5 * 1024;
 constexpr int LDS_BYTES = 2 * BUF + PARK;
-static_assert((64 - VROWS) * RS <= KBYTES, "phantom V^T rows must stay inside the K rows");
+static_assert(phantom_rows_fit(64, VROWS, RS, KBYTES), "phantom V^T rows must stay inside the K rows");
 
 typedef int v8i_t __attribute__((ext_vector_type(8)));
-typedef __attribute__((__vector_size__(4 * sizeof(uint32_t)))) uint32_t v4u;
-__device__ __forceinline__ uint4 buf_load16(const __amdgpu_buffer_rsrc_t& rs, uint32_t byte_off) {
-    const v4u v = __builtin_amdgcn_raw_buffer_load_b128(rs, (int)byte_off, 0, 0);
-    return make_uint4(v[0], v[1], v[2], v[3]);
-}
-constexpr uint32_t OOB = 0xffffffffu;
 
 __device__ __forceinline__ v8i_t frag32(const char* p) {          // 32 bytes of one LDS row: two conflict-free b128 reads
     const uint4 a = *reinterpret_cast<const uint4*>(p), b = *reinterpret_cast<const uint4*>(p + 16);
@@ -71,24 +64,15 @@ __global__ __launch_bounds__(256, 2) void attn40_fp8_kernel(const AttnParams p, 
     using E = El<F16>;
     constexpr float TARGET = 8.0f;            // the running maximum maps to P = 2^8 ...
     constexpr float THR = 8.25f;              // ... and m_ref moves when a score passes 2^8.25 (e4m3 tops out at 448 = 2^8.8)
-    constexpr int L_REG = 4;                  // accumulator row 40: second row block, register 4, lanes with hi == 0
+    using PS = AttnPad<D>;                    // accumulator row 40 / Q slots 40, 41: where they live (attn_common.h)
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, hi = lane >> 5, col = lane & 31;
     int wx, h, b;
-    {
-        const unsigned gx = gridDim.x, gy = gridDim.y, gz = gridDim.z, total = gx * gy * gz;
-        const unsigned Lb = blockIdx.x + gx * (blockIdx.y + gy * blockIdx.z);
-        const unsigned xcd = Lb & 7u, slot = Lb >> 3, q8 = total >> 3, r8 = total & 7u;
-        unsigned w = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + slot;
-        if (p.flags & 1) w = Lb;
-        wx = (int)(w % gx);
-        b = (int)((w / gx) % gz);
-        h = (int)(w / (gx * gz));
-    }
+    attn_work_item<WORK_KNOB>(p, wx, h, b);                       // XCD-aware work list
     const int q0 = (wx * 4 + wave) * 64;
     const int sa = 127 - ek, sb = 127 - eq;                       // E8M0 bytes: A = K (2^-ek), B = Q (2^-eq)
 
-    {   // V^T row 40 = 2^ev in both buffers, written once
+    {   // V^T row 40 = 2^ev in both buffers, written once (inline: through attn_const_row the file's assembly differs in 46 lines)
         const uint32_t one = f32_to_fp8(__builtin_exp2f((float)ev)) * 0x01010101u;
         for (int v = tid; v < 2 * (RS / 16); v += 256)
             *reinterpret_cast<uint4*>(smem + (v / (RS / 16)) * BUF + D * RS + (v % (RS / 16)) * 16) = make_uint4(one, one, one, one);
@@ -118,9 +102,10 @@ __global__ __launch_bounds__(256, 2) void attn40_fp8_kernel(const AttnParams p, 
         float m_ref[2] = {0.f, 0.f};
 #pragma unroll
         for (int qb = 0; qb < 2; ++qb) {
-            if (hi == 1) qf[qb][2] &= (int)0xffff0000u;           // Q slots 40, 41 (bytes 8, 9 of the upper half) = -m_ref = 0
+            if (hi == PS::QPAD8_HI) qf[qb][PS::QPAD8_W] &= (int)0xffff0000u;      // Q slots 40, 41 (bytes 8, 9 of the upper half) = -m_ref = 0
             o[qb][0] = zero16; o[qb][1] = zero16;
         }
+        // operands of this phase (inline, see attention.hip: through a shared helper 90 lines of this file's assembly differ)
         const int L = ph ? p.L2 : p.L1, LP = ph ? p.L2P : p.L1P;
         const int kvb = ph ? (b / p.kv2_bdiv) : (b / p.kv1_bdiv);
         const unsigned char* kbase = reinterpret_cast<const unsigned char*>(ph ? p.k2 : p.k1) + (size_t)(kvb * p.H + h) * L * 64;
@@ -212,7 +197,7 @@ __global__ __launch_bounds__(256, 2) void attn40_fp8_kernel(const AttnParams p, 
 #pragma unroll
                     for (int r = 0; r < 16; ++r) { sc[qb][r] -= delta; sn[qb][r] -= delta; }
                     m_ref[qb] = nref;
-                    if (hi == 1) qf[qb][2] = (int)(((uint32_t)qf[qb][2] & 0xffff0000u) | bh | (bl << 8));
+                    if (hi == PS::QPAD8_HI) qf[qb][PS::QPAD8_W] = (int)(((uint32_t)qf[qb][PS::QPAD8_W] & 0xffff0000u) | bh | (bl << 8));
                     if (!first && half == 1) {        // the first half of the current group was packed at the old scale
                         // (rare) rescale it through fp32; its bytes are this lane's own
                         const float alpha = __builtin_amdgcn_exp2f(-delta);
@@ -261,9 +246,9 @@ __global__ __launch_bounds__(256, 2) void attn40_fp8_kernel(const AttnParams p, 
 
 #pragma unroll
         for (int qb = 0; qb < 2; ++qb) {
-            const float mine = o[qb][1][L_REG];
+            const float mine = o[qb][PS::L_DT][PS::L_REG];
             const float other = __shfl_xor(mine, 32);
-            const float lt = (hi == 0) ? mine : other;
+            const float lt = (hi == PS::L_HI) ? mine : other;
             const float inv = ((ph == 1) ? w2 : 1.0f) / lt;
             uint32_t pk[10];
 #pragma unroll

@@ -28,9 +28,7 @@
 // One barrier per tile.  Measured on MI355X (fp16, kernel alone, per tile of one workgroup): MFMAs and softmax without staging 2.05 us, staging
 // without compute 1.05 us, this kernel 3.8 us at 4096 keys and 3.05 us at 16384 -- the two do not overlap yet at one wave per SIMD; 705 TFLOP/s
 // at B = 4, N = 16384.
-#include "common.h"
-#include "imd_kernels.h"
-#include "lds_dma.h"
+#include "attn_common.h"
 
 namespace {
 
@@ -46,12 +44,6 @@ constexpr int KOFF = 2 * VBYTES;           // LDS: V^T stages 0 / 1, then a ring
 constexpr int LDS_BYTES = KOFF + 3 * KBYTES;   // 160 KB: all of a CU's LDS
 constexpr int PIECES = KBYTES / 1024 / 4;  // 1 KB LDS-DMA pieces per wave and operand tile (8)
 static_assert(KBYTES == 4 * PIECES * 1024 && VBYTES == 4 * PIECES * 1024, "a tile is a whole number of pieces per wave");
-
-typedef __attribute__((__vector_size__(4 * sizeof(uint32_t)))) uint32_t v4u;
-__device__ __forceinline__ uint4 buf_load16(const __amdgpu_buffer_rsrc_t& rs, uint32_t byte_off) {
-    const v4u v = __builtin_amdgcn_raw_buffer_load_b128(rs, (int)byte_off, 0, 0);
-    return make_uint4(v[0], v[1], v[2], v[3]);
-}
 
 // x * alpha for an accumulator element that LIVES in an AGPR: read, multiply, write back in one statement.  Written out because hipcc, handed
 // `o[dt][r] *= alpha` over the 256-register accumulator, moves the whole accumulator to VGPRs at the top of the tile loop and spills the Q
@@ -74,15 +66,10 @@ __global__ __launch_bounds__(256, 1) void attn_d512_kernel(const AttnParams p) {
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int hi = lane >> 5;
     const int col = lane & 31;
-    // XCD-aware work mapping as in attention.hip: every XCD gets a contiguous slice of the (head, batch, q-tile) list, so the q-tiles that
-    // stream the same K / V^T share one L2
     int wx, h, b;
     {
-        const unsigned gx = gridDim.x, gz = gridDim.z, total = gridDim.x * gridDim.y * gridDim.z;
-        const unsigned L = blockIdx.x + gx * (blockIdx.y + gridDim.y * blockIdx.z);
-        const unsigned xcd = L & 7u, slot = L >> 3;
-        const unsigned q8 = total >> 3, r8 = total & 7u;          // bijective also when total % 8 != 0
-        const unsigned w = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + slot;
+        const unsigned w = attn_work_index<WORK_XCD>(p);          // XCD-aware work list, no plain-order knob (split inline: through attn_work_split 128 lines differ)
+        const unsigned gx = gridDim.x, gz = gridDim.z;
         wx = (int)(w % gx);
         b = (int)((w / gx) % gz);
         h = (int)(w / (gx * gz));
