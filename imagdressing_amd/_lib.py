@@ -155,6 +155,14 @@ class LoraRowsParams(_Sized):
                 ("x_ld", C.c_int), ("out_ld", C.c_int), ("dtype", C.c_int)]
 
 
+SCALE_ROWS_MAX_SEGMENTS = 16         # IMD_SCALE_ROWS_MAX_SEGMENTS
+
+
+class ScaleRowsParams(_Sized):
+    _fields_ = [("struct_bytes", C.c_uint32), ("dtype", C.c_int), ("rows", C.c_int), ("segments", C.c_int), ("scale_rows", C.c_void_p),
+                ("data", C.c_void_p * SCALE_ROWS_MAX_SEGMENTS), ("row_elems", C.c_int * SCALE_ROWS_MAX_SEGMENTS)]
+
+
 class ImageResampleParams(_Sized):
     _fields_ = [("struct_bytes", C.c_uint32),
         ("src", C.c_void_p), ("src_row_stride", C.c_int64), ("src_img_stride", C.c_int64), ("out", C.c_void_p), ("tmp", C.c_void_p),
@@ -239,6 +247,7 @@ SYMBOLS = {
     "imd_guidance_rescale": (C.c_int, [C.POINTER(GuidanceRescaleParams), C.c_void_p]),
     "imd_noise_rows": (C.c_int, [C.POINTER(NoiseParams), C.c_void_p]),
     "imd_lora_expand_rows": (C.c_int, [C.POINTER(LoraRowsParams), C.c_void_p]),
+    "imd_residual_scale_rows": (C.c_int, [C.POINTER(ScaleRowsParams), C.c_void_p]),
     "imd_session_input_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "imd_image_resample": (C.c_int, [C.POINTER(ImageResampleParams), C.c_void_p]),
     "imd_image_resample_form": (C.c_int, [C.POINTER(ImageResampleParams)]),

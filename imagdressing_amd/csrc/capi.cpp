@@ -347,6 +347,25 @@ int imd_noise_rows(const imd_noise_params* p, void* stream) {
     return imd_launch_noise_rows(*p, (hipStream_t)stream);
 }
 
+int imd_residual_scale_rows(const imd_scale_rows_params* p, void* stream) {
+    const char* n = "residual_scale_rows";
+    IMD_REQUIRE(p != nullptr, "%s: null params", n);
+    IMD_REQUIRE_SIZE(p, n);
+    IMD_REQUIRE(p->dtype == IMD_DTYPE_BF16 || p->dtype == IMD_DTYPE_F16, "%s: unknown dtype %d", n, p->dtype);
+    IMD_REQUIRE(p->segments >= 1 && p->segments <= IMD_SCALE_ROWS_MAX_SEGMENTS, "%s: segments (%d) outside 1..%d", n, p->segments,
+                IMD_SCALE_ROWS_MAX_SEGMENTS);
+    IMD_REQUIRE(p->rows >= 1, "%s: rows (%d) must be at least 1", n, p->rows);
+    IMD_REQUIRE(p->scale_rows != nullptr, "%s: null scale_rows", n);
+    IMD_REQUIRE(((uintptr_t)p->scale_rows & 3) == 0, "%s: scale_rows must be 4-byte aligned", n);
+    for (int k = 0; k < p->segments; ++k) {
+        IMD_REQUIRE(p->row_elems[k] > 0 && p->row_elems[k] % 8 == 0, "%s: row_elems[%d] (%d) must be a positive multiple of 8", n, k,
+                    p->row_elems[k]);
+        IMD_REQUIRE(p->data[k] != nullptr, "%s: null data[%d]", n, k);
+        IMD_REQUIRE(((uintptr_t)p->data[k] & 15) == 0, "%s: data[%d] must be 16-byte aligned", n, k);
+    }
+    return imd_launch_residual_scale_rows(*p, (hipStream_t)stream);
+}
+
 int imd_session_input_rows(const float* z, const int* row_slot, const float* in_scale_rows, void* x_in, int B, int slots, int HW,
                            int dtype_code, void* stream) {
     return imd_launch_session_input_rows(z, row_slot, in_scale_rows, (bf16_t*)x_in, B, slots, HW, dtype_code, (hipStream_t)stream);

@@ -6,7 +6,7 @@ from typing import Any, Callable, Dict, List, Optional, Union
 
 import torch
 
-from ._base import (PipelineBase, RefSAttnProcessor2_0, as_batch, controlnet_keep, first, min_guidance, per_call_value, set_scale_by_type)
+from ._base import PipelineBase, RefSAttnProcessor2_0, as_batch, min_guidance, per_call_value, set_scale_by_type
 
 
 class IMAGDressing_v1(PipelineBase):
@@ -21,25 +21,28 @@ class IMAGDressing_v1(PipelineBase):
     def set_scale(self, scale):                                              # :352-355
         set_scale_by_type(self.unet, RefSAttnProcessor2_0, scale=scale)
 
-    def _control(self, pose_image, prompt_embeds, negative_prompt_embeds, num_inference_steps, scale, start, end, device, size=None):
+    def _control(self, pose_image, prompt_embeds, negative_prompt_embeds, num_inference_steps, scale, start, end, device, size=None, requests=1):
         """ControlNet inputs: the pose image (shared by the CFG halves, :497-498) and the TEXT-ONLY embeddings
-        (``prompt_embeds_control``, ..._ipa_controlnet.py:550)."""
+        (``prompt_embeds_control``, ..._ipa_controlnet.py:550).  ``rows``: None (the folded route), or with
+        ``enable_request_control_scales`` and differing (scale, start, end) the effective scale of every request at every step."""
         if pose_image is None:
             return None
         image, hw = self._image_tensor(pose_image, device, normalize=False, size=size, multiple=self.vae_scale_factor, layout="nhwc8")
+        scale, keep, rows = self._control_plan(scale, start, end, requests, num_inference_steps)
         return dict(image=image, hw=hw, prompt_embeds=prompt_embeds,
-                    negative_prompt_embeds=negative_prompt_embeds, scale=float(first(scale)),
-                    keep=controlnet_keep(num_inference_steps, float(first(start)), float(first(end))))
+                    negative_prompt_embeds=negative_prompt_embeds, scale=scale, keep=keep, rows=rows)
 
     def open_session(self, slots: int, width: int, height: int, controlnet_conditioning_scale: float = 1.0, compact: bool = False, widths=None,
-                     device_noise: Optional[bool] = None):
+                     device_noise: Optional[bool] = None, control_rows: Optional[bool] = None):
         """In-flight batching: a :class:`imagdressing_amd.session.DenoiseSession` with ``slots`` slots at ``width`` x ``height``; every
         request brings its own pose image, ``controlnet_conditioning_scale`` holds for the whole session (the gate is one scalar per
-        launch).  A pipeline built without a ControlNet opens the session of the base pipeline.  ``compact`` / ``widths``: run only as
-        many batch rows as requests are running; ``device_noise``: per-request seeded noise, None = follow ``enable_device_noise``
-        (``_open_session``)."""
+        launch) unless ``control_rows`` (None = follow ``enable_request_control_scales``): then ``submit`` takes
+        ``controlnet_conditioning_scale`` (None: the value given here), ``control_guidance_start`` and ``control_guidance_end`` per
+        request and every step runs one ``imd_residual_scale_rows`` launch behind the ControlNet, whatever the values.  A pipeline
+        built without a ControlNet opens the session of the base pipeline.  ``compact`` / ``widths``: run only as many batch rows as
+        requests are running; ``device_noise``: per-request seeded noise, None = follow ``enable_device_noise`` (``_open_session``)."""
         return self._open_session(slots, width, height, controlnet_conditioning_scale, with_controlnet=self.controlnet is not None,
-                                  compact=compact, widths=widths, device_noise=device_noise)
+                                  compact=compact, widths=widths, device_noise=device_noise, control_rows=control_rows)
 
     @torch.no_grad()
     def __call__(self, prompt, null_prompt, negative_prompt, ref_image, width, height, num_inference_steps, guidance_scale,
@@ -59,7 +62,9 @@ class IMAGDressing_v1(PipelineBase):
                                      pose_image=pose_image, guidance_scale=guidance_scale, image_scale=image_scale,
                                      guidance_rescale=guidance_rescale),
                                 dict(num_inference_steps=num_inference_steps, eta=eta, controlnet_conditioning_scale=controlnet_conditioning_scale),
-                                shard_over_ranks)
+                                shard_over_ranks,
+                                control=dict(controlnet_conditioning_scale=controlnet_conditioning_scale,
+                                             control_guidance_start=control_guidance_start, control_guidance_end=control_guidance_end))
         num_inference_steps, eta = per_call_value("num_inference_steps", num_inference_steps), per_call_value("eta", eta)
         if guess_mode or min_guidance(guidance_scale) <= 1.0:
             # neither runs in the reference: with guess_mode its ControlNet sees the cond half only and the loop then indexes
@@ -77,7 +82,7 @@ class IMAGDressing_v1(PipelineBase):
                                                           ref_clip_hidden_states, device)
         control = self._control(as_batch(pose_image, "pose_image"), prompt_embeds, negative_prompt_embeds, num_inference_steps,
                                 controlnet_conditioning_scale, control_guidance_start, control_guidance_end, device,
-                                size=(height, width))
+                                size=(height, width), requests=R)
         if control is not None:
             height, width = control["hw"]                                   # :501
         self.scheduler.set_timesteps(num_inference_steps, device=device)      # (init_noise_sigma may depend on the schedule; IMAGDressing_v1_pipeline.py:386)

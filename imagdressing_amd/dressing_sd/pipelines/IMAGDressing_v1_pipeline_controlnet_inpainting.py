@@ -7,7 +7,7 @@ from typing import Any, Callable, Dict, List, Optional, Union
 import torch
 
 from ...unet import nchw_to_nhwc8
-from ._base import (PipelineBase, RefSAttnProcessor2_0, RequestLayout, StableDiffusionPipelineOutput, as_batch, controlnet_keep, first,
+from ._base import (PipelineBase, RefSAttnProcessor2_0, RequestLayout, StableDiffusionPipelineOutput, as_batch,
                     min_guidance, per_call_value, randn_tensor, set_scale_by_type, to_image_tensor, unipc_fused)
 
 
@@ -270,7 +270,9 @@ class IMAGDressing_v1(PipelineBase):
                                      mask_latents=mask_latents, guidance_scale=guidance_scale, image_scale=image_scale,
                                      guidance_rescale=guidance_rescale),
                                 dict(num_inference_steps=num_inference_steps, strength=strength, eta=eta,
-                                     controlnet_conditioning_scale=controlnet_conditioning_scale), shard_over_ranks)
+                                     controlnet_conditioning_scale=controlnet_conditioning_scale), shard_over_ranks,
+                                control=dict(controlnet_conditioning_scale=controlnet_conditioning_scale,
+                                             control_guidance_start=control_guidance_start, control_guidance_end=control_guidance_end))
         num_inference_steps, strength, eta = (per_call_value("num_inference_steps", num_inference_steps), per_call_value("strength", strength),
                                               per_call_value("eta", eta))
         if guess_mode or min_guidance(guidance_scale) <= 1.0 or timesteps:
@@ -326,10 +328,12 @@ class IMAGDressing_v1(PipelineBase):
         else:
             control_tensor = self._image_tensor(as_batch(control_image, "control_image"), device, normalize=False, size=(height, width),
                                                 multiple=self.vae_scale_factor, layout="nhwc8")[0]
+        # (enable_request_control_scales and differing triples: ``rows``, the effective scale of every request at every step that runs)
+        ctrl_scale, ctrl_keep, ctrl_rows = self._control_plan(controlnet_conditioning_scale, control_guidance_start, control_guidance_end,
+                                                              R, max(steps_run, 1))
         control = dict(image=control_tensor,
                        prompt_embeds=prompt_embeds,
-                       negative_prompt_embeds=negative_prompt_embeds, scale=float(first(controlnet_conditioning_scale)),
-                       keep=controlnet_keep(max(steps_run, 1), float(first(control_guidance_start)), float(first(control_guidance_end))))
+                       negative_prompt_embeds=negative_prompt_embeds, scale=ctrl_scale, keep=ctrl_keep, rows=ctrl_rows)
         B = R * num_images_per_prompt
         h, w = height // self.vae_scale_factor, width // self.vae_scale_factor
         # strength == 1.0: start from pure noise; the SAME noise re-noises the original latents in the blend (:496-498).

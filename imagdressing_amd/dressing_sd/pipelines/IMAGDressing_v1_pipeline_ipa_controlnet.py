@@ -8,7 +8,7 @@ from typing import Any, Callable, Dict, List, Optional, Union
 import torch
 
 from ...adapter.resampler import ProjPlusModel
-from ._base import (IPAttnProcessor2_0, LoRAIPAttnProcessor2_0, LoraRefSAttnProcessor2_0, PipelineBase, as_batch, controlnet_keep, first,
+from ._base import (IPAttnProcessor2_0, LoRAIPAttnProcessor2_0, LoraRefSAttnProcessor2_0, PipelineBase, as_batch,
                     min_guidance, per_call_value, request_rows, set_scale_by_type)
 
 
@@ -107,7 +107,9 @@ class IMAGDressing_v1(PipelineBase):
                                      face_uncond_clip_hidden_states=face_uncond_clip_hidden_states,
                                      guidance_scale=guidance_scale, image_scale=image_scale, guidance_rescale=guidance_rescale),
                                 dict(dict(num_inference_steps=num_inference_steps, eta=eta, controlnet_conditioning_scale=controlnet_conditioning_scale),
-                                     **({} if rows_on else adapter)), shard_over_ranks)
+                                     **({} if rows_on else adapter)), shard_over_ranks,
+                                control=dict(controlnet_conditioning_scale=controlnet_conditioning_scale,
+                                             control_guidance_start=control_guidance_start, control_guidance_end=control_guidance_end))
         num_inference_steps, eta = per_call_value("num_inference_steps", num_inference_steps), per_call_value("eta", eta)
         adapter_rows = None
         if rows_on:
@@ -147,10 +149,11 @@ class IMAGDressing_v1(PipelineBase):
         if pose_image is not None:                                            # ControlNet sees the 77 text tokens only (:550)
             image, (height, width) = self._image_tensor(as_batch(pose_image, "pose_image"), device, normalize=False, size=(height, width),
                                                         multiple=self.vae_scale_factor, layout="nhwc8")
+            # (enable_request_control_scales and differing triples: ``rows``, the effective scale of every request at every step)
+            ctrl_scale, ctrl_keep, ctrl_rows = self._control_plan(controlnet_conditioning_scale, control_guidance_start, control_guidance_end,
+                                                                  R, num_inference_steps)
             control = dict(image=image, prompt_embeds=prompt_embeds,
-                           negative_prompt_embeds=negative_prompt_embeds, scale=float(first(controlnet_conditioning_scale)),
-                           keep=controlnet_keep(num_inference_steps, float(first(control_guidance_start)),
-                                                float(first(control_guidance_end))))
+                           negative_prompt_embeds=negative_prompt_embeds, scale=ctrl_scale, keep=ctrl_keep, rows=ctrl_rows)
         if has_face:                                                          # :513-521, :555-557
             pos, neg = self.get_image_embeds(face_clip_image, faceid_embeds, face_clip_hidden_states, face_uncond_clip_hidden_states)
             if R > 1:                                                         # one face per request (or one shared by all)

@@ -208,6 +208,27 @@ class PipelineBase:
     def disable_request_adapter_scales(self):
         return self.enable_request_adapter_scales(False)
 
+    def enable_request_control_scales(self, flag: bool = True):
+        """Opt in to ``controlnet_conditioning_scale``, ``control_guidance_start`` and ``control_guidance_end`` PER REQUEST in a
+        request-batched call of the ControlNet, IP-Adapter + ControlNet and inpainting pipelines (and in their sessions,
+        ``open_session(control_rows=...)``): each takes one value or one per request.  The route is chosen once per call.  Requests
+        whose (scale, start, end) triples all agree keep the folded route -- the scale is ``out_scale`` of the 13 zero-conv launches,
+        every launch and every bit as with the switch off.  Otherwise the whole call takes the rows route: the zero convs run with
+        ``out_scale`` = 1 and ONE ``imd_residual_scale_rows`` launch per step gives every batch row ``scale_r * keep_r[step]``; a
+        row at 1.0 is not touched.  A residual is then 16-bit(s 16-bit(W x + b)) instead of 16-bit(s (W x + b)): at most one unit in the
+        last place apart, equal where s is 1 (bf16: a power of two).  On the rows route ``enable_step_graph`` replays calls whose gate
+        changes over the steps (the scale array is refreshed next to the coefficients).  Off by default: a differing list then raises
+        and the window arguments read their first entry, as ever.  A no-op on the base pipeline, which has no ControlNet."""
+        self._request_control_scales = bool(flag)
+        return self
+
+    def disable_request_control_scales(self):
+        return self.enable_request_control_scales(False)
+
+    def _control_plan(self, scale, start, end, R: int, steps: int):
+        """-> (scale, keep, rows) of a call's ``control`` dict: ``control_plan`` under this pipeline's switch"""
+        return control_plan(scale, start, end, R, steps, per_request=getattr(self, "_request_control_scales", False))
+
     def enable_device_noise(self, flag: bool = True):
         """Opt in to noise that belongs to a REQUEST and is made on the device (``imd_noise_rows``, imagdressing_amd/noise.py): the
         initial latents (unless ``latents=`` is given), the per-step noise of Euler-ancestral and of ``eta`` > 0 (unless
@@ -487,6 +508,22 @@ class PipelineBase:
         if variance_noise is not None and stochastic and len(variance_noise) < len(timesteps):
             raise ValueError(f"variance_noise has {len(variance_noise)} entries for {len(timesteps)} steps")
         ctrl_scale = 0.0 if control is None else float(control.get("scale", 1.0))
+        # control["rows"] (enable_request_control_scales, the triples differ): the rows route for the whole call -- the effective scale of
+        # every batch row at every UNet call, uploaded once; the captured step of a graph reads the fixed-address ctrl_dev instead
+        ctrl_table = ctrl_dev = None
+        if control is not None and control.get("rows") is not None:
+            if len(control["rows"]) != lay.requests:
+                raise ValueError(f"control rows: {len(control['rows'])} requests' scales for {lay.requests} requests")
+            ctrl_table = control_scale_table(control["rows"], len(timesteps), lay, clamp=fused).to(dev)
+            ctrl_dev = torch.ones(2 * B, dtype=torch.float32, device=dev)
+
+        def control_residuals(t, i, mode):
+            """the ControlNet forward of UNet call ``i`` (None: the captured step of a graph replay) -> (down, mid)"""
+            if control is None:
+                return None, None
+            if ctrl_table is not None:
+                return self.controlnet.forward_nhwc(x_in, t, ctrl_ehs, ctrl_img, 1.0, scale_rows=ctrl_dev if i is None else ctrl_table[i], **mode)
+            return self.controlnet.forward_nhwc(x_in, t, ctrl_ehs, ctrl_img, ctrl_scale * (keeps[0] if i is None else keeps[i]), **mode)
         # DeepCache (enable_deepcache): one feature cache for this call, shared by the UNet and the ControlNet; UNet call i == loop index i
         # (timesteps holds the executed calls only, PNDM's extra one included).  Switch off or interval 1: no cache, no keyword, today's calls
         dc_on = getattr(self, "_deepcache", None) is not None
@@ -527,10 +564,8 @@ class PipelineBase:
         def sampler_step(t, i=None, coefs=None):
             """ControlNet + UNet + ONE imd_sampler_step -- imd_unipc_step for UniPC -- (CFG / update / history / noise / blend / next UNet input); ``t``, ``coefs`` as
             for ``ddim_step`` (graph replay: the coefficient row, history slot included, is read from device memory)."""
-            down = mid = None
             mode = {} if i is None else dc_kw(i)          # (i is None: the captured step of a graph replay, which never runs with the cache)
-            if control is not None:
-                down, mid = self.controlnet.forward_nhwc(x_in, t, ctrl_ehs, ctrl_img, ctrl_scale * (keeps[0] if i is None else keeps[i]), **mode)
+            down, mid = control_residuals(t, i, mode)
             eps = self.unet.forward_nhwc(x_in, t, ehs, cak, down, mid, cfg_pair=True, **mode)
             if phi_arg is not None:
                 ops.guidance_rescale(eps.view(2 * B, HW, Cl), guidance=g_arg, rescale=phi_arg)
@@ -544,10 +579,8 @@ class PipelineBase:
         def ddim_step(t, i=None, coefs=None):
             """ControlNet + UNet + CFG / DDIM / blend / next UNet input for one timestep; ``t`` a Python int (eager) or a device
             scalar with ``coefs`` the device-side schedule coefficients (graph replay: nothing step-specific is baked in)."""
-            down = mid = None
             mode = {} if i is None else dc_kw(i)
-            if control is not None:
-                down, mid = self.controlnet.forward_nhwc(x_in, t, ctrl_ehs, ctrl_img, ctrl_scale * (keeps[0] if i is None else keeps[i]), **mode)
+            down, mid = control_residuals(t, i, mode)
             eps = self.unet.forward_nhwc(x_in, t, ehs, cak, down, mid, cfg_pair=True, **mode)     # x_in = [z; z]: both halves see the same latent
             if phi_arg is not None:
                 ops.guidance_rescale(eps.view(2 * B, HW, Cl), guidance=g_arg, rescale=phi_arg)
@@ -579,7 +612,7 @@ class PipelineBase:
             # (a stochastic step replays only where its noise is made on the device: Euler-ancestral with enable_device_noise)
             use_graph = (getattr(self, "_step_graph", False) and not dc_on and not multistep and (not stochastic or (noisy and dev_noise))
                          and callback is None and trace is None
-                         and len(timesteps) > 2 and (keeps is None or len(set(keeps)) == 1) and ops.ATTN_EVENT_HOOK is None)
+                         and len(timesteps) > 2 and (keeps is None or ctrl_table is not None or len(set(keeps)) == 1) and ops.ATTN_EVENT_HOOK is None)
             if use_graph:
                 # HIP-graph replay of the denoising step (opt-in, ``enable_step_graph``): step 0 runs eagerly on the pipeline's side stream
                 # (it also fills the step-invariant K / V caches of the processors), step 1 is CAPTURED (not executed) into a graph whose
@@ -604,6 +637,8 @@ class PipelineBase:
                     t_dev.copy_(t_table[0:1]); coef_dev.copy_(coef_table[0])
                     if dev_noise:
                         key_dev.copy_(key_table[0])
+                    if ctrl_table is not None:
+                        ctrl_dev.copy_(ctrl_table[0])
                     temb_bufs = [torch.empty_like(tab[0:1]) for tab in tables]     # fixed addresses inside the captured step, refreshed like t_dev
                     for e, buf, tab in zip(encs, temb_bufs, tables):
                         buf.copy_(tab[0:1])
@@ -619,6 +654,8 @@ class PipelineBase:
                         t_dev.copy_(t_table[i:i + 1]); coef_dev.copy_(coef_table[i])
                         if dev_noise:
                             key_dev.copy_(key_table[i])
+                        if ctrl_table is not None:
+                            ctrl_dev.copy_(ctrl_table[i])
                         for buf, tab in zip(temb_bufs, tables):
                             buf.copy_(tab[i:i + 1])
                         g.replay()
@@ -627,10 +664,8 @@ class PipelineBase:
                 return z.view(B, h, w, Cl).permute(0, 3, 1, 2).contiguous()
             for i, t in enumerate(timesteps):
                 if multistep:
-                    down = mid = None
                     mode = dc_kw(i)
-                    if control is not None:
-                        down, mid = self.controlnet.forward_nhwc(x_in, t, ctrl_ehs, ctrl_img, ctrl_scale * keeps[i], **mode)
+                    down, mid = control_residuals(t, i, mode)
                     eps = self.unet.forward_nhwc(x_in, t, ehs, cak, down, mid, cfg_pair=True, **mode)
                     z = sch.step_guided(eps.view(2 * B, HW, Cl), z, gs[0])
                     # emit the next 16-bit UNet input (both CFG halves) from z: the fused step with eps = 0, alpha = 1 is the identity on z
@@ -654,7 +689,7 @@ class PipelineBase:
 
     # ---- in-flight batching (imagdressing_amd/session.py) ----
     def _open_session(self, slots: int, width: int, height: int, controlnet_conditioning_scale: float = 1.0, with_controlnet: bool = False,
-                      compact: bool = False, widths=None, device_noise: Optional[bool] = None):
+                      compact: bool = False, widths=None, device_noise: Optional[bool] = None, control_rows: Optional[bool] = None):
         """A denoising session of ``slots`` latent rows at one geometry: requests are submitted at any time, enter a free slot at the
         start of any step, run their own number of steps and leave when done (``session.DenoiseSession``).  DPM-Solver++, Euler, PNDM
         and DDIM (eta = 0), UniPC after ``scheduler.enable_fused_step()``; refused with UniPC otherwise, Euler-ancestral and while ``enable_deepcache`` is on; ``enable_step_graph`` is ignored.
@@ -663,13 +698,23 @@ class PipelineBase:
         widths it ran under.
         ``device_noise`` (None: follow ``enable_device_noise``): every request carries a seed (``submit(seed=...)``) and its noise is
         made on the device, one ``imd_noise_rows`` launch per step for all slots -- Euler-ancestral is then accepted, and so is
-        ``submit(eta=...)`` > 0 under DDIM, per request; a request's latents do not depend on its slot or on the other requests."""
+        ``submit(eta=...)`` > 0 under DDIM, per request; a request's latents do not depend on its slot or on the other requests.
+        ``control_rows`` (None: follow ``enable_request_control_scales``; a session with a ControlNet only): the ControlNet scale and
+        its guidance window are per request -- ``submit(controlnet_conditioning_scale=, control_guidance_start=, control_guidance_end=)``
+        -- and EVERY step takes the rows route (``imd_residual_scale_rows`` behind the ControlNet at ``out_scale`` 1), so that a request's
+        bits cannot depend on whether its company happens to share its values."""
         from ...session import DenoiseSession
         return DenoiseSession(self, slots, width, height, controlnet_conditioning_scale, with_controlnet=with_controlnet, compact=compact,
-                              widths=widths, device_noise=device_noise)
+                              widths=widths, device_noise=device_noise, control_rows=control_rows)
 
     # ---- request-batched calls (RequestLayout) ----
-    def _request_count(self, args: Dict[str, Any], per_call: Dict[str, Any], shard_over_ranks: bool) -> int:
+    def _request_count(self, args: Dict[str, Any], per_call: Dict[str, Any], shard_over_ranks: bool,
+                       control: Optional[Dict[str, Any]] = None) -> int:
+        """``control``: the ControlNet pipelines' ``controlnet_conditioning_scale`` / ``control_guidance_start`` / ``control_guidance_end``.
+        Switch off (``enable_request_control_scales``): they are checked as ever -- the scale per call, the window not at all."""
+        if control is not None and getattr(self, "_request_control_scales", False):
+            per_call = {k: v for k, v in per_call.items() if k not in CONTROL_KEYS}
+            return request_count(args, per_call, shard_over_ranks=shard_over_ranks, scheduler=self.scheduler, control=control)
         return request_count(args, per_call, shard_over_ranks=shard_over_ranks, scheduler=self.scheduler)
 
     def _request_prompts(self, R, prompt, negative_prompt, prompt_embeds, negative_prompt_embeds, device, clip_skip=None):
@@ -875,16 +920,64 @@ REQUEST_KEYS = ("prompt", "prompt_embeds", "ref_image", "ref_clip_image", "ref_c
 PER_CALL_KEYS = ("num_inference_steps", "strength", "eta", "ipa_scale", "s_lora_scale", "c_lora_scale", "controlnet_conditioning_scale")
 
 
+CONTROL_KEYS = ("controlnet_conditioning_scale", "control_guidance_start", "control_guidance_end")
+
+
+def control_request_values(scale, start, end, R: int) -> List[tuple]:
+    """The three ControlNet arguments of a call with ``enable_request_control_scales`` -> R triples (scale, start, end).  Each is one
+    value or a sequence of 1 or R (else ValueError naming it).  Where any of them is a sequence: every scale is finite and every
+    window satisfies 0 <= start < end <= 1 (the rule of diffusers' ``check_inputs``); scalars are taken as they are, like the switch-off
+    path takes them."""
+    cols = [per_request_floats(k, v, R) for k, v in zip(CONTROL_KEYS, (scale, start, end))]
+    triples = list(zip(*cols))
+    if any(_is_seq(v) for v in (scale, start, end)):
+        for r, (s, a, b) in enumerate(triples):
+            if not math.isfinite(s):
+                raise ValueError(f"controlnet_conditioning_scale of request {r} must be finite, got {s}")
+            if not (math.isfinite(a) and math.isfinite(b) and 0.0 <= a < b <= 1.0):
+                raise ValueError(f"control_guidance_start / control_guidance_end of request {r}: need 0 <= start < end <= 1, got "
+                                 f"start = {a}, end = {b}")
+    return triples
+
+
+def control_plan(scale, start, end, R: int, steps: int, *, per_request: bool = False):
+    """-> (scale, keep, rows) for the ``control`` dict of :meth:`PipelineBase._denoise`.  ``per_request`` False (the switch is off),
+    or the R triples agree: the FOLDED route -- the first entries as ever, ``rows`` None.  Otherwise the ROWS route for the whole call:
+    scale 1.0, keep all 1 and ``rows[r][i] = scale_r * controlnet_keep(steps, start_r, end_r)[i]``, the effective scale of request r at
+    loop index i."""
+    if per_request:
+        triples = control_request_values(scale, start, end, R)
+        if len(set(triples)) > 1:
+            rows = [[s * k for k in controlnet_keep(steps, a, b)] for s, a, b in triples]
+            return 1.0, [1.0] * steps, rows
+        scale, start, end = triples[0]
+    return float(first(scale)), controlnet_keep(steps, float(first(start)), float(first(end))), None
+
+
+def control_scale_table(rows: Sequence[Sequence[float]], calls: int, lay: "RequestLayout", clamp: bool) -> torch.Tensor:
+    """``rows`` of :func:`control_plan` -> the host table [calls, 2 lay.rows] fp32 that ``imd_residual_scale_rows`` reads one row of per
+    UNet call: request-major over the images of a request (``RequestLayout.per_row``), the cond half then the same values for the
+    uncond half.  ``clamp``: a call index past the gate's length reads its last entry (PNDM calls the UNet once more than it has
+    steps)."""
+    n = len(rows[0])
+    if not clamp and calls > n:
+        raise ValueError(f"the ControlNet gate has {n} entries for {calls} UNet calls")
+    return torch.stack([lay.per_row([r[min(i, n - 1)] for r in rows]).repeat(2) for i in range(calls)])
+
+
 def request_count(args: Dict[str, Any], per_call: Optional[Dict[str, Any]] = None, *, shard_over_ranks: bool = False,
-                  scheduler=None) -> int:
+                  scheduler=None, control: Optional[Dict[str, Any]] = None) -> int:
     """R of a call and the checks of a request-batched one.  R = the largest entry count of the garment / prompt arguments
     (``REQUEST_KEYS``; 1 when all are single).  Every per-request argument in ``args`` has 1 entry (shared) or R, else ValueError
-    naming it; the per-call arguments in ``per_call`` must not differ; ``shard_over_ranks`` and UniPC with differing guidance raise."""
+    naming it; the per-call arguments in ``per_call`` must not differ; ``shard_over_ranks`` and UniPC with differing guidance raise.
+    ``control`` (``enable_request_control_scales``): the three ``CONTROL_KEYS`` arguments, per request -- :func:`control_request_values`."""
     counts = {k: entries(k, v) for k, v in args.items()}
     R = max([c for k, c in counts.items() if k in REQUEST_KEYS and c is not None] or [1])
     for k, c in counts.items():
         if c is not None and c not in (1, R):
             raise ValueError(f"{k} has {c} entries for {R} requests (give one, shared, or one per request)")
+    if control is not None:
+        control_request_values(*(control.get(k, d) for k, d in zip(CONTROL_KEYS, (1.0, 0.0, 1.0))), R)
     if R > 1:
         for k, v in (per_call or {}).items():
             per_call_value(k, v)
@@ -968,5 +1061,5 @@ def set_scale_by_type(unet, cls, **attrs):
 
 
 __all__ = ["deepcache_plan", "RequestLayout", "request_count", "request_rows", "unipc_fused", "per_request_floats", "guidance_rescale_values", "per_call_value", "as_batch", "min_guidance", "entries",
-           "controlnet_keep", "first", "to_image_tensor", "PipelineBase", "StableDiffusionPipelineOutput", "randn_tensor", "set_scale_by_type",
+           "controlnet_keep", "control_plan", "control_request_values", "control_scale_table", "CONTROL_KEYS", "first", "to_image_tensor", "PipelineBase", "StableDiffusionPipelineOutput", "randn_tensor", "set_scale_by_type",
            "RefSAttnProcessor2_0", "LoraRefSAttnProcessor2_0", "LoRAIPAttnProcessor2_0", "IPAttnProcessor2_0"]

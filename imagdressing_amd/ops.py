@@ -1396,6 +1396,47 @@ def lora_expand_rows(x: torch.Tensor, down: torch.Tensor, row_scale: torch.Tenso
     return out
 
 
+# ---- a scale per batch row on several tensors at once: the ControlNet residuals (csrc/residual_scale_rows.hip) ----
+SCALE_ROWS_COUNTER = {"launches": 0}      # imd_residual_scale_rows launches of this process (tests check that the folded route makes none)
+SCALE_ROWS_MAX_SEGMENTS = L.SCALE_ROWS_MAX_SEGMENTS
+
+
+def residual_scale_rows(tensors: Sequence[torch.Tensor], scale_rows: torch.Tensor):
+    """Row r of every tensor times ``scale_rows[r]``, in place, in one launch (``imd_residual_scale_rows``): 1 to 16 contiguous 16-bit
+    device tensors of one dtype with equal ``shape[0]`` = rows whose rows hold a multiple of 8 elements, ``scale_rows`` fp32 [rows] on the
+    device.  A row at exactly 1.0 keeps its bytes; every other gets ``(x.float() * s).to(dtype)``, round to nearest even."""
+    what = "residual_scale_rows"
+    if not isinstance(tensors, (list, tuple)) or not 1 <= len(tensors) <= SCALE_ROWS_MAX_SEGMENTS:
+        n = len(tensors) if isinstance(tensors, (list, tuple)) else type(tensors).__name__
+        raise L.ImdError(f"{what}: expected a list of 1 to {SCALE_ROWS_MAX_SEGMENTS} tensors, got {n}")
+    if not all(isinstance(t, torch.Tensor) and t.dim() >= 1 for t in tensors):
+        raise L.ImdError(f"{what}: every segment must be a torch.Tensor [rows, ...]")
+    first = tensors[0]
+    rows = first.shape[0]
+    if any(t.shape[0] != rows for t in tensors):
+        raise L.ImdError(f"{what}: the tensors differ in shape[0] ({[t.shape[0] for t in tensors]}): one scale per row of all of them")
+    if any(t.dtype != first.dtype for t in tensors):
+        raise L.ImdError(f"{what}: the tensors differ in dtype ({sorted({str(t.dtype) for t in tensors})})")
+    if not isinstance(scale_rows, torch.Tensor) or scale_rows.dim() != 1 or scale_rows.numel() != rows:
+        raise L.ImdError(f"{what}: scale_rows must be a 1-d fp32 device tensor of {rows} values, got "
+                         f"{tuple(getattr(scale_rows, 'shape', ()))}")
+    p = L.ScaleRowsParams()
+    p.dtype, p.rows, p.segments = _code(first, what), rows, len(tensors)
+    for k, t in enumerate(tensors):
+        if rows < 1 or t.numel() == 0 or (t.numel() // rows) % 8:
+            raise L.ImdError(f"{what}: tensor {k} {tuple(t.shape)}: a row must hold a positive multiple of 8 elements")
+        if not t.is_contiguous():
+            raise L.ImdError(f"{what}: tensor {k} must be contiguous (a segment is one [rows, row_elems] block)")
+    for k, t in enumerate(tensors):
+        p.data[k] = _dev(t, first.dtype, f"tensor {k}")
+        p.row_elems[k] = t.numel() // rows
+    ensure_device(first.device)
+    p.scale_rows = _dev(scale_rows, torch.float32, "scale_rows")
+    L.check(L.load().imd_residual_scale_rows(C.byref(p), _stream()))
+    SCALE_ROWS_COUNTER["launches"] += 1
+    return tensors
+
+
 # ---- UniPC on one fused step launch (csrc/unipc_step.hip;the coefficients come from scheduler.UniPCMultistepScheduler.plan_fused) ----
 UNIPC_COEFS = 19
 UNIPC_ROW_FLOATS = 24

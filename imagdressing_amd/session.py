@@ -67,10 +67,14 @@ def check_pipeline(pipe) -> None:
 
 def check_request(*, size, width=None, height=None, num_inference_steps, guidance_scale, image_scale=1.0, eta=0.0,
                   shard_over_ranks=False, control_guidance_start=0.0, control_guidance_end=1.0, num_images_per_prompt=1, slots=1,
-                  guidance_rescale=0.0, device_noise=False, scheduler=None, seed=None) -> None:
+                  guidance_rescale=0.0, device_noise=False, scheduler=None, seed=None, controlnet_conditioning_scale=None,
+                  control_rows=False) -> None:
     """what ``submit`` refuses, before anything is launched or queued.  ``size`` = (width, height) of the session.  ``device_noise``
     (the session draws its noise per request on the device): ``eta`` > 0 is accepted where ``scheduler`` is DDIM and raises ValueError
-    for any other sampler, ``seed`` must be None or an int in [0, 2^64); without it ``eta`` > 0 and ``seed`` are refused."""
+    for any other sampler, ``seed`` must be None or an int in [0, 2^64); without it ``eta`` > 0 and ``seed`` are refused.
+    ``control_rows`` (the session scales the ControlNet residuals per batch row): ``controlnet_conditioning_scale`` is None (the
+    session's) or one finite value and the window needs 0 <= start < end <= 1; without it a scale per request and any window other
+    than 0 / 1 are refused."""
     for name, v in (("num_inference_steps", num_inference_steps), ("guidance_scale", guidance_scale), ("image_scale", image_scale),
                     ("guidance_rescale", guidance_rescale)):
         if isinstance(v, (list, tuple)):
@@ -91,7 +95,20 @@ def check_request(*, size, width=None, height=None, num_inference_steps, guidanc
         raise NotImplementedError("shard_over_ranks: a session lives on one rank (sessions over several ranks are a later change)")
     if (width is not None and int(width) != int(size[0])) or (height is not None and int(height) != int(size[1])):
         raise ValueError(f"width x height {width} x {height}: this session was opened for {size[0]} x {size[1]} (one geometry per session)")
-    if float(control_guidance_start) != 0.0 or float(control_guidance_end) != 1.0:
+    if control_rows:
+        for name, v in (("controlnet_conditioning_scale", controlnet_conditioning_scale), ("control_guidance_start", control_guidance_start),
+                        ("control_guidance_end", control_guidance_end)):
+            if isinstance(v, (list, tuple)):
+                raise ValueError(f"{name} is per request in a session: submit one request per call, got {list(v)}")
+        if controlnet_conditioning_scale is not None and not math.isfinite(float(controlnet_conditioning_scale)):
+            raise ValueError(f"controlnet_conditioning_scale must be finite, got {controlnet_conditioning_scale}")
+        a, b = float(control_guidance_start), float(control_guidance_end)
+        if not (math.isfinite(a) and math.isfinite(b) and 0.0 <= a < b <= 1.0):
+            raise ValueError(f"control_guidance_start / control_guidance_end: need 0 <= start < end <= 1, got start = {a}, end = {b}")
+    elif controlnet_conditioning_scale is not None:
+        raise NotImplementedError("controlnet_conditioning_scale per request: this session was opened without control_rows, its ControlNet "
+                                  "scale is the one given at open_session (out_scale of the zero-conv launches)")
+    elif float(control_guidance_start) != 0.0 or float(control_guidance_end) != 1.0:
         raise NotImplementedError("control_guidance_start / control_guidance_end other than 0 / 1: the ControlNet gate is one scalar "
                                   "per launch (the zero-conv epilogue), the rows of a session are at different steps")
     if float(guidance_scale) <= 1.0:
@@ -108,9 +125,10 @@ def check_request(*, size, width=None, height=None, num_inference_steps, guidanc
 # ---- the plan ----
 class PlanRun:
     """One latent row's run: its own scheduler instance (``set_timesteps(n)``), history bookkeeping and position."""
-    __slots__ = ("scheduler", "ring", "timesteps", "steps", "i", "slot", "row", "in_scale", "ready", "payload", "seed", "image", "eta")
+    __slots__ = ("scheduler", "ring", "timesteps", "steps", "i", "slot", "row", "in_scale", "ready", "payload", "seed", "image", "eta", "control")
 
-    def __init__(self, scheduler, num_inference_steps: int, payload=None, seed: Optional[int] = None, image: int = 0, eta: float = 0.0):
+    def __init__(self, scheduler, num_inference_steps: int, payload=None, seed: Optional[int] = None, image: int = 0, eta: float = 0.0,
+                 control=None):
         # the noise key of the run (a plan with device_noise): the request's seed and the image index inside the request; eta: DDIM's
         self.seed, self.image, self.eta = seed, int(image), float(eta)
         sch = copy.copy(scheduler)          # the class and configuration of the pipeline's scheduler; set_timesteps rebinds, never mutates
@@ -128,6 +146,14 @@ class PlanRun:
             self.timesteps = [int(t) for t in sch.timesteps]
             self.steps = len(self.timesteps)
             self.ring = SamplerHistory(0)
+        # control = (scale, start, end) of a plan with control_rows -> the effective ControlNet scale of every UNet call of the run:
+        # scale * controlnet_keep(num_inference_steps, start, end)[i]; a call past the gate (PNDM's extra one) keeps the last entry
+        self.control: Optional[List[float]] = None
+        if control is not None:
+            scale, start, end = (float(c) for c in control)
+            n = int(num_inference_steps)
+            keep = [1.0 - float(k / n < start or (k + 1) / n > end) for k in range(n)]          # diffusers' gate (pipelines._base.controlnet_keep)
+            self.control = [scale * keep[min(k, n - 1)] for k in range(self.steps)]
         self.i = 0
         self.slot: Optional[int] = None
         self.row: Optional[int] = None          # its position in the batch the forward runs (== slot unless the plan compacts)
@@ -177,13 +203,16 @@ class PlanStep:
     ``row_timesteps[r]``; ``repack`` = the rows were laid out anew before this step.  A plan that does not compact has width =
     slots, row r = slot r and never repacks.  A plan with ``device_noise``: ``noise`` = (slot, seed, image, draw) of every running
     row whose step reads noise and ``key_rows`` [slots][8] = the ``ops.noise_key_row`` of every SLOT for this step (inactive for
-    every other slot), whether the plan compacts or not; otherwise both are None."""
-    __slots__ = ("rows", "timesteps", "running", "finished", "width", "row_slot", "repack", "coef_rows", "row_timesteps", "noise", "key_rows")
+    every other slot), whether the plan compacts or not; otherwise both are None.  A plan with ``control_rows``: ``control_rows``
+    [2 width] = the effective ControlNet scale of every batch ROW for this step, the cond rows then the same values for their uncond
+    twins, 1.0 for an idle row (``imd_residual_scale_rows`` skips it); otherwise None."""
+    __slots__ = ("rows", "timesteps", "running", "finished", "width", "row_slot", "repack", "coef_rows", "row_timesteps", "noise", "key_rows",
+                 "control_rows")
 
     def __init__(self, rows, timesteps, running, finished, width=None, row_slot=None, repack=False, coef_rows=None, row_timesteps=None,
-                 noise=None, key_rows=None):
+                 noise=None, key_rows=None, control_rows=None):
         self.rows, self.timesteps, self.running, self.finished = rows, timesteps, running, finished
-        self.noise, self.key_rows = noise, key_rows
+        self.noise, self.key_rows, self.control_rows = noise, key_rows, control_rows
         self.width = len(rows) if width is None else width
         self.row_slot = list(range(len(rows))) if row_slot is None else row_slot
         self.repack = repack
@@ -218,11 +247,14 @@ def check_widths(slots: int, widths) -> tuple:
 
 
 class SessionPlan:
-    def __init__(self, slots: int, scheduler, compact: bool = False, widths=None, *, device_noise: bool = False):
+    def __init__(self, slots: int, scheduler, compact: bool = False, widths=None, *, device_noise: bool = False, control_rows: bool = False,
+                 control_scale: float = 1.0):
         if int(slots) < 1:
             raise ValueError(f"slots must be >= 1, got {slots}")
         check_scheduler(scheduler, device_noise=bool(device_noise))
         self.device_noise = bool(device_noise)
+        # control_rows: every run carries its own ControlNet scale and window (control_scale: the scale of a run that names none)
+        self.control_rows, self.control_scale = bool(control_rows), float(control_scale)
         # the step launch may be handed a noise operand: the session's sampler can be stochastic (Euler-ancestral, or DDIM -- eta is per request)
         self.noisy = self.device_noise and not unipc_fused(scheduler) and (bool(getattr(scheduler, "stochastic", False))
                                                                          or isinstance(scheduler, DDIMScheduler))
@@ -245,8 +277,15 @@ class SessionPlan:
         self._laid: Optional[PlanLayout] = None
         self.repacks = 0
 
-    def submit(self, num_inference_steps: int, payload=None, *, seed: Optional[int] = None, image: int = 0, eta: float = 0.0) -> PlanRun:
-        """``seed`` / ``image`` (a plan with ``device_noise``): the noise key of the run; ``eta`` > 0: the stochastic DDIM step"""
+    def submit(self, num_inference_steps: int, payload=None, *, seed: Optional[int] = None, image: int = 0, eta: float = 0.0,
+               control=None) -> PlanRun:
+        """``seed`` / ``image`` (a plan with ``device_noise``): the noise key of the run; ``eta`` > 0: the stochastic DDIM step;
+        ``control`` (a plan with ``control_rows``): (scale or None = the plan's, start, end) of the run's ControlNet gate"""
+        if control is not None and not self.control_rows:
+            raise NotImplementedError("a ControlNet scale or window per run: the plan was made without control_rows")
+        if self.control_rows:
+            scale, start, end = control if control is not None else (None, 0.0, 1.0)
+            control = (self.control_scale if scale is None else scale, start, end)
         if unipc_fused(self.scheduler) != self.unipc:
             raise RuntimeError("the scheduler's fused-step switch changed since the session was opened: its buffers and its step kernel "
                                "were chosen for the other setting; open a new session")
@@ -254,7 +293,7 @@ class SessionPlan:
             raise NotImplementedError("eta > 0: the stochastic DDIM step draws noise per step; a session runs the deterministic samplers")
         if float(eta) > 0.0 and not isinstance(self.scheduler, DDIMScheduler):
             raise ValueError(f"eta > 0 is the stochastic DDIM step; this session's sampler is {type(self.scheduler).__name__}")
-        run = PlanRun(self.scheduler, num_inference_steps, payload, seed=seed, image=image, eta=eta)
+        run = PlanRun(self.scheduler, num_inference_steps, payload, seed=seed, image=image, eta=eta, control=control)
         if self.noisy and run.noisy and seed is None:
             raise ValueError("a run whose steps read noise needs its request's seed (DenoiseSession.submit resolves it)")
         self.queue.append(run)
@@ -330,11 +369,14 @@ class SessionPlan:
         rows, ts, running, finished = [], [], [], []
         noise = [] if self.noisy else None          # (slot, seed, image, draw): draw 1 + i, i the step index of the run's own schedule
         keys = [ops.noise_key_row(0, 0, 0, active=False) for _ in range(self.S)] if self.noisy else None
+        gate = {}                                   # slot -> the effective ControlNet scale of its run for this step
         for s, run in enumerate(self._slots):
             if run is None:
                 rows.append(list(self.idle_row))
                 ts.append(None)
                 continue
+            if self.control_rows:
+                gate[s] = run.control[run.i]
             ts.append(run.timesteps[run.i])
             running.append((s, run, run.i))
             if self.noisy and run.noisy:
@@ -347,9 +389,12 @@ class SessionPlan:
                 self._slots[s] = None
                 self._rows[run.row] = None
         if not self.compact:
-            return PlanStep(rows, ts, running, finished, noise=noise, key_rows=keys)
+            ctrl = [gate.get(s, 1.0) for s in range(self.S)] * 2 if self.control_rows else None
+            return PlanStep(rows, ts, running, finished, noise=noise, key_rows=keys, control_rows=ctrl)
         row_slot = [-1 if r is None else r.slot for r in lay.rows]
+        ctrl = [gate.get(s, 1.0) for s in row_slot] * 2 if self.control_rows else None          # by batch ROW: what a repack moved is written anew
         return PlanStep(rows, ts, running, finished, width=lay.width, row_slot=row_slot, repack=lay.repack, noise=noise, key_rows=keys,
+                        control_rows=ctrl,
                         coef_rows=[list(self.idle_row) if s < 0 else rows[s] for s in row_slot],
                         row_timesteps=[None if s < 0 else ts[s] for s in row_slot])
 
@@ -439,6 +484,7 @@ class _WidthViews:
         self.guidance_rows = ses.guidance_rows[:B] if ses.guidance_rows is not None else None
         self.rescale_rows = ses.rescale_rows[:B] if ses.rescale_rows is not None else None
         self.row_slot = ses.row_slot[:B]
+        self.control_rows = ses.control_scale_rows[:2 * B] if ses.control_scale_rows is not None else None
         self.ehs = self.garment = self.cak = None          # with the context buffers, at the first admission
 
     def bind_context(self, ses: "DenoiseSession"):
@@ -453,11 +499,17 @@ class DenoiseSession:
     """``pipe.open_session(slots=S, width=W, height=H, compact=False, widths=None)``; a context manager.  See the module docstring."""
 
     def __init__(self, pipe, slots: int, width: int, height: int, controlnet_conditioning_scale: float = 1.0, with_controlnet: bool = False,
-                 compact: bool = False, widths=None, device_noise: Optional[bool] = None):
+                 compact: bool = False, widths=None, device_noise: Optional[bool] = None, control_rows: Optional[bool] = None):
         check_pipeline(pipe)
         # device_noise None: follow the pipeline's switch (enable_device_noise) as it stands when the session opens
         self.device_noise = bool(getattr(pipe, "_device_noise", False)) if device_noise is None else bool(device_noise)
-        self.plan = SessionPlan(slots, pipe.scheduler, compact=compact, widths=widths, device_noise=self.device_noise)
+        # control_rows None: follow enable_request_control_scales as it stands when the session opens; a session without a ControlNet has no such rows
+        self.control_rows = bool(with_controlnet) and (bool(getattr(pipe, "_request_control_scales", False)) if control_rows is None
+                                                       else bool(control_rows))
+        if control_rows and not with_controlnet:
+            raise ValueError("open_session: control_rows needs a ControlNet; this session has none")
+        self.plan = SessionPlan(slots, pipe.scheduler, compact=compact, widths=widths, device_noise=self.device_noise,
+                                control_rows=self.control_rows, control_scale=float(controlnet_conditioning_scale))
         self.pipe = pipe
         self.compact = self.plan.compact
         vsf = pipe.vae_scale_factor
@@ -489,6 +541,9 @@ class DenoiseSession:
         # reads noise by slot).  noise is ZERO-FILLED: a row with z_n = 0 multiplies it, so it must never hold uninitialised bytes
         self.noise = torch.zeros(S, self.HW, 4, dtype=torch.float32, device=dev) if self.plan.noisy else None
         self.key_rows = torch.zeros(S, ops.NOISE_ROW_WORDS, dtype=torch.int32, device=dev) if self.plan.noisy else None
+        # control_rows: the effective ControlNet scale of every batch ROW, [cond; uncond] at the current width, rewritten whole every step
+        # (idle rows 1.0: imd_residual_scale_rows leaves them alone)
+        self.control_scale_rows = torch.ones(2 * S, dtype=torch.float32, device=dev) if self.control_rows else None
         self.coef_rows = torch.zeros(S, self.plan.row_floats, dtype=torch.float32, device=dev)
         self.row_slot = torch.arange(S, dtype=torch.int32, device=dev)
         self._row_slot_host = list(range(S))
@@ -549,7 +604,7 @@ class DenoiseSession:
                 t.error = RuntimeError("the session was closed")
         self._tickets = []
         self.plan = None
-        for name in ("z", "x_in", "hist", "noise", "key_rows", "mask_rows", "guidance", "guidance_rows", "rescale", "rescale_rows", "coef_rows", "row_slot", "temb", "ctrl_img", "ehs",
+        for name in ("z", "x_in", "hist", "noise", "key_rows", "mask_rows", "guidance", "guidance_rows", "rescale", "rescale_rows", "control_scale_rows", "coef_rows", "row_slot", "temb", "ctrl_img", "ehs",
                      "garment", "_views"):
             setattr(self, name, None)
 
@@ -564,19 +619,24 @@ class DenoiseSession:
                negative_prompt_embeds=None, ref_clip_hidden_states=None, ref_image_latents=None, latents=None,
                width: Optional[int] = None, height: Optional[int] = None, eta: float = 0.0, shard_over_ranks: bool = False,
                control_guidance_start: float = 0.0, control_guidance_end: float = 1.0, guidance_rescale: float = 0.0,
-               seed: Optional[int] = None) -> SessionTicket:
+               seed: Optional[int] = None, controlnet_conditioning_scale: Optional[float] = None) -> SessionTicket:
         """Queue one request (the per-request arguments of the pipeline's ``__call__``, with ``num_inference_steps``, ``guidance_scale``,
         ``image_scale`` and ``guidance_rescale`` per request) and return its ticket.  Never blocks and launches nothing: the request is admitted at the
         start of the first ``step()`` in which a slot is free.  ``num_images_per_prompt`` = n takes n slots.
         A session with ``device_noise``: ``seed`` (an int in [0, 2^64); else ``generator.initial_seed()``, else 8 bytes of
         ``os.urandom``; kept in ``ticket.seed``) keys the request's noise -- draw 0 its initial latents (unless ``latents`` is given),
-        draw 1 + i its step i -- and ``eta`` > 0 is the stochastic DDIM step of this request alone."""
+        draw 1 + i its step i -- and ``eta`` > 0 is the stochastic DDIM step of this request alone.
+        A session with ``control_rows``: ``controlnet_conditioning_scale`` (None: the value given at ``open_session``),
+        ``control_guidance_start`` and ``control_guidance_end`` are this request's; its step i of n runs the ControlNet at
+        ``scale * controlnet_keep(n, start, end)[i]``."""
         self._check_open()
         check_request(size=(self.image_width, self.image_height), width=width, height=height, num_inference_steps=num_inference_steps,
                       guidance_scale=guidance_scale, image_scale=image_scale, eta=eta, shard_over_ranks=shard_over_ranks,
                       control_guidance_start=control_guidance_start, control_guidance_end=control_guidance_end,
                       num_images_per_prompt=num_images_per_prompt, slots=self.S, guidance_rescale=guidance_rescale,
-                      device_noise=self.device_noise, scheduler=self.plan.scheduler, seed=seed)
+                      device_noise=self.device_noise, scheduler=self.plan.scheduler, seed=seed,
+                      controlnet_conditioning_scale=controlnet_conditioning_scale, control_rows=self.control_rows)
+        control = (controlnet_conditioning_scale, float(control_guidance_start), float(control_guidance_end)) if self.control_rows else None
         if self.device_noise:
             if isinstance(generator, (list, tuple)):
                 raise ValueError("generator: a session request has one seed; pass one generator or seed=")
@@ -597,7 +657,7 @@ class DenoiseSession:
         ticket = SessionTicket(req)
         ticket.seed = seed
         for j in range(n):
-            ticket._runs.append(self.plan.submit(num_inference_steps, payload=(ticket, j), seed=seed, image=j, eta=float(eta)))
+            ticket._runs.append(self.plan.submit(num_inference_steps, payload=(ticket, j), seed=seed, image=j, eta=float(eta), control=control))
             ticket._latents.append(None)
         self._tickets.append(ticket)
         return ticket
@@ -761,7 +821,11 @@ class DenoiseSession:
                 e.use_time_embedding(buf)
             down = mid = None
             if self.controlnet is not None:
-                down, mid = self.controlnet.forward_nhwc(v.x_in, 0, v.ehs, v.ctrl_img, self.control_scale)
+                if self.control_rows:          # ALWAYS the rows route: a request's bits do not depend on its company's values
+                    v.control_rows.copy_(torch.tensor(st.control_rows, dtype=torch.float32))
+                    down, mid = self.controlnet.forward_nhwc(v.x_in, 0, v.ehs, v.ctrl_img, 1.0, scale_rows=v.control_rows)
+                else:
+                    down, mid = self.controlnet.forward_nhwc(v.x_in, 0, v.ehs, v.ctrl_img, self.control_scale)
             eps = pipe.unet.forward_nhwc(v.x_in, 0, v.ehs, v.cak, down, mid, cfg_pair=True)
         finally:
             for e in self.encoders:

@@ -829,11 +829,21 @@ class ControlNetModel(_Encoder):
         return e
 
     def forward_nhwc(self, x, timestep, encoder_hidden_states, cond_nhwc8, conditioning_scale: float = 1.0,
-                     deepcache: Optional[DeepCache] = None):
+                     deepcache: Optional[DeepCache] = None, scale_rows: Optional[torch.Tensor] = None):
         """x [B, H, W, 8]; cond [Bc, 8H, 8W, 8] with Bc == B or 1 -> (list of 12 NHWC residuals, mid).
         ``deepcache`` in its shallow mode (``not deepcache.full``): the residuals a shallow UNet forward reads -- conv_in, the conditioning
-        embedding, layers 0 .. depth - 2 of the first down block and zero-convs 0 .. depth - 1 -> (list of depth residuals, None)."""
+        embedding, layers 0 .. depth - 2 of the first down block and zero-convs 0 .. depth - 1 -> (list of depth residuals, None).
+        ``scale_rows`` (a device fp32 [B] array, one conditioning scale per batch row): the zero convs run with out_scale = 1 and ONE
+        ``imd_residual_scale_rows`` launch then scales, in place, the residuals that exist (every zero conv's output is a fresh tensor
+        of this forward, nothing else reads it); a row at 1.0 keeps its bytes.  ``conditioning_scale`` must then be 1."""
         B = x.shape[0]
+        if scale_rows is not None:
+            if float(conditioning_scale) != 1.0:
+                raise ValueError(f"ControlNet: scale_rows and conditioning_scale = {conditioning_scale} were both given; with a scale per "
+                                 "row the scalar must be 1")
+            if not isinstance(scale_rows, torch.Tensor) or scale_rows.dim() != 1 or scale_rows.numel() != B:
+                raise ValueError(f"ControlNet: scale_rows must be a 1-d fp32 device tensor of {B} values (one per batch row), got "
+                                 f"{tuple(getattr(scale_rows, 'shape', ()))}")
         layers = None
         if deepcache is not None:
             deepcache.check_depth(len(self.down_blocks[0].resnets))
@@ -854,6 +864,8 @@ class ControlNetModel(_Encoder):
         for s, zc in zip(skips, self.zero_convs):
             down.append(_scaled_conv1x1(zc, s, conditioning_scale))
         mid = None if layers is not None else _scaled_conv1x1(self.zero_mid, h, conditioning_scale)
+        if scale_rows is not None:
+            ops.residual_scale_rows(down + ([mid] if mid is not None else []), scale_rows)
         return down, mid
 
     def forward(self, sample, timestep, encoder_hidden_states, controlnet_cond, conditioning_scale=1.0,

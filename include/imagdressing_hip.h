@@ -411,6 +411,24 @@ typedef struct imd_lora_rows_params {
     int dtype;
 } imd_lora_rows_params;
 
+/* A scale per batch row on up to 16 tensors at once, in place (imd_residual_scale_rows): the ControlNet residuals of a batch whose
+ * requests differ in controlnet_conditioning_scale or in their guidance window.  The zero convs then run with out_scale = 1 and this
+ * launch follows them.  Segment k is a contiguous 16-bit [rows, row_elems[k]] tensor; for every segment and every row r
+ *   scale_rows[r] == 1.0f:  the row is neither read nor written -- its bytes, NaN payloads included, stay
+ *   otherwise:              out = 16-bit( float(x) * scale_rows[r] )     widen, ONE fp32 multiply, round to nearest even
+ * 0 and negative values are scales like any other.  Against the folded launch, 16-bit(s (W x + b)), the result 16-bit(s 16-bit(W x + b))
+ * carries one more rounding: at most one unit in the last place of the element type, none where s is 1 (bf16: a power of two).
+ * Segments must not overlap. */
+#define IMD_SCALE_ROWS_MAX_SEGMENTS 16
+typedef struct imd_scale_rows_params {
+    uint32_t struct_bytes; /* sizeof(imd_scale_rows_params) in the caller's view; checked on entry */
+    int dtype;             /* IMD_DTYPE_*: the element type of every segment */
+    int rows, segments;    /* rows >= 1; segments in 1..IMD_SCALE_ROWS_MAX_SEGMENTS */
+    const float* scale_rows; /* DEVICE [rows] fp32, 4-byte aligned: the same array for all segments */
+    void* data[16];        /* [IMD_SCALE_ROWS_MAX_SEGMENTS] segment bases, 16-byte aligned; entries at or past `segments` are not read */
+    int row_elems[16];     /* elements per row of each segment: positive multiples of 8 */
+} imd_scale_rows_params;
+
 /* Device-side image input (imd_image_resample): separable antialiased resampling of uint8 images, bit-exact with Pillow's 8-bit
  * resampler (libImaging/Resample.c), with a fused output stage -- the work diffusers' VaeImageProcessor / transformers'
  * CLIPImageProcessor do on the host in front of IMAGDressing_v1_pipeline*.py.  Per axis whose size changes the caller passes a
@@ -770,6 +788,12 @@ int imd_noise_rows(const imd_noise_params* p, void* stream);
  * outside 16..384, M != E * rows_per_entry (or any of them < 1), x_ld < C, out_ld < C + T, a leading dimension that is not a multiple of
  * 8 elements, x / down / out not 16-byte aligned, row_scale not 4-byte aligned, out overlapping x, an operand of 2 GiB or more. */
 int imd_lora_expand_rows(const imd_lora_rows_params* p, void* stream);
+
+/* Every row of every segment times its row's scale, in place, as ONE launch (16 KiB chunks numbered through all segments, see
+ * residual_scale_rows.hip); see imd_scale_rows_params.  Errors without launching: null params, a foreign struct_bytes, an unknown
+ * dtype, segments outside 1..16, rows < 1, scale_rows NULL or not 4-byte aligned, a row_elems that is not a positive multiple of 8,
+ * a data pointer that is NULL or not 16-byte aligned, 2^31 chunks or more. */
+int imd_residual_scale_rows(const imd_scale_rows_params* p, void* stream);
 
 /* Pillow-exact resize (+ crop, normalise, layout) of uint8 images on the device; see imd_image_resample_params.  Errors without
  * launching: a foreign struct size, null src / out, C outside {1, 3}, an incomplete table or a skipped axis whose size changes, a
