@@ -198,6 +198,16 @@ class ImageMaskFilterParams(_Sized):
                 ("r", C.c_uint32), ("ww", C.c_uint32), ("fw", C.c_uint32), ("flags", C.c_int)]
 
 
+class ImageMaskReleaseParams(_Sized):
+    _fields_ = [("struct_bytes", C.c_uint32), ("src", C.c_void_p), ("src_row_stride", C.c_int64), ("out", C.c_void_p),
+                ("H0", C.c_int), ("W0", C.c_int), ("h", C.c_int), ("w", C.c_int), ("n", C.c_int)]
+
+
+class SoftMaskRowsParams(_Sized):
+    _fields_ = [("struct_bytes", C.c_uint32), ("release", C.c_void_p), ("step_rows", C.c_void_p), ("mask", C.c_void_p),
+                ("B", C.c_int), ("HW", C.c_int)]
+
+
 # every symbol include/imagdressing_hip.h declares: name -> (restype, argtypes)
 SYMBOLS = {
     "imd_abi_version": (C.c_int, []),
@@ -256,6 +266,8 @@ SYMBOLS = {
     "imd_image_inpaint_condition": (C.c_int, [C.POINTER(ImageInpaintConditionParams), C.c_void_p]),
     "imd_image_mask_filter": (C.c_int, [C.POINTER(ImageMaskFilterParams), C.c_void_p]),
     "imd_image_mask_filter_form": (C.c_int, [C.POINTER(ImageMaskFilterParams)]),
+    "imd_image_mask_release": (C.c_int, [C.POINTER(ImageMaskReleaseParams), C.c_void_p]),
+    "imd_soft_mask_rows": (C.c_int, [C.POINTER(SoftMaskRowsParams), C.c_void_p]),
     "imd_timestep_embedding": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "imd_add": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_long, C.c_int, C.c_float, C.c_int, C.c_void_p]),
     "imd_embed_tokens": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_long, C.c_int, C.c_int, C.c_void_p]),

@@ -411,6 +411,18 @@ int imd_image_mask_filter_form(const imd_image_mask_filter_params* p) {
     return imd_image_mask_filter_form_of(*p);
 }
 
+int imd_image_mask_release(const imd_image_mask_release_params* p, void* stream) {
+    IMD_REQUIRE(p != nullptr, "image_mask_release: null params");
+    IMD_REQUIRE_SIZE(p, "image_mask_release");
+    return imd_launch_image_mask_release(*p, (hipStream_t)stream);
+}
+
+int imd_soft_mask_rows(const imd_soft_mask_rows_params* p, void* stream) {
+    IMD_REQUIRE(p != nullptr, "soft_mask_rows: null params");
+    IMD_REQUIRE_SIZE(p, "soft_mask_rows");
+    return imd_launch_soft_mask_rows(*p, (hipStream_t)stream);
+}
+
 int imd_ddim_cfg_step_rows(const imd_ddim_params* p, const float* guidance, void* stream) {
     IMD_REQUIRE(p != nullptr, "ddim_cfg_step_rows: null params");
     IMD_REQUIRE_SIZE(p, "ddim_cfg_step_rows");

@@ -118,6 +118,8 @@ int imd_launch_image_overlay(const ImageOverlayParams& p, hipStream_t s);
 int imd_launch_image_inpaint_condition(const ImageInpaintConditionParams& p, hipStream_t s);
 int imd_launch_image_mask_filter(const ImageMaskFilterParams& p, hipStream_t s);      // image_filter.hip
 int imd_image_mask_filter_form_of(const ImageMaskFilterParams& p);                   // launches it would make, 0 = refused
+int imd_launch_image_mask_release(const imd_image_mask_release_params& p, hipStream_t s);      // soft_mask.hip
+int imd_launch_soft_mask_rows(const imd_soft_mask_rows_params& p, hipStream_t s);
 int imd_launch_timestep_embedding(const float* t, float* out, int B, int dim, hipStream_t s);
 int imd_launch_add(const bf16_t* a, int a_ld, const bf16_t* b, int b_ld, bf16_t* out, int out_ld, long rows, int C, float b_scale, int dtype, hipStream_t s);
 int imd_launch_embed_tokens(const bf16_t* table, int vocab, const bf16_t* pos, int T, const int64_t* ids, bf16_t* out, long rows, int C, int dtype, hipStream_t s);

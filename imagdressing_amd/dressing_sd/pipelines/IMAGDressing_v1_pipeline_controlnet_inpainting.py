@@ -50,6 +50,19 @@ def _mask_filter_requests(mask_dilate, mask_blur, R: int):
     return vals if any(k > 0 or b > 0.0 for k, b in vals) else None
 
 
+def _soft_mask_requests(soft_mask, R: int) -> Optional[List[bool]]:
+    """``soft_mask`` of a call, checked -> R bools, or None when every value is False (the call is then the one without the argument).
+    A list gives one value per request: any other length raises ValueError.  bool, ``numpy.bool_`` and the ints 0 / 1 are taken."""
+    import numpy as np
+    vals = list(soft_mask) if isinstance(soft_mask, (list, tuple)) else [soft_mask] * R
+    if len(vals) != R:
+        raise ValueError(f"soft_mask has {len(vals)} entries for {R} requests (give one value, or one per request)")
+    for v in vals:
+        if not isinstance(v, (bool, int, np.bool_)) or v not in (0, 1):
+            raise ValueError(f"soft_mask takes True or False, got {v!r}")
+    return [bool(v) for v in vals] if any(vals) else None
+
+
 class _InpaintImages:
     """The person image(s) and mask(s) of a call that crops (``padding_mask_crop``), composites (``overlay``) or builds the inpaint
     condition itself: pair j = (image j, mask j) of request j (one pair: shared), its crop box, and its inputs on either image route --
@@ -238,6 +251,37 @@ class IMAGDressing_v1(PipelineBase):
         from PIL import Image
         return StableDiffusionPipelineOutput(images=[Image.fromarray(a) for a in arrs], nsfw_content_detected=None)
 
+    def _mask_release(self, mask_image, front: Optional[_InpaintImages], ups, h: int, w: int, n: int) -> torch.Tensor:
+        """``soft_mask``: the release steps of every mask of the call, uint16 [masks, h, w] -- each mask read as "L" (filtered already
+        where ``mask_dilate`` / ``mask_blur`` were given), its crop box's window under ``padding_mask_crop`` and whole otherwise.  Host
+        route: ``mask_release_reference`` in numpy.  Device route: one ``imd_image_mask_release`` launch per mask on the uploaded bytes
+        (``ups``: the plain route's filtered uploads), the window a view."""
+        import numpy as np
+        from ...image import mask_as_l, mask_release_reference
+        if front is not None:                                 # (parsed, converted and -- device route -- uploaded there already)
+            on_device = front.on_device
+            count, boxes = len(front.masks), [front.boxes[j] if front.cropped else None for j in range(front.n)]
+        else:                                                 # the plain route: the hard mask goes through _image_tensor, which keeps no images
+            on_device = bool(getattr(self, "_device_image_io", False)) and torch.device(self.device).type == "cuda"
+            try:
+                masks = _pil_images(mask_image, "mask_image", None)
+            except ValueError as e:
+                raise ValueError(f"soft_mask reads mask_image as an 8-bit 'L' image: {e}") from None
+            count, boxes = len(masks), [None] * len(masks)
+        rows = []
+        for j in range(count):
+            if on_device:
+                proc = self._image_processor()
+                up = front.uploaded("mask_l", j) if front is not None else (ups[j] if ups is not None else proc._upload(masks[j], "L"))
+                rows.append(proc.mask_release(up, h, w, n, boxes[j]).view(torch.int16))
+            else:
+                a = mask_as_l(front.mask_l(j) if front is not None else masks[j])
+                if boxes[j] is not None:
+                    x1, y1, x2, y2 = boxes[j]
+                    a = a[y1:y2, x1:x2]
+                rows.append(torch.from_numpy(mask_release_reference(np.ascontiguousarray(a), h, w, n)).view(torch.int16))
+        return torch.stack(rows).view(torch.uint16)
+
     def open_session(self, *args, **kwargs):
         raise NotImplementedError("open_session on the inpainting pipeline: the per-row blend coefficients are in imd_sampler_step_rows, the per-slot mask / image-latent buffers are not built yet")
 
@@ -257,8 +301,19 @@ class IMAGDressing_v1(PipelineBase):
                  image_latents: Optional[torch.Tensor] = None, mask_latents: Optional[torch.Tensor] = None,
                  noise: Optional[torch.Tensor] = None, shard_over_ranks: bool = False, trace: Optional[list] = None,
                  mask_dilate: Union[int, List[int]] = 0, mask_blur: Union[float, List[float]] = 0.0,
-                 guidance_rescale: Union[float, List[float]] = 0.0, overlay: bool = False, **kwargs):
-        """``mask_dilate`` = k and ``mask_blur`` = b (one value, or a list with one per request; 0: the step is skipped) grow and feather
+                 soft_mask: Union[bool, List[bool]] = False, guidance_rescale: Union[float, List[float]] = 0.0,
+                 overlay: bool = False, **kwargs):
+        """``soft_mask`` (one bool, or a list with one per request; default False): the gray level of a mask pixel decides for how
+        many of the LAST steps it is free to be repainted (Differential Diffusion, Levin & Fried 2023) instead of the mask being
+        binarised at 0.5: the mask is read as "L" -- after ``mask_dilate`` / ``mask_blur``, inside the crop box of
+        ``padding_mask_crop`` -- and ``image.mask_release_reference`` (host route) or ``imd_image_mask_release`` (device route) turns it
+        into the release step of every latent pixel for the n = ``init_steps`` positions the call runs; ``mask_latents`` as a float
+        tensor in [0, 1] is taken as the levels themselves (the tensor is read, never written).  ``mask_image`` must be a PIL image
+        or a uint8 array (or a list of them) here, also on the plain route, where the hard mask takes a tensor too: gray levels are
+        read from 8-bit "L" pixels, and a tensor ``mask_image`` raises ValueError -- pass it as ``mask_latents``.  Every step still blends with a 0 / 1 mask, written by ONE
+        ``imd_soft_mask_rows`` launch in front of it; a request at False keeps its hard mask and its bits.
+
+        ``mask_dilate`` = k and ``mask_blur`` = b (one value, or a list with one per request; 0: the step is skipped) grow and feather
         the mask before ANY reader sees it -- the crop box, the binarised latent mask, the built-in inpaint condition, the overlay and
         the plain route with a caller's ``control_image``: the call equals, byte for byte, the same call given each mask as
         ``m.convert("L").filter(ImageFilter.MaxFilter(2 k + 1)).filter(ImageFilter.GaussianBlur(b))`` (always "L" first, also for an
@@ -278,6 +333,17 @@ class IMAGDressing_v1(PipelineBase):
         if guess_mode or min_guidance(guidance_scale) <= 1.0 or timesteps:
             raise NotImplementedError("guess_mode, guidance_scale <= 1 and custom timesteps are not implemented "
                                       "(the reference script uses none of them)")
+        soft_rows = _soft_mask_requests(soft_mask, R)
+        if soft_rows is not None:
+            if shard_over_ranks:
+                raise NotImplementedError("soft_mask with shard_over_ranks: the release steps are built for the rows of one rank")
+            if mask_image is None and mask_latents is None:
+                raise ValueError("soft_mask reads the gray levels of mask_image (or of a float mask_latents); neither was given")
+            if mask_latents is not None:
+                if not isinstance(mask_latents, torch.Tensor) or not mask_latents.is_floating_point() or mask_latents.dim() != 4:
+                    raise ValueError("soft_mask with mask_latents: a float [1 | R | B, 1, h, w] tensor of levels in [0, 1]")
+                if not bool(torch.isfinite(mask_latents).all()) or float(mask_latents.min()) < 0.0 or float(mask_latents.max()) > 1.0:
+                    raise ValueError("soft_mask: mask_latents must be finite and in [0, 1]")
         # mask_dilate / mask_blur: the host route swaps the filtered "L" masks in for mask_image here, before anything reads it; the
         # device route filters the uploaded masks (in _InpaintImages, or below for the plain route)
         mask_filter = _mask_filter_requests(mask_dilate, mask_blur, R)
@@ -365,6 +431,10 @@ class IMAGDressing_v1(PipelineBase):
             if il.shape[0] != B:                                              # one person image shared, or one per request (request-major rows)
                 il = il.expand(B, -1, -1, -1) if il.shape[0] == 1 else RequestLayout(R, num_images_per_prompt).expand(il, "image / image_latents")
             lat = self.scheduler.add_noise(il, noise.to(device=device, dtype=torch.float32), t0)
+        ups = release = None
+        if soft_rows is not None and mask_latents is not None:                # the caller's levels, [1 | R | B, 1, h, w] in [0, 1]
+            from ...image import release_of_levels
+            release = torch.from_numpy(release_of_levels(mask_latents[:, 0], init_steps))
         if mask_latents is None and front is not None and front.cropped:
             mask_latents = front.mask_latents(h, w)
         elif mask_latents is None and mask_filter is not None:                # (device route: the uploaded masks, filtered; then as below)
@@ -384,6 +454,10 @@ class IMAGDressing_v1(PipelineBase):
         lat, noise_s = self._shard(lat, shard_over_ranks), self._shard(noise.to(device), shard_over_ranks)
         sa = self._sa_states(ref_lat, cloth_tokens, shard_over_ranks, G)
         inpaint = dict(mask=mask_latents, image_latents=image_latents, noise=noise_s)
+        if soft_rows is not None:
+            if release is None:
+                release = self._mask_release(mask_image, front, ups, h, w, init_steps)
+            inpaint.update(release=release, soft_rows=soft_rows)
         out = self.denoise(latents=lat, prompt_embeds=prompt_embeds, negative_prompt_embeds=negative_prompt_embeds,
                            sa_hidden_states=sa, num_inference_steps=num_inference_steps, guidance_scale=guidance_scale,
                            control=control, inpaint=inpaint, callback=callback, callback_steps=callback_steps, trace=trace,

@@ -433,7 +433,11 @@ class PipelineBase:
 
         ``control`` = dict(image=[1|B, 3, H, W] in [0,1] or NHWC8 bf16, prompt_embeds=[1,77,768],
         negative_prompt_embeds=[1,77,768], scale=float, keep=[float]*steps)
-        ``inpaint`` = dict(mask=[B|1,1,h,w], image_latents=[B|1,4,h,w], noise=[B,4,h,w])
+        ``inpaint`` = dict(mask=[B|1,1,h,w], image_latents=[B|1,4,h,w], noise=[B,4,h,w]) and, for ``soft_mask``, optionally
+        ``release`` = integer [1|R|B, h, w] (``image.mask_release_reference``: the step from which a pixel is free) with ``soft_rows`` =
+        R bools (None: every request): ONE ``imd_soft_mask_rows`` launch in front of every step writes the 0 / 1 mask ``k >= release``
+        into the soft requests' rows of the mask buffer, k from a [calls][B] table uploaded once (:func:`soft_step_table`); a captured
+        step reads k from a fixed buffer refreshed next to the coefficients.  The hard requests' rows keep ``mask``.
         """
         dev = self.device
         B, Cl, h, w = latents.shape
@@ -500,6 +504,37 @@ class PipelineBase:
                        noise=nhwc(inpaint["noise"], Cl))
         if multistep and inp is not None:
             raise NotImplementedError("the inpainting blend is defined on the DDIM step (…inpainting.py:487-500)")       # (and on imd_sampler_step)
+        # soft_mask: the rows of the soft requests get their 0 / 1 mask from the release steps in front of every step; the mask buffer
+        # stays at its one address, the hard rows keep what was filled in above.  The step of every call is known before the first
+        # launch: one [calls][B] table for the whole call, -1 for a hard row.  No soft row: nothing is allocated, uploaded or launched.
+        soft = None
+        if inp is not None and inpaint.get("release") is not None:
+            flags = inpaint.get("soft_rows")
+            flags = [True] * lay.requests if flags is None else [bool(f) for f in flags]
+            if len(flags) != lay.requests:
+                raise ValueError(f"inpaint soft_rows has {len(flags)} entries for {lay.requests} requests")
+            if any(flags):
+                rel = torch.as_tensor(inpaint["release"])
+                if rel.is_floating_point() or rel.dtype == torch.bool or rel.dim() != 3 or tuple(rel.shape[1:]) != (h, w):
+                    raise ValueError(f"inpaint release: expected an integer [1 | R | B, {h}, {w}] tensor, got {rel.dtype} {tuple(rel.shape)}")
+                rel = rel.to(dev)
+                if rel.dtype == torch.uint16:          # (the bits, as int16: the type torch expands and repeats on every device)
+                    rel = rel.view(torch.int16)
+                else:
+                    rel = rel.to(torch.int64)
+                    lo, hi = int(rel.min()), int(rel.max())
+                    if lo < 0 or hi > ops.RELEASE_MAX_STEPS:
+                        raise ValueError(f"inpaint release: a release step is in [0, {ops.RELEASE_MAX_STEPS}], got values from {lo} to {hi}")
+                    rel = torch.where(rel >= 32768, rel - 65536, rel).to(torch.int16)
+                rel = lay.expand(rel, "inpaint release").reshape(B, HW).contiguous().view(torch.uint16)
+                # the launches write the mask at every step: the loop's buffer must not be the caller's tensor (an fp32 mask of B rows
+                # on the device passes through nhwc() without a copy)
+                inp["mask"] = inp["mask"].clone()
+                # executed schedule positions: PNDM's run makes one UNet call more than it has positions
+                positions = len(timesteps) - ((len(sch.timesteps) - int(num_inference_steps)) if fused else 0)
+                table = soft_step_table(timesteps, positions, [flags[lay.request_of_row(b)] for b in range(B)])
+                soft = dict(release=rel, table=torch.tensor(table, dtype=torch.int32).to(dev),
+                            step_dev=torch.full((B,), -1, dtype=torch.int32, device=dev))          # the captured step reads its steps here
         keep_in = None if control is None else control.get("keep", [1.0] * len(timesteps))
         # (PNDM calls the UNet once more than it has steps: the extra call keeps the last gate)
         keeps = None if control is None else [keep_in[min(i, len(keep_in) - 1) if fused else i] for i in range(len(timesteps))]
@@ -574,6 +609,8 @@ class PipelineBase:
                 kw = dict(mask=inp["mask"], z_img=inp["z_img"], blend_noise=inp["noise"])
             if noisy:
                 kw["noise"] = step_noise(i)
+            if soft is not None:
+                ops.soft_mask_rows(inp["mask"], soft["release"], soft["step_dev"] if i is None else soft["table"][i])
             (ops.unipc_step if unipc else ops.sampler_step)(z, eps, x_in.view(2 * B, HW, 8), guidance=g_arg, coefs=sampler_rows[i] if coefs is None else coefs, hist=hist, **kw)
 
         def ddim_step(t, i=None, coefs=None):
@@ -587,6 +624,8 @@ class PipelineBase:
             kw = {}
             if inp is not None:
                 kw = dict(mask=inp["mask"], z_img=inp["z_img"], noise=inp["noise"])
+            if soft is not None:
+                ops.soft_mask_rows(inp["mask"], soft["release"], soft["step_dev"] if i is None else soft["table"][i])
             if coefs is not None:
                 ops.ddim_cfg_step(z, eps, x_in.view(2 * B, HW, 8), guidance=g_arg, coefs=coefs, **kw)
             else:
@@ -639,6 +678,8 @@ class PipelineBase:
                         key_dev.copy_(key_table[0])
                     if ctrl_table is not None:
                         ctrl_dev.copy_(ctrl_table[0])
+                    if soft is not None:
+                        soft["step_dev"].copy_(soft["table"][0])
                     temb_bufs = [torch.empty_like(tab[0:1]) for tab in tables]     # fixed addresses inside the captured step, refreshed like t_dev
                     for e, buf, tab in zip(encs, temb_bufs, tables):
                         buf.copy_(tab[0:1])
@@ -656,6 +697,8 @@ class PipelineBase:
                             key_dev.copy_(key_table[i])
                         if ctrl_table is not None:
                             ctrl_dev.copy_(ctrl_table[i])
+                        if soft is not None:
+                            soft["step_dev"].copy_(soft["table"][i])
                         for buf, tab in zip(temb_bufs, tables):
                             buf.copy_(tab[i:i + 1])
                         g.replay()
@@ -887,6 +930,23 @@ def guidance_rescale_values(value, R: int) -> List[float]:
     return vals
 
 
+def soft_step_table(timesteps: Sequence, positions: int, soft_rows: Sequence[bool]) -> List[List[int]]:
+    """``soft_mask``: the step k of every UNet call of a run, per latent row -- [calls][B], -1 for a hard row.  ``timesteps``: the
+    executed calls; call i blends towards ``timesteps[i + 1]`` (the last call: towards the clean image latents), and k counts the
+    distinct positions aimed at so far, so PNDM's doubled first call holds k = 0 twice; ``positions`` = n caps k at n - 1, the blend
+    of the last position.  DDIM, DPM-Solver++, Euler and UniPC: k = i.  PNDM at ``strength`` < 1 from schedule position 2 or later is
+    the one case in which ``positions`` is FEWER than the distinct positions aimed at: the slice of its doubled timestep list then
+    holds no doubled entry, its n + 1 calls aim at n + 1 levels, and the table ends [.., n - 1, n - 1] -- the cap keeps a pixel whose
+    release is n the clean original."""
+    ks, k = [], 0
+    for i in range(len(timesteps)):
+        aim = timesteps[i + 1] if i + 1 < len(timesteps) else None
+        if i > 0 and aim != timesteps[i]:          # (timesteps[i] is what call i - 1 aimed at)
+            k += 1
+        ks.append(min(k, int(positions) - 1))
+    return [[k if s else -1 for s in soft_rows] for k in ks]
+
+
 def per_call_value(name: str, value):
     """Arguments folded into weights or shared by the schedule (steps, strength, eta, LoRA / IP-Adapter / ControlNet scales) stay per call:
     a sequence is accepted only if its entries agree."""
@@ -1060,6 +1120,6 @@ def set_scale_by_type(unet, cls, **attrs):
                 setattr(proc, k, v)
 
 
-__all__ = ["deepcache_plan", "RequestLayout", "request_count", "request_rows", "unipc_fused", "per_request_floats", "guidance_rescale_values", "per_call_value", "as_batch", "min_guidance", "entries",
+__all__ = ["deepcache_plan", "RequestLayout", "request_count", "request_rows", "unipc_fused", "per_request_floats", "guidance_rescale_values", "soft_step_table", "per_call_value", "as_batch", "min_guidance", "entries",
            "controlnet_keep", "control_plan", "control_request_values", "control_scale_table", "CONTROL_KEYS", "first", "to_image_tensor", "PipelineBase", "StableDiffusionPipelineOutput", "randn_tensor", "set_scale_by_type",
            "RefSAttnProcessor2_0", "LoraRefSAttnProcessor2_0", "LoRAIPAttnProcessor2_0", "IPAttnProcessor2_0"]

@@ -338,6 +338,55 @@ def mask_filter_host(mask, dilate: int = 0, blur: float = 0.0):
     return m
 
 
+def _pool_edges(n_in: int, n_out: int) -> Tuple[np.ndarray, np.ndarray]:
+    """the bins of torch's ``adaptive_avg_pool2d`` along one axis: output i covers [floor(i n_in / n_out), ceil((i + 1) n_in / n_out))"""
+    i = np.arange(n_out, dtype=np.int64)
+    return i * n_in // n_out, ((i + 1) * n_in + n_out - 1) // n_out
+
+
+def mask_release_reference(mask_u8: np.ndarray, h: int, w: int, n: int) -> np.ndarray:
+    """``soft_mask``: the "L" mask window ``mask_u8`` (uint8 [H0, W0]) -> uint16 [h, w], the step of a run of ``n`` schedule positions
+    from which each latent pixel is free to be repainted (Differential Diffusion, Levin & Fried 2023).  Latent pixel (y, x) covers the
+    ``adaptive_avg_pool2d`` bin of the window; S = the integer sum of its bytes, D = 255 cnt, c = S / D in [0, 1]:
+
+        release = n - ceil(c n) = n - (S n + D - 1) // D          (64-bit integers: exact)
+
+    so c = 1 gives 0 (repainted at every step), c = 0 gives n (ends as the clean original), and a pixel in between runs its last
+    ceil(c n) steps free.  The blend that aims at position k + 1 uses the 0 / 1 mask ``k >= release``.  This is the host route of the
+    inpainting pipeline and the oracle of ``DeviceImageProcessor.mask_release`` (``imd_image_mask_release``)."""
+    a = np.asarray(mask_u8)
+    h, w, n = int(h), int(w), int(n)
+    if a.dtype != np.uint8 or a.ndim != 2 or a.shape[0] < 1 or a.shape[1] < 1:
+        raise ValueError(f"mask_release: the mask window is a non-empty uint8 [H0, W0] array, got {a.dtype} {a.shape}")
+    if h < 1 or w < 1:
+        raise ValueError(f"mask_release: empty latent ({h} x {w})")
+    if not 1 <= n <= 65535:
+        raise ValueError(f"mask_release: n must be in [1, 65535], got {n}")
+    H0, W0 = a.shape
+    (y0, y1), (x0, x1) = _pool_edges(H0, h), _pool_edges(W0, w)
+    # prefix sums along the rows (a row of fewer than 2^24 bytes sums below 2^32), the bins' column ranges taken from them, then prefix
+    # sums of those [H0, w] column sums down the rows: ONE pass over the window
+    P = np.zeros((H0, W0 + 1), dtype=np.uint32 if W0 < (1 << 24) else np.int64)
+    np.cumsum(a, axis=1, dtype=P.dtype, out=P[:, 1:])
+    Q = np.zeros((H0 + 1, w), dtype=np.int64)
+    np.cumsum(P[:, x1].astype(np.int64) - P[:, x0].astype(np.int64), axis=0, out=Q[1:])
+    S = Q[y1] - Q[y0]
+    D = 255 * ((y1 - y0)[:, None] * (x1 - x0)[None, :])
+    return (n - (S * n + D - 1) // D).astype(np.uint16)
+
+
+def release_of_levels(levels, n: int) -> np.ndarray:
+    """``soft_mask`` with ``mask_latents=`` given as a float tensor: levels c in [0, 1] (any shape) -> uint16 release = n - ceil(c n),
+    in float64 from the fp32 values.  Non-finite values and values outside [0, 1] raise ValueError."""
+    c = (levels.detach().to("cpu", torch.float32).numpy() if isinstance(levels, torch.Tensor) else np.asarray(levels, dtype=np.float32)).astype(np.float64)
+    n = int(n)
+    if not 1 <= n <= 65535:
+        raise ValueError(f"mask_release: n must be in [1, 65535], got {n}")
+    if not np.isfinite(c).all() or (c < 0.0).any() or (c > 1.0).any():
+        raise ValueError("soft_mask: mask_latents must be finite and in [0, 1]")
+    return (n - np.ceil(c * n)).astype(np.uint16)
+
+
 def overlay_reference(orig: np.ndarray, gen: np.ndarray, mask: np.ndarray, box: Tuple[int, int, int, int]) -> np.ndarray:
     """``Image.composite`` in numpy: uint8 ``orig`` [..., H0, W0, 3], ``mask`` [..., H0, W0], ``gen`` [..., ch, cw, 3] already at the size
     of ``box`` = (x1, y1, x2, y2) -> ``orig`` outside the box, ((t >> 8) + t) >> 8 with t = orig (255 - m) + gen m + 128 inside."""
@@ -505,6 +554,21 @@ class DeviceImageProcessor:
             return res[0].unsqueeze(-1), res[1]
         return res.unsqueeze(-1)
 
+    def mask_release(self, mask_u8, h: int, w: int, n: int, box: Optional[Tuple[int, int, int, int]] = None) -> torch.Tensor:
+        """``mask_release_reference`` on the device (``imd_image_mask_release``): ``mask_u8`` ("L": PIL / uint8 [H0, W0] or an uploaded
+        [1, H0, W0, 1] tensor), its window ``box`` = (x1, y1, x2, y2) (None: the whole mask; the window is a view, nothing is copied)
+        -> uint16 [h, w] on the device, the release step of every latent pixel for a run of ``n`` schedule positions."""
+        if not isinstance(mask_u8, torch.Tensor) and not _is_pil(mask_u8):
+            mask_u8 = mask_as_l(mask_u8)
+        m = self._upload(mask_u8, "L")
+        if m.shape[0] != 1:
+            raise ValueError(f"mask_release: one mask per call, got {tuple(m.shape)}")
+        src = m[0, :, :, 0]
+        if box is not None:
+            x1, y1, x2, y2 = (int(v) for v in box)
+            src = src[y1:y2, x1:x2]
+        return ops.mask_release(src, h, w, n)
+
     # ---- output ----
     def overlay(self, decoded: torch.Tensor, orig, mask, box: Tuple[int, int, int, int], out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """``overlay_host`` on the device: uint8 ``decoded`` [B, H, W, 3] (``pack``) resized to ``box`` = (x1, y1, x2, y2) with Lanczos and
@@ -564,4 +628,4 @@ class MaskProcessor:
 __all__ = ["resample_tables", "resample_reference", "tile_rows", "device_tables", "resize_to", "DeviceImageProcessor", "CLIP_MEAN", "CLIP_STD",
            "get_crop_region", "crop_region_of_bounds", "mask_as_l", "overlay_reference", "overlay_host", "inpaint_condition_host",
            "gaussian_box", "blur_reference", "dilate_reference", "mask_filter_host", "mask_filter_values", "MaskProcessor", "GAUSSIAN_PASSES",
-           "PILLOW_PINNED"]
+           "PILLOW_PINNED", "mask_release_reference", "release_of_levels"]

@@ -1789,6 +1789,60 @@ def image_mask_filter(src: torch.Tensor, dilate: int = 0, box: Optional[Tuple[in
     return (out, bnd) if bounds else out
 
 
+# ---- soft_mask: gray mask levels as per-pixel repaint depth (csrc/soft_mask.hip) ----
+SOFT_MASK_COUNTER = {"mask_release": 0, "soft_mask_rows": 0}          # calls made (tests, tools/soft_mask_bench.py)
+RELEASE_MAX_STEPS = 65535                                             # a release step is a uint16
+
+
+def mask_release(src: torch.Tensor, h: int, w: int, n: int, *, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """uint8 "L" mask window ``src`` [H0, W0] on the device (rows may be strided: a crop window is a view) -> uint16 [h, w], the
+    release step of every latent pixel for a run of ``n`` schedule positions (``imd_image_mask_release``): with S the integer sum of
+    the pixel's ``adaptive_avg_pool2d`` bin and D = 255 cnt, n - ceil(S n / D) -- ``image.mask_release_reference``, bit for bit."""
+    if not isinstance(src, torch.Tensor) or not src.is_cuda:
+        raise L.ImdError(f"src: tensor is on {getattr(src, 'device', type(src))}; imagdressing_amd runs on MI355X only (no CPU path)")
+    if src.dtype != torch.uint8 or src.dim() != 2 or (src.shape[1] > 1 and src.stride(1) != 1):
+        raise L.ImdError(f"src: expected uint8 [H0, W0] with contiguous rows, got {src.dtype} {tuple(src.shape)} strides {src.stride()}")
+    ensure_device(src.device)
+    h, w = int(h), int(w)
+    if out is None:
+        out = torch.empty(max(h, 0), max(w, 0), dtype=torch.uint16, device=src.device)
+    elif (not isinstance(out, torch.Tensor) or out.dtype != torch.uint16 or out.device != src.device or out.numel() != h * w
+          or not out.is_contiguous()):
+        raise L.ImdError(f"out: expected contiguous uint16 of {h * w} values on {src.device}, got {getattr(out, 'dtype', None)} "
+                         f"{tuple(getattr(out, 'shape', ()))}")
+    p = L.ImageMaskReleaseParams()
+    p.src, p.src_row_stride, p.out = src.data_ptr(), src.stride(0), out.data_ptr()
+    p.H0, p.W0, p.h, p.w, p.n = int(src.shape[0]), int(src.shape[1]), h, w, int(n)
+    L.check(L.load().imd_image_mask_release(C.byref(p), _stream()))
+    SOFT_MASK_COUNTER["mask_release"] += 1
+    return out
+
+
+def soft_mask_rows(mask: torch.Tensor, release: torch.Tensor, step_rows: torch.Tensor) -> torch.Tensor:
+    """The 0 / 1 blend mask of one step in one launch (``imd_soft_mask_rows``): ``mask`` [B, HW] fp32, ``release`` [B, HW] uint16 and
+    ``step_rows`` [B] int32, all contiguous on the device.  Row r with ``step_rows[r]`` >= 0 receives
+    ``(step_rows[r] >= release[r]) ? 1 : 0``; a row with a negative entry keeps its bytes (a hard-mask request of the batch)."""
+    if not isinstance(mask, torch.Tensor) or mask.dim() != 2:
+        raise L.ImdError(f"soft_mask_rows: mask {tuple(getattr(mask, 'shape', ()))}: expected [B, HW]")
+    ensure_device(mask.device)
+    B, HW = int(mask.shape[0]), int(mask.shape[1])
+    if (not isinstance(release, torch.Tensor) or release.dtype != torch.uint16 or tuple(release.shape) != (B, HW) or not release.is_contiguous()
+            or release.device != mask.device):
+        raise L.ImdError(f"soft_mask_rows: release must be a contiguous device uint16 tensor [{B}, {HW}], got "
+                         f"{getattr(release, 'dtype', type(release))} {tuple(getattr(release, 'shape', ()))}")
+    if (not isinstance(step_rows, torch.Tensor) or step_rows.dtype != torch.int32 or step_rows.numel() != B or not step_rows.is_contiguous()):
+        raise L.ImdError(f"soft_mask_rows: step_rows must be a contiguous device int32 tensor [{B}], got "
+                         f"{getattr(step_rows, 'dtype', type(step_rows))} {tuple(getattr(step_rows, 'shape', ()))}")
+    p = L.SoftMaskRowsParams()
+    p.mask = _dev(mask, torch.float32, "mask")
+    p.release = release.data_ptr()
+    p.step_rows = _dev(step_rows, torch.int32, "step_rows")
+    p.B, p.HW = B, HW
+    L.check(L.load().imd_soft_mask_rows(C.byref(p), _stream()))
+    SOFT_MASK_COUNTER["soft_mask_rows"] += 1
+    return mask
+
+
 def timestep_embedding(t: torch.Tensor, dim: int) -> torch.Tensor:
     ensure_device(t.device)
     out = torch.empty((t.shape[0], dim), dtype=torch.float32, device=t.device)

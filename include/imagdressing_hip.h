@@ -391,6 +391,34 @@ typedef struct imd_noise_params {
     int rows, HW, kind;
 } imd_noise_params;
 
+/* soft_mask (imd_image_mask_release, imd_soft_mask_rows): the gray level of an inpainting mask as per-pixel repaint depth --
+ * Differential Diffusion (Levin & Fried, 2023).  A call runs n schedule positions k = 0 .. n - 1.  Latent pixel (y, x) of an h x w
+ * latent covers, on the H0 x W0 mask window, the bin of torch's adaptive_avg_pool2d: rows [floor(y H0 / h), ceil((y + 1) H0 / h)),
+ * columns [floor(x W0 / w), ceil((x + 1) W0 / w)).  With S the integer sum of the bin's bytes and D = 255 cnt,
+ *   release = n - ceil(S n / D) = n - (S n + D - 1) / D          (64-bit integers; 0 for an all-255 bin, n for an all-0 bin)
+ * and the blend that aims at position k + 1 uses the 0 / 1 mask [k >= release]: the pixel is reset to the re-noised original up to
+ * the blend that aims at position `release` and runs its last n - release = ceil(c n) steps free. */
+typedef struct imd_image_mask_release_params {
+    uint32_t struct_bytes;  /* sizeof(imd_image_mask_release_params) in the caller's view; checked on entry */
+    const uint8_t* src;     /* DEVICE "L" mask window [H0][W0], row y at src + y * src_row_stride (a crop window is a view) */
+    int64_t src_row_stride; /* bytes, >= W0 */
+    uint16_t* out;          /* DEVICE [h * w] release steps, each in [0, n] */
+    int H0, W0, h, w;
+    int n;                  /* executed schedule positions, in [1, 65535] */
+} imd_image_mask_release_params;
+
+/* The 0 / 1 blend mask of one step from the release steps: for every row r with step_rows[r] >= 0,
+ *   mask[r][p] = step_rows[r] >= release[r][p] ? 1.0f : 0.0f
+ * A row with a negative entry is neither read nor written.  The launch goes in front of any step entry point that takes `mask`
+ * (fp32 [B][HW] at a fixed address), none of which changes. */
+typedef struct imd_soft_mask_rows_params {
+    uint32_t struct_bytes;    /* sizeof(imd_soft_mask_rows_params) in the caller's view; checked on entry */
+    const uint16_t* release;  /* DEVICE [B][HW], 8-byte aligned */
+    const int32_t* step_rows; /* DEVICE [B]: the step k of the row, negative = leave the row alone */
+    float* mask;              /* DEVICE [B][HW] fp32, 16-byte aligned */
+    int B, HW;
+} imd_soft_mask_rows_params;
+
 /* Per-row LoRA with the low-rank path unfolded (imd_lora_expand_rows).  For a linear layer with LoRA,
  *   y = x W^T + s_row ((x D^T) U^T) = [x | s_row (x D^T)] [W | U]^T
  * so a scale that differs from row to row goes into the ACTIVATIONS and the augmented weight [W | U] (network_alpha / rank folded into
@@ -811,6 +839,14 @@ int imd_image_inpaint_condition(const imd_image_inpaint_condition_params* p, voi
  * imd_image_mask_filter_form: the number of launches imd_image_mask_filter would make for *p, 0 when it would refuse. */
 int imd_image_mask_filter(const imd_image_mask_filter_params* p, void* stream);
 int imd_image_mask_filter_form(const imd_image_mask_filter_params* p);
+/* uint8 "L" mask window -> the uint16 release step of every latent pixel for a run of n positions, one wave per latent pixel; see
+ * imd_image_mask_release_params.  Errors without launching: null params, a foreign struct_bytes, src or out NULL, h, w, H0 or W0 < 1,
+ * src_row_stride < W0, n outside [1, 65535], out not 2-byte aligned, a window of 2^31 bytes or a latent of 2^30 pixels or more. */
+int imd_image_mask_release(const imd_image_mask_release_params* p, void* stream);
+/* The 0 / 1 blend mask of the rows that ask for it, as ONE launch in front of a step (grid (pixels, rows), four pixels per thread);
+ * see imd_soft_mask_rows_params.  Errors without launching: null params, a foreign struct_bytes, release, step_rows or mask NULL,
+ * release not 8-byte, step_rows not 4-byte or mask not 16-byte aligned, B < 1 (or more than 65535), HW < 1. */
+int imd_soft_mask_rows(const imd_soft_mask_rows_params* p, void* stream);
 
 /* diffusers Timesteps(dim, flip_sin_to_cos=True, freq_shift=0): out[B, dim] fp32 = [cos | sin]. */
 int imd_timestep_embedding(const float* t, float* out, int B, int dim, void* stream);
