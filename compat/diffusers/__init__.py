@@ -19,11 +19,11 @@ import os as _os
 
 from imagdressing_amd.scheduler import (DDIMScheduler, DPMSolverMultistepScheduler, EulerAncestralDiscreteScheduler,  # noqa: F401
                                         EulerDiscreteScheduler, PNDMScheduler, UniPCMultistepScheduler)
-from imagdressing_amd.unet import ControlNetModel, UNet2DConditionModel  # noqa: F401
+from imagdressing_amd.unet import ControlNetModel, MultiControlNetModel, UNet2DConditionModel  # noqa: F401
 from imagdressing_amd.vae import AutoencoderKL  # noqa: F401
 
 __version__ = "0.24.0+imagdressing_amd"
-__all__ = ["UNet2DConditionModel", "ControlNetModel", "AutoencoderKL", "DDIMScheduler", "UniPCMultistepScheduler",
+__all__ = ["UNet2DConditionModel", "ControlNetModel", "MultiControlNetModel", "AutoencoderKL", "DDIMScheduler", "UniPCMultistepScheduler",
            "DPMSolverMultistepScheduler", "EulerDiscreteScheduler", "EulerAncestralDiscreteScheduler", "PNDMScheduler"]
 
 

@@ -163,6 +163,16 @@ class ScaleRowsParams(_Sized):
                 ("data", C.c_void_p * SCALE_ROWS_MAX_SEGMENTS), ("row_elems", C.c_int * SCALE_ROWS_MAX_SEGMENTS)]
 
 
+MIX_ROWS_MAX_SOURCES = 4             # IMD_MIX_ROWS_MAX_SOURCES
+MIX_ROWS_MAX_SEGMENTS = 16           # IMD_MIX_ROWS_MAX_SEGMENTS
+
+
+class MixRowsParams(_Sized):
+    _fields_ = [("struct_bytes", C.c_uint32), ("dtype", C.c_int), ("rows", C.c_int), ("segments", C.c_int), ("sources", C.c_int),
+                ("scales", C.c_void_p), ("src", (C.c_void_p * MIX_ROWS_MAX_SEGMENTS) * MIX_ROWS_MAX_SOURCES),
+                ("dst", C.c_void_p * MIX_ROWS_MAX_SEGMENTS), ("row_elems", C.c_int * MIX_ROWS_MAX_SEGMENTS)]
+
+
 class ImageResampleParams(_Sized):
     _fields_ = [("struct_bytes", C.c_uint32),
         ("src", C.c_void_p), ("src_row_stride", C.c_int64), ("src_img_stride", C.c_int64), ("out", C.c_void_p), ("tmp", C.c_void_p),
@@ -258,6 +268,7 @@ SYMBOLS = {
     "imd_noise_rows": (C.c_int, [C.POINTER(NoiseParams), C.c_void_p]),
     "imd_lora_expand_rows": (C.c_int, [C.POINTER(LoraRowsParams), C.c_void_p]),
     "imd_residual_scale_rows": (C.c_int, [C.POINTER(ScaleRowsParams), C.c_void_p]),
+    "imd_residual_mix_rows": (C.c_int, [C.POINTER(MixRowsParams), C.c_void_p]),
     "imd_session_input_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "imd_image_resample": (C.c_int, [C.POINTER(ImageResampleParams), C.c_void_p]),
     "imd_image_resample_form": (C.c_int, [C.POINTER(ImageResampleParams)]),

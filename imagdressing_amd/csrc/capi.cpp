@@ -366,6 +366,48 @@ int imd_residual_scale_rows(const imd_scale_rows_params* p, void* stream) {
     return imd_launch_residual_scale_rows(*p, (hipStream_t)stream);
 }
 
+int imd_residual_mix_rows(const imd_mix_rows_params* p, void* stream) {
+    const char* n = "residual_mix_rows";
+    IMD_REQUIRE(p != nullptr, "%s: null params", n);
+    IMD_REQUIRE_SIZE(p, n);
+    IMD_REQUIRE(p->dtype == IMD_DTYPE_BF16 || p->dtype == IMD_DTYPE_F16, "%s: unknown dtype %d", n, p->dtype);
+    IMD_REQUIRE(p->sources >= 1 && p->sources <= IMD_MIX_ROWS_MAX_SOURCES, "%s: sources (%d) outside 1..%d", n, p->sources,
+                IMD_MIX_ROWS_MAX_SOURCES);
+    IMD_REQUIRE(p->segments >= 1 && p->segments <= IMD_MIX_ROWS_MAX_SEGMENTS, "%s: segments (%d) outside 1..%d", n, p->segments,
+                IMD_MIX_ROWS_MAX_SEGMENTS);
+    IMD_REQUIRE(p->rows >= 1, "%s: rows (%d) must be at least 1", n, p->rows);
+    IMD_REQUIRE(p->scales != nullptr, "%s: null scales", n);
+    IMD_REQUIRE(((uintptr_t)p->scales & 3) == 0, "%s: scales must be 4-byte aligned", n);
+    unsigned long long chunks = 0;
+    for (int j = 0; j < p->segments; ++j) {
+        IMD_REQUIRE(p->row_elems[j] > 0 && p->row_elems[j] % 8 == 0, "%s: row_elems[%d] (%d) must be a positive multiple of 8", n, j,
+                    p->row_elems[j]);
+        IMD_REQUIRE(p->dst[j] != nullptr, "%s: null dst[%d]", n, j);
+        IMD_REQUIRE(((uintptr_t)p->dst[j] & 15) == 0, "%s: dst[%d] must be 16-byte aligned", n, j);
+        for (int k = 0; k < p->sources; ++k) {
+            IMD_REQUIRE(p->src[k][j] != nullptr, "%s: null src[%d][%d]", n, k, j);
+            IMD_REQUIRE(((uintptr_t)p->src[k][j] & 15) == 0, "%s: src[%d][%d] must be 16-byte aligned", n, k, j);
+        }
+        chunks += (unsigned long long)p->rows * (unsigned long long)((p->row_elems[j] / 8 + 1023) / 1024);
+        IMD_REQUIRE(chunks < 0x80000000ull, "%s: operand too large (2^31 chunks of 16 KiB or more)", n);
+    }
+    // a dst segment may BE the same segment of a source (in place); every other overlap would let one thread's store reach another's load
+    for (int j = 0; j < p->segments; ++j) {
+        const uintptr_t d0 = (uintptr_t)p->dst[j], d1 = d0 + (uintptr_t)p->rows * (uintptr_t)p->row_elems[j] * 2;
+        for (int i = 0; i < p->segments; ++i) {
+            const uintptr_t bytes = (uintptr_t)p->rows * (uintptr_t)p->row_elems[i] * 2;
+            for (int k = 0; k < p->sources; ++k) {
+                const uintptr_t s0 = (uintptr_t)p->src[k][i];
+                IMD_REQUIRE((i == j && s0 == d0) || s0 >= d1 || s0 + bytes <= d0,
+                            "%s: dst[%d] overlaps src[%d][%d] (in place means dst[j] == src[k][j], nothing else)", n, j, k, i);
+            }
+            const uintptr_t e0 = (uintptr_t)p->dst[i];
+            IMD_REQUIRE(i == j || e0 >= d1 || e0 + bytes <= d0, "%s: dst[%d] overlaps dst[%d]", n, j, i);
+        }
+    }
+    return imd_launch_residual_mix_rows(*p, (hipStream_t)stream);
+}
+
 int imd_session_input_rows(const float* z, const int* row_slot, const float* in_scale_rows, void* x_in, int B, int slots, int HW,
                            int dtype_code, void* stream) {
     return imd_launch_session_input_rows(z, row_slot, in_scale_rows, (bf16_t*)x_in, B, slots, HW, dtype_code, (hipStream_t)stream);

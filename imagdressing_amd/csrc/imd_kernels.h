@@ -109,6 +109,7 @@ int imd_launch_guidance_rescale(const imd_guidance_rescale_params& p, hipStream_
 int imd_launch_noise_rows(const imd_noise_params& p, hipStream_t s);                                 // noise.hip
 int imd_launch_lora_expand_rows(const LoraRowsParams& p, hipStream_t s);                              // lora_rows.hip
 int imd_launch_residual_scale_rows(const imd_scale_rows_params& p, hipStream_t s);                    // residual_scale_rows.hip
+int imd_launch_residual_mix_rows(const imd_mix_rows_params& p, hipStream_t s);                        // residual_mix_rows.hip
 int imd_launch_session_input_rows(const float* z, const int* row_slot, const float* in_scale_rows, bf16_t* x_in, int B, int slots, int HW,
                                   int dtype, hipStream_t s);
 int imd_launch_image_resample(const ImageResampleParams& p, hipStream_t s);          // image.hip

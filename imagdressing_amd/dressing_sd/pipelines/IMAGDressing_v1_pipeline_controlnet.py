@@ -6,7 +6,7 @@ from typing import Any, Callable, Dict, List, Optional, Union
 
 import torch
 
-from ._base import PipelineBase, RefSAttnProcessor2_0, as_batch, min_guidance, per_call_value, set_scale_by_type
+from ._base import PipelineBase, RefSAttnProcessor2_0, as_batch, min_guidance, multi_control_images, per_call_value, set_scale_by_type
 
 
 class IMAGDressing_v1(PipelineBase):
@@ -32,6 +32,17 @@ class IMAGDressing_v1(PipelineBase):
         return dict(image=image, hw=hw, prompt_embeds=prompt_embeds,
                     negative_prompt_embeds=negative_prompt_embeds, scale=scale, keep=keep, rows=rows)
 
+    def _controls(self, K, pose_image, prompt_embeds, negative_prompt_embeds, num_inference_steps, scale, start, end, device, size=None, requests=1):
+        """``_control`` for K >= 2 nets: ``pose_image`` holds one entry per net; ``multi_rows[k][r][i]`` is the effective scale of net k
+        for request r at step i (the mix route, whatever the values)."""
+        tensors = [self._image_tensor(as_batch(im, "pose_image"), device, normalize=False, size=size, multiple=self.vae_scale_factor,
+                                      layout="nhwc8") for im in multi_control_images("pose_image", pose_image, K, requests)]
+        if len({hw for _, hw in tensors}) > 1:
+            raise ValueError(f"pose_image: the images of the {K} ControlNets differ in size ({[hw for _, hw in tensors]}) after resizing")
+        rows = self._multi_control_plan(scale, start, end, K, requests, num_inference_steps)
+        return dict(image=[t for t, _ in tensors], hw=tensors[0][1], prompt_embeds=prompt_embeds,
+                    negative_prompt_embeds=negative_prompt_embeds, scale=1.0, multi_rows=rows)
+
     def open_session(self, slots: int, width: int, height: int, controlnet_conditioning_scale: float = 1.0, compact: bool = False, widths=None,
                      device_noise: Optional[bool] = None, control_rows: Optional[bool] = None):
         """In-flight batching: a :class:`imagdressing_amd.session.DenoiseSession` with ``slots`` slots at ``width`` x ``height``; every
@@ -56,15 +67,17 @@ class IMAGDressing_v1(PipelineBase):
                  ref_clip_hidden_states: Optional[torch.Tensor] = None, ref_image_latents: Optional[torch.Tensor] = None,
                  latents: Optional[torch.Tensor] = None, shard_over_ranks: bool = False, trace: Optional[list] = None,
                  guidance_rescale: Union[float, List[float]] = 0.0, **kwargs):
+        K = self._multi_control("pose_image", pose_image, shard_over_ranks)          # >= 2: per-net lists, checked in _controls
         R = self._request_count(dict(prompt=prompt, prompt_embeds=prompt_embeds, negative_prompt=negative_prompt, null_prompt=null_prompt,
                                      negative_prompt_embeds=negative_prompt_embeds, ref_image=ref_image, ref_clip_image=ref_clip_image,
                                      ref_clip_hidden_states=ref_clip_hidden_states, ref_image_latents=ref_image_latents,
-                                     pose_image=pose_image, guidance_scale=guidance_scale, image_scale=image_scale,
+                                     pose_image=None if K else pose_image, guidance_scale=guidance_scale, image_scale=image_scale,
                                      guidance_rescale=guidance_rescale),
-                                dict(num_inference_steps=num_inference_steps, eta=eta, controlnet_conditioning_scale=controlnet_conditioning_scale),
+                                dict(dict(num_inference_steps=num_inference_steps, eta=eta),
+                                     **({} if K else dict(controlnet_conditioning_scale=controlnet_conditioning_scale))),
                                 shard_over_ranks,
-                                control=dict(controlnet_conditioning_scale=controlnet_conditioning_scale,
-                                             control_guidance_start=control_guidance_start, control_guidance_end=control_guidance_end))
+                                control=None if K else dict(controlnet_conditioning_scale=controlnet_conditioning_scale,
+                                                            control_guidance_start=control_guidance_start, control_guidance_end=control_guidance_end))
         num_inference_steps, eta = per_call_value("num_inference_steps", num_inference_steps), per_call_value("eta", eta)
         if guess_mode or min_guidance(guidance_scale) <= 1.0:
             # neither runs in the reference: with guess_mode its ControlNet sees the cond half only and the loop then indexes
@@ -80,9 +93,14 @@ class IMAGDressing_v1(PipelineBase):
             R, prompt, negative_prompt, prompt_embeds, negative_prompt_embeds, device, clip_skip)
         ref_lat, cloth_tokens, G = self._request_garments(R, null_prompt, ref_image, ref_image_latents, ref_clip_image,
                                                           ref_clip_hidden_states, device)
-        control = self._control(as_batch(pose_image, "pose_image"), prompt_embeds, negative_prompt_embeds, num_inference_steps,
-                                controlnet_conditioning_scale, control_guidance_start, control_guidance_end, device,
-                                size=(height, width), requests=R)
+        if K:
+            control = self._controls(K, pose_image, prompt_embeds, negative_prompt_embeds, num_inference_steps,
+                                     controlnet_conditioning_scale, control_guidance_start, control_guidance_end, device,
+                                     size=(height, width), requests=R)
+        else:
+            control = self._control(as_batch(pose_image, "pose_image"), prompt_embeds, negative_prompt_embeds, num_inference_steps,
+                                    controlnet_conditioning_scale, control_guidance_start, control_guidance_end, device,
+                                    size=(height, width), requests=R)
         if control is not None:
             height, width = control["hw"]                                   # :501
         self.scheduler.set_timesteps(num_inference_steps, device=device)      # (init_noise_sigma may depend on the schedule; IMAGDressing_v1_pipeline.py:386)

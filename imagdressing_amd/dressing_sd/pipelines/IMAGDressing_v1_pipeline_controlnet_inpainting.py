@@ -8,7 +8,7 @@ import torch
 
 from ...unet import nchw_to_nhwc8
 from ._base import (PipelineBase, RefSAttnProcessor2_0, RequestLayout, StableDiffusionPipelineOutput, as_batch,
-                    min_guidance, per_call_value, randn_tensor, set_scale_by_type, to_image_tensor, unipc_fused)
+                    min_guidance, multi_control_images, per_call_value, randn_tensor, set_scale_by_type, to_image_tensor, unipc_fused)
 
 
 def _pil_images(value, name: str, mode: Optional[str]) -> list:
@@ -318,16 +318,20 @@ class IMAGDressing_v1(PipelineBase):
         the plain route with a caller's ``control_image``: the call equals, byte for byte, the same call given each mask as
         ``m.convert("L").filter(ImageFilter.MaxFilter(2 k + 1)).filter(ImageFilter.GaussianBlur(b))`` (always "L" first, also for an
         RGB mask).  Host route: those Pillow calls.  ``enable_device_image_io()``: ``imd_image_mask_filter`` on the uploaded mask."""
+        # several nets: control_image holds one entry per net (at most one None: the condition built here), checked below
+        K = self._multi_control("control_image", control_image if control_image is not None else (), shard_over_ranks)
         R = self._request_count(dict(prompt=prompt, prompt_embeds=prompt_embeds, negative_prompt=negative_prompt, null_prompt=null_prompt,
                                      negative_prompt_embeds=negative_prompt_embeds, ref_image=ref_image, ref_clip_image=ref_clip_image,
                                      ref_clip_hidden_states=ref_clip_hidden_states, ref_image_latents=ref_image_latents,
-                                     control_image=control_image, image=image, mask_image=mask_image, image_latents=image_latents,
+                                     control_image=None if K else control_image, image=image, mask_image=mask_image, image_latents=image_latents,
                                      mask_latents=mask_latents, guidance_scale=guidance_scale, image_scale=image_scale,
                                      guidance_rescale=guidance_rescale),
-                                dict(num_inference_steps=num_inference_steps, strength=strength, eta=eta,
-                                     controlnet_conditioning_scale=controlnet_conditioning_scale), shard_over_ranks,
-                                control=dict(controlnet_conditioning_scale=controlnet_conditioning_scale,
-                                             control_guidance_start=control_guidance_start, control_guidance_end=control_guidance_end))
+                                dict(dict(num_inference_steps=num_inference_steps, strength=strength, eta=eta),
+                                     **({} if K else dict(controlnet_conditioning_scale=controlnet_conditioning_scale))), shard_over_ranks,
+                                control=None if K else dict(controlnet_conditioning_scale=controlnet_conditioning_scale,
+                                                            control_guidance_start=control_guidance_start, control_guidance_end=control_guidance_end))
+        control_images = multi_control_images("control_image", control_image, K, R, allow_none=1) if K else [control_image]
+        builtin_condition = any(e is None for e in control_images)
         num_inference_steps, strength, eta = (per_call_value("num_inference_steps", num_inference_steps), per_call_value("strength", strength),
                                               per_call_value("eta", eta))
         if guess_mode or min_guidance(guidance_scale) <= 1.0 or timesteps:
@@ -364,7 +368,7 @@ class IMAGDressing_v1(PipelineBase):
                 mask_image, mask_filter = (done if len(done) > 1 else done[0]), None
         # padding_mask_crop / overlay / control_image=None (the condition built here): the image and mask as images, one box per request
         front = None
-        if padding_mask_crop is not None or overlay or (control_image is None and image is not None and mask_image is not None):
+        if padding_mask_crop is not None or overlay or (builtin_condition and image is not None and mask_image is not None):
             if padding_mask_crop is not None and (image_latents is not None or mask_latents is not None):
                 raise ValueError("padding_mask_crop crops image and mask_image; image_latents / mask_latents cannot be cropped")
             if overlay and output_type not in ("pil", "np"):
@@ -389,17 +393,24 @@ class IMAGDressing_v1(PipelineBase):
         ref_lat, cloth_tokens, G = self._request_garments(R, null_prompt, ref_image, ref_image_latents, ref_clip_image,
                                                           ref_clip_hidden_states, device)
         steps_run = min(int(num_inference_steps * float(strength)), num_inference_steps)          # the gate is over the timesteps actually run (:376-381)
-        if front is not None and (front.cropped or control_image is None):
-            control_tensor = front.control(control_image, self.vae_scale_factor)
+        control_tensors = []
+        for entry in control_images:
+            if front is not None and (front.cropped or entry is None):
+                control_tensors.append(front.control(entry, self.vae_scale_factor))
+            else:
+                control_tensors.append(self._image_tensor(as_batch(entry, "control_image"), device, normalize=False, size=(height, width),
+                                                          multiple=self.vae_scale_factor, layout="nhwc8")[0])
+        if K:          # the mix route: ``multi_rows[k][r][i]``, the effective scale of net k for request r at every step that runs
+            control = dict(image=control_tensors, prompt_embeds=prompt_embeds, negative_prompt_embeds=negative_prompt_embeds, scale=1.0,
+                           multi_rows=self._multi_control_plan(controlnet_conditioning_scale, control_guidance_start, control_guidance_end,
+                                                               K, R, max(steps_run, 1)))
         else:
-            control_tensor = self._image_tensor(as_batch(control_image, "control_image"), device, normalize=False, size=(height, width),
-                                                multiple=self.vae_scale_factor, layout="nhwc8")[0]
-        # (enable_request_control_scales and differing triples: ``rows``, the effective scale of every request at every step that runs)
-        ctrl_scale, ctrl_keep, ctrl_rows = self._control_plan(controlnet_conditioning_scale, control_guidance_start, control_guidance_end,
-                                                              R, max(steps_run, 1))
-        control = dict(image=control_tensor,
-                       prompt_embeds=prompt_embeds,
-                       negative_prompt_embeds=negative_prompt_embeds, scale=ctrl_scale, keep=ctrl_keep, rows=ctrl_rows)
+            # (enable_request_control_scales and differing triples: ``rows``, the effective scale of every request at every step that runs)
+            ctrl_scale, ctrl_keep, ctrl_rows = self._control_plan(controlnet_conditioning_scale, control_guidance_start, control_guidance_end,
+                                                                  R, max(steps_run, 1))
+            control = dict(image=control_tensors[0],
+                           prompt_embeds=prompt_embeds,
+                           negative_prompt_embeds=negative_prompt_embeds, scale=ctrl_scale, keep=ctrl_keep, rows=ctrl_rows)
         B = R * num_images_per_prompt
         h, w = height // self.vae_scale_factor, width // self.vae_scale_factor
         # strength == 1.0: start from pure noise; the SAME noise re-noises the original latents in the blend (:496-498).

@@ -9,7 +9,7 @@ import torch
 
 from ...adapter.resampler import ProjPlusModel
 from ._base import (IPAttnProcessor2_0, LoRAIPAttnProcessor2_0, LoraRefSAttnProcessor2_0, PipelineBase, as_batch,
-                    min_guidance, per_call_value, request_rows, set_scale_by_type)
+                    min_guidance, multi_control_images, per_call_value, request_rows, set_scale_by_type)
 
 
 def _faces(name, value):
@@ -99,17 +99,19 @@ class IMAGDressing_v1(PipelineBase):
                  guidance_rescale: Union[float, List[float]] = 0.0, **kwargs):
         rows_on = bool(getattr(self, "_request_adapter_scales", False))          # enable_request_adapter_scales
         adapter = dict(ipa_scale=ipa_scale, s_lora_scale=s_lora_scale, c_lora_scale=c_lora_scale)
+        K = self._multi_control("pose_image", pose_image, shard_over_ranks)          # >= 2: per-net lists, checked below
         R = self._request_count(dict(prompt=prompt, prompt_embeds=prompt_embeds, negative_prompt=negative_prompt, null_prompt=null_prompt,
                                      negative_prompt_embeds=negative_prompt_embeds, ref_image=ref_image, ref_clip_image=ref_clip_image,
                                      ref_clip_hidden_states=ref_clip_hidden_states, ref_image_latents=ref_image_latents,
-                                     pose_image=pose_image, face_clip_image=face_clip_image, faceid_embeds=faceid_embeds,
+                                     pose_image=None if K else pose_image, face_clip_image=face_clip_image, faceid_embeds=faceid_embeds,
                                      face_clip_hidden_states=face_clip_hidden_states,
                                      face_uncond_clip_hidden_states=face_uncond_clip_hidden_states,
                                      guidance_scale=guidance_scale, image_scale=image_scale, guidance_rescale=guidance_rescale),
-                                dict(dict(num_inference_steps=num_inference_steps, eta=eta, controlnet_conditioning_scale=controlnet_conditioning_scale),
+                                dict(dict(num_inference_steps=num_inference_steps, eta=eta),
+                                     **({} if K else dict(controlnet_conditioning_scale=controlnet_conditioning_scale)),
                                      **({} if rows_on else adapter)), shard_over_ranks,
-                                control=dict(controlnet_conditioning_scale=controlnet_conditioning_scale,
-                                             control_guidance_start=control_guidance_start, control_guidance_end=control_guidance_end))
+                                control=None if K else dict(controlnet_conditioning_scale=controlnet_conditioning_scale,
+                                                            control_guidance_start=control_guidance_start, control_guidance_end=control_guidance_end))
         num_inference_steps, eta = per_call_value("num_inference_steps", num_inference_steps), per_call_value("eta", eta)
         adapter_rows = None
         if rows_on:
@@ -146,7 +148,17 @@ class IMAGDressing_v1(PipelineBase):
         prompt_embeds, negative_prompt_embeds = self._request_prompts(
             R, prompt, negative_prompt, prompt_embeds, negative_prompt_embeds, device, clip_skip)
         control = None
-        if pose_image is not None:                                            # ControlNet sees the 77 text tokens only (:550)
+        if K:                                                                 # several nets: one pose_image entry per net, the mix route
+            tensors = [self._image_tensor(as_batch(im, "pose_image"), device, normalize=False, size=(height, width),
+                                          multiple=self.vae_scale_factor, layout="nhwc8")
+                       for im in multi_control_images("pose_image", pose_image, K, R)]
+            if len({hw for _, hw in tensors}) > 1:
+                raise ValueError(f"pose_image: the images of the {K} ControlNets differ in size ({[hw for _, hw in tensors]}) after resizing")
+            height, width = tensors[0][1]
+            control = dict(image=[t for t, _ in tensors], prompt_embeds=prompt_embeds, negative_prompt_embeds=negative_prompt_embeds, scale=1.0,
+                           multi_rows=self._multi_control_plan(controlnet_conditioning_scale, control_guidance_start, control_guidance_end,
+                                                               K, R, num_inference_steps))
+        elif pose_image is not None:                                          # ControlNet sees the 77 text tokens only (:550)
             image, (height, width) = self._image_tensor(as_batch(pose_image, "pose_image"), device, normalize=False, size=(height, width),
                                                         multiple=self.vae_scale_factor, layout="nhwc8")
             # (enable_request_control_scales and differing triples: ``rows``, the effective scale of every request at every step)

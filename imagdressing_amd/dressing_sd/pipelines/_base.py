@@ -73,6 +73,9 @@ class PipelineBase:
 
         def ready(m):          # a ``from_pretrained`` handle that never met ``.to(device=...)``: build it now (default device)
             return m._build() if isinstance(m, PendingModel) else m
+        if isinstance(controlnet, (list, tuple)):          # controlnet=[a, b]: wrapped like diffusers does
+            from ...unet import MultiControlNetModel
+            controlnet = MultiControlNetModel([ready(n) for n in controlnet])
         vae, reference_unet, unet, controlnet = ready(vae), ready(reference_unet), ready(unet), ready(controlnet)
         text_encoder, image_encoder = ready(text_encoder), ready(image_encoder)
         for role, m in (("unet", unet), ("reference_unet", reference_unet), ("controlnet", controlnet)):
@@ -93,6 +96,25 @@ class PipelineBase:
         self._garment_cache = None
         if vae is not None and hasattr(vae, "config") and hasattr(vae.config, "block_out_channels"):
             self.vae_scale_factor = 2 ** (len(vae.config.block_out_channels) - 1)
+
+    # ---- one ControlNet or several (unet.MultiControlNetModel) ----
+    def _control_nets(self) -> list:
+        """the ControlNets of this pipeline, in order: none, the one given, or the nets of a ``MultiControlNetModel``"""
+        cn = getattr(self, "controlnet", None)
+        if cn is None:
+            return []
+        return list(cn.nets) if hasattr(cn, "nets") else [cn]
+
+    def _single_controlnet(self):
+        """what the one-net routes drive: the net itself, also where it came wrapped (``MultiControlNetModel([a])`` is ``a``)"""
+        nets = self._control_nets()
+        return nets[0] if len(nets) == 1 else getattr(self, "controlnet", None)
+
+    def _refuse_multi(self, what: str):
+        K = len(self._control_nets())
+        if K >= 2:
+            raise NotImplementedError(f"{what} on a pipeline with {K} ControlNets: the mix of several nets' residuals "
+                                      "(imd_residual_mix_rows) is built for whole calls on one rank; use one ControlNet here")
 
     # ---- reference surface ----
     @property
@@ -224,6 +246,19 @@ class PipelineBase:
 
     def disable_request_control_scales(self):
         return self.enable_request_control_scales(False)
+
+    def _multi_control(self, name: str, images, shard_over_ranks: bool):
+        """K of a call that drives several ControlNets (0: it does not -- one net, none, or no control image), after the refusals"""
+        K = len(self._control_nets())
+        if K < 2 or images is None:
+            return 0
+        if shard_over_ranks:
+            self._refuse_multi("shard_over_ranks=True")
+        return K
+
+    def _multi_control_plan(self, scale, start, end, K: int, R: int, steps: int):
+        """``multi_rows`` of a call's ``control`` dict on K >= 2 nets: ``multi_control_plan`` under this pipeline's switch"""
+        return multi_control_plan(scale, start, end, K, R, steps, per_request=getattr(self, "_request_control_scales", False))
 
     def _control_plan(self, scale, start, end, R: int, steps: int):
         """-> (scale, keep, rows) of a call's ``control`` dict: ``control_plan`` under this pipeline's switch"""
@@ -487,11 +522,14 @@ class PipelineBase:
             if vals is not None:
                 cak[key] = lay.per_row(per_request_floats(key, vals, lay.requests)).repeat(2).to(device=dev, dtype=torch.float32).contiguous()
         ctrl_img = ctrl_ehs = None
+        # control["multi_rows"]: a call on K >= 2 ControlNets -- control["image"] is then a list of K images, one per net
+        multi = control is not None and control.get("multi_rows") is not None
         if control is not None:
-            img = control["image"]
-            if lay.requests > 1 and img.shape[0] > 1:          # one control image per request (or per image): the ControlNet batch is 2B rows
-                img = lay.expand(img, "control image").repeat(2, *([1] * (img.dim() - 1)))
-            ctrl_img = img if (img.dim() == 4 and img.shape[-1] == 8 and img.dtype == dt) else nchw_to_nhwc8(img.to(dev), dt)
+            def control_image(img):
+                if lay.requests > 1 and img.shape[0] > 1:          # one control image per request (or per image): the ControlNet batch is 2B rows
+                    img = lay.expand(img, "control image").repeat(2, *([1] * (img.dim() - 1)))
+                return img if (img.dim() == 4 and img.shape[-1] == 8 and img.dtype == dt) else nchw_to_nhwc8(img.to(dev), dt)
+            ctrl_img = [control_image(img) for img in control["image"]] if multi else control_image(control["image"])
             ctrl_ehs = lay.text_context(control["prompt_embeds"], control["negative_prompt_embeds"]).to(device=dev, dtype=dt).contiguous()
         inp = None
         if inpaint is not None:
@@ -551,14 +589,31 @@ class PipelineBase:
                 raise ValueError(f"control rows: {len(control['rows'])} requests' scales for {lay.requests} requests")
             ctrl_table = control_scale_table(control["rows"], len(timesteps), lay, clamp=fused).to(dev)
             ctrl_dev = torch.ones(2 * B, dtype=torch.float32, device=dev)
+        # several nets: ONE table [calls, K, 2B] for the whole call, uploaded once; ctrl_run[i][k]: does net k contribute to any row at
+        # call i?  The eager loop does not run a net that does not (its source is at scale 0 in the mix launch, which never reads it)
+        ctrl_run = None
+        control_net = self._single_controlnet()
+        if multi:
+            nets = self._control_nets()
+            if len(control["multi_rows"]) != len(nets) or len(ctrl_img) != len(nets):
+                raise ValueError(f"control: {len(control['multi_rows'])} nets' scales and {len(ctrl_img)} images for {len(nets)} ControlNets")
+            if any(len(r) != lay.requests for r in control["multi_rows"]):
+                raise ValueError(f"control multi_rows: every net needs the scales of {lay.requests} requests")
+            host_table = multi_control_scale_table(control["multi_rows"], len(timesteps), lay, clamp=fused)
+            ctrl_run = [[bool(host_table[i, k].ne(0).any()) for k in range(len(nets))] for i in range(len(timesteps))]
+            ctrl_table = host_table.to(dev)
+            ctrl_dev = torch.zeros(len(nets), 2 * B, dtype=torch.float32, device=dev)
 
         def control_residuals(t, i, mode):
             """the ControlNet forward of UNet call ``i`` (None: the captured step of a graph replay) -> (down, mid)"""
             if control is None:
                 return None, None
+            if multi:
+                return self.controlnet.forward_nhwc(x_in, t, ctrl_ehs, ctrl_img, ctrl_dev if i is None else ctrl_table[i],
+                                                    run=None if i is None else ctrl_run[i], **mode)
             if ctrl_table is not None:
-                return self.controlnet.forward_nhwc(x_in, t, ctrl_ehs, ctrl_img, 1.0, scale_rows=ctrl_dev if i is None else ctrl_table[i], **mode)
-            return self.controlnet.forward_nhwc(x_in, t, ctrl_ehs, ctrl_img, ctrl_scale * (keeps[0] if i is None else keeps[i]), **mode)
+                return control_net.forward_nhwc(x_in, t, ctrl_ehs, ctrl_img, 1.0, scale_rows=ctrl_dev if i is None else ctrl_table[i], **mode)
+            return control_net.forward_nhwc(x_in, t, ctrl_ehs, ctrl_img, ctrl_scale * (keeps[0] if i is None else keeps[i]), **mode)
         # DeepCache (enable_deepcache): one feature cache for this call, shared by the UNet and the ControlNet; UNet call i == loop index i
         # (timesteps holds the executed calls only, PNDM's extra one included).  Switch off or interval 1: no cache, no keyword, today's calls
         dc_on = getattr(self, "_deepcache", None) is not None
@@ -639,7 +694,7 @@ class PipelineBase:
 
         # The time-embedding chain depends on the timestep only: one pass over the whole schedule here, every forward of the loop picks its row
         # (unet._Encoder.precompute_time_embeddings; 7 launches per UNet / ControlNet forward gone)
-        encs = [m for m in [self.unet] + ([self.controlnet] if control is not None else []) if hasattr(m, "precompute_time_embeddings")]
+        encs = [m for m in [self.unet] + (self._control_nets() if control is not None else []) if hasattr(m, "precompute_time_embeddings")]
         tables = [e.precompute_time_embeddings(timesteps, dev) for e in encs] if ops.TEMB_TABLE else []
         if not tables:
             encs = []
@@ -747,6 +802,7 @@ class PipelineBase:
         -- and EVERY step takes the rows route (``imd_residual_scale_rows`` behind the ControlNet at ``out_scale`` 1), so that a request's
         bits cannot depend on whether its company happens to share its values."""
         from ...session import DenoiseSession
+        self._refuse_multi("open_session")
         return DenoiseSession(self, slots, width, height, controlnet_conditioning_scale, with_controlnet=with_controlnet, compact=compact,
                               widths=widths, device_noise=device_noise, control_rows=control_rows)
 
@@ -1025,6 +1081,71 @@ def control_scale_table(rows: Sequence[Sequence[float]], calls: int, lay: "Reque
     return torch.stack([lay.per_row([r[min(i, n - 1)] for r in rows]).repeat(2) for i in range(calls)])
 
 
+def multi_control_values(scale, start, end, K: int, R: int, *, per_request: bool = False) -> List[List[tuple]]:
+    """The three ControlNet arguments of a call on K >= 2 nets -> ``values[k][r]`` = (scale, start, end) of net k for request r.  Each
+    argument is one value (all nets) or a flat list of K (per net: the diffusers meaning); with ``per_request``
+    (``enable_request_control_scales``) each of the K entries may itself be a list of 1 or R values.  A wrong length raises ValueError
+    naming the argument and both counts.  Every scale is finite and every window satisfies 0 <= start < end <= 1."""
+    cols = []
+    for name, v in zip(CONTROL_KEYS, (scale, start, end)):
+        if _is_seq(v):
+            if len(v) != K:
+                raise ValueError(f"{name} has {len(v)} entries for {K} ControlNets (give one value for all nets, or one per net)")
+            per_net = list(v)
+        else:
+            per_net = [v] * K
+        col = []
+        for k, e in enumerate(per_net):
+            if _is_seq(e):
+                if not per_request:
+                    raise ValueError(f"{name}[{k}] is a list: a value per request needs enable_request_control_scales() (one value per "
+                                     f"net otherwise)")
+                if len(e) not in (1, R):
+                    raise ValueError(f"{name}[{k}] has {len(e)} entries for {R} requests (give one, shared, or one per request)")
+                col.append([float(x) for x in e] * (R if len(e) == 1 else 1))
+            else:
+                col.append([float(e)] * R)
+        cols.append(col)
+    values = [[(cols[0][k][r], cols[1][k][r], cols[2][k][r]) for r in range(R)] for k in range(K)]
+    for k, per_req in enumerate(values):
+        for r, (s, a, b) in enumerate(per_req):
+            if not math.isfinite(s):
+                raise ValueError(f"controlnet_conditioning_scale of net {k}, request {r} must be finite, got {s}")
+            if not (math.isfinite(a) and math.isfinite(b) and 0.0 <= a < b <= 1.0):
+                raise ValueError(f"control_guidance_start / control_guidance_end of net {k}, request {r}: need 0 <= start < end <= 1, got "
+                                 f"start = {a}, end = {b}")
+    return values
+
+
+def multi_control_plan(scale, start, end, K: int, R: int, steps: int, *, per_request: bool = False) -> List[List[List[float]]]:
+    """-> ``rows[k][r][i] = scale * controlnet_keep(steps, start, end)[i]`` of net k for request r (:func:`multi_control_values`): the
+    effective scale at loop index i.  A call on K >= 2 nets always takes this route, whatever the values."""
+    return [[[s * g for g in controlnet_keep(steps, a, b)] for s, a, b in per_req]
+            for per_req in multi_control_values(scale, start, end, K, R, per_request=per_request)]
+
+
+def multi_control_scale_table(rows: Sequence[Sequence[Sequence[float]]], calls: int, lay: "RequestLayout", clamp: bool) -> torch.Tensor:
+    """``rows`` of :func:`multi_control_plan` -> the host table [calls, K, 2 lay.rows] fp32 that ``imd_residual_mix_rows`` reads one
+    [K, 2B] slice of per UNet call: :func:`control_scale_table` per net (the cond half, then the same values for the uncond half;
+    ``clamp``: PNDM's extra call reads the last gate)."""
+    return torch.stack([control_scale_table(r, calls, lay, clamp) for r in rows], dim=1).contiguous()
+
+
+def multi_control_images(name: str, images, K: int, R: int, allow_none: int = 0) -> list:
+    """The control image argument of a call on K >= 2 nets: a list of K entries, one per net, each whatever one net takes (one image,
+    or a per-request list / batched tensor of 1 or R); at most ``allow_none`` of them None."""
+    if not _is_seq(images) or len(images) != K:
+        n = len(images) if _is_seq(images) else (0 if images is None else 1)
+        raise ValueError(f"{name} has {n} entries for {K} ControlNets (give a list with one entry per net)")
+    if sum(e is None for e in images) > allow_none:
+        raise ValueError(f"{name}: {sum(e is None for e in images)} of the {K} entries are None (at most {allow_none} may be)")
+    for k, e in enumerate(images):
+        c = entries(name, e)
+        if c is not None and c not in (1, R):
+            raise ValueError(f"{name}[{k}] has {c} entries for {R} requests (give one, shared, or one per request)")
+    return list(images)
+
+
 def request_count(args: Dict[str, Any], per_call: Optional[Dict[str, Any]] = None, *, shard_over_ranks: bool = False,
                   scheduler=None, control: Optional[Dict[str, Any]] = None) -> int:
     """R of a call and the checks of a request-batched one.  R = the largest entry count of the garment / prompt arguments
@@ -1121,5 +1242,5 @@ def set_scale_by_type(unet, cls, **attrs):
 
 
 __all__ = ["deepcache_plan", "RequestLayout", "request_count", "request_rows", "unipc_fused", "per_request_floats", "guidance_rescale_values", "soft_step_table", "per_call_value", "as_batch", "min_guidance", "entries",
-           "controlnet_keep", "control_plan", "control_request_values", "control_scale_table", "CONTROL_KEYS", "first", "to_image_tensor", "PipelineBase", "StableDiffusionPipelineOutput", "randn_tensor", "set_scale_by_type",
+           "controlnet_keep", "control_plan", "control_request_values", "control_scale_table", "multi_control_values", "multi_control_plan", "multi_control_scale_table", "multi_control_images", "CONTROL_KEYS", "first", "to_image_tensor", "PipelineBase", "StableDiffusionPipelineOutput", "randn_tensor", "set_scale_by_type",
            "RefSAttnProcessor2_0", "LoraRefSAttnProcessor2_0", "LoRAIPAttnProcessor2_0", "IPAttnProcessor2_0"]

@@ -1437,6 +1437,66 @@ def residual_scale_rows(tensors: Sequence[torch.Tensor], scale_rows: torch.Tenso
     return tensors
 
 
+# ---- the scaled sum of several sources, a scale per source and batch row: several ControlNets' residuals (csrc/residual_mix_rows.hip) ----
+MIX_ROWS_COUNTER = {"launches": 0}        # imd_residual_mix_rows launches of this process (tests check that one net makes none)
+MIX_ROWS_MAX_SOURCES = L.MIX_ROWS_MAX_SOURCES
+MIX_ROWS_MAX_SEGMENTS = L.MIX_ROWS_MAX_SEGMENTS
+
+
+def residual_mix_rows(sources: Sequence[Sequence[torch.Tensor]], scales: torch.Tensor, out: Optional[Sequence[torch.Tensor]] = None):
+    """``out[j][r] = 16-bit(sum over k of sources[k][j][r].float() * scales[k, r])`` in one launch (``imd_residual_mix_rows``): 1 to 4
+    sources, each a list of the same 1 to 16 contiguous 16-bit device tensors [rows, ...] whose rows hold a multiple of 8 elements;
+    ``scales`` fp32 [sources, rows] on the device.  The sum runs in source order in fp32, every product and every sum rounded (no FMA);
+    a source whose scale for a row is 0 is not read there; all 0 gives +0.  ``out``: None (fresh tensors) or a list like one source,
+    which may BE one of the sources (in place).  -> ``out``."""
+    what = "residual_mix_rows"
+    if not isinstance(sources, (list, tuple)) or not 1 <= len(sources) <= MIX_ROWS_MAX_SOURCES:
+        n = len(sources) if isinstance(sources, (list, tuple)) else type(sources).__name__
+        raise L.ImdError(f"{what}: expected a list of 1 to {MIX_ROWS_MAX_SOURCES} sources, got {n}")
+    for k, src in enumerate(sources):
+        if not isinstance(src, (list, tuple)) or not 1 <= len(src) <= MIX_ROWS_MAX_SEGMENTS:
+            n = len(src) if isinstance(src, (list, tuple)) else type(src).__name__
+            raise L.ImdError(f"{what}: source {k}: expected a list of 1 to {MIX_ROWS_MAX_SEGMENTS} tensors, got {n}")
+        if not all(isinstance(t, torch.Tensor) and t.dim() >= 1 for t in src):
+            raise L.ImdError(f"{what}: source {k}: every segment must be a torch.Tensor [rows, ...]")
+    first = sources[0][0]
+    rows, K, S = first.shape[0], len(sources), len(sources[0])
+    if out is None:
+        out = [torch.empty_like(t) for t in sources[0]]
+    elif not isinstance(out, (list, tuple)) or not all(isinstance(t, torch.Tensor) for t in out):
+        raise L.ImdError(f"{what}: out must be None or a list of tensors like one source")
+    groups = [(f"source {k}", src) for k, src in enumerate(sources)] + [("out", out)]
+    for name, g in groups:
+        if len(g) != S:
+            raise L.ImdError(f"{what}: {name} has {len(g)} segments, source 0 has {S}")
+        for j, t in enumerate(g):
+            if t.dtype != first.dtype:
+                raise L.ImdError(f"{what}: {name}, tensor {j}: the tensors differ in dtype ({t.dtype} and {first.dtype})")
+            if tuple(t.shape) != tuple(sources[0][j].shape):
+                raise L.ImdError(f"{what}: {name}, tensor {j}: shape {tuple(t.shape)} differs from source 0's {tuple(sources[0][j].shape)}")
+            if not t.is_contiguous():
+                raise L.ImdError(f"{what}: {name}, tensor {j} must be contiguous (a segment is one [rows, row_elems] block)")
+    if not isinstance(scales, torch.Tensor) or tuple(scales.shape) != (K, rows):
+        raise L.ImdError(f"{what}: scales must be an fp32 device tensor [{K}, {rows}] (sources x rows), got "
+                         f"{tuple(getattr(scales, 'shape', ()))}")
+    p = L.MixRowsParams()
+    p.dtype, p.rows, p.segments, p.sources = _code(first, what), rows, S, K
+    for j, t in enumerate(sources[0]):
+        if rows < 1 or t.numel() == 0 or (t.numel() // rows) % 8:
+            raise L.ImdError(f"{what}: tensor {j} {tuple(t.shape)}: a row must hold a positive multiple of 8 elements")
+        p.row_elems[j] = t.numel() // rows
+    for k, src in enumerate(sources):
+        for j, t in enumerate(src):
+            p.src[k][j] = _dev(t, first.dtype, f"source {k}, tensor {j}")
+    for j, t in enumerate(out):
+        p.dst[j] = _dev(t, first.dtype, f"out, tensor {j}")
+    ensure_device(first.device)
+    p.scales = _dev(scales, torch.float32, "scales")
+    L.check(L.load().imd_residual_mix_rows(C.byref(p), _stream()))
+    MIX_ROWS_COUNTER["launches"] += 1
+    return list(out)
+
+
 # ---- UniPC on one fused step launch (csrc/unipc_step.hip;the coefficients come from scheduler.UniPCMultistepScheduler.plan_fused) ----
 UNIPC_COEFS = 19
 UNIPC_ROW_FLOATS = 24

@@ -518,7 +518,8 @@ class DenoiseSession:
         self.S, self.image_width, self.image_height = int(slots), int(width), int(height)
         self.h, self.w = self.image_height // vsf, self.image_width // vsf
         self.HW = self.h * self.w
-        self.controlnet = pipe.controlnet if with_controlnet else None
+        # (a MultiControlNetModel of one net is that net; several nets are refused by the pipeline's open_session)
+        self.controlnet = (pipe._single_controlnet() if hasattr(pipe, "_single_controlnet") else pipe.controlnet) if with_controlnet else None
         if with_controlnet and self.controlnet is None:
             raise ValueError("open_session: this pipeline was built without a ControlNet")
         self.control_scale = float(controlnet_conditioning_scale)

@@ -881,6 +881,98 @@ class ControlNetModel(_Encoder):
     __call__ = forward
 
 
+class MultiControlNetModel:
+    """1 to 4 :class:`ControlNetModel` of one dtype, device and widths whose residuals are summed for the UNet, every net with its own
+    conditioning scale per batch row (diffusers' ``MultiControlNetModel``).  The nets run one after another on the current stream
+    with ``conditioning_scale`` = 1; ONE ``imd_residual_mix_rows`` launch then forms the scaled sum in fp32 and rounds it once."""
+
+    MAX_NETS = ops.MIX_ROWS_MAX_SOURCES
+
+    def __init__(self, controlnets):
+        if isinstance(controlnets, MultiControlNetModel):
+            controlnets = controlnets.nets
+        nets = list(controlnets) if isinstance(controlnets, (list, tuple)) else [controlnets]
+        if not 1 <= len(nets) <= self.MAX_NETS:
+            raise ValueError(f"MultiControlNetModel: expected 1 to {self.MAX_NETS} ControlNets, got {len(nets)}")
+        for k, n in enumerate(nets):
+            if not isinstance(n, ControlNetModel):
+                raise TypeError(f"MultiControlNetModel: net {k} is a {type(n).__name__}, expected a ControlNetModel")
+        a = nets[0]
+        for k, n in enumerate(nets[1:], 1):
+            if n.dtype != a.dtype or n.device != a.device:
+                raise ValueError(f"MultiControlNetModel: net {k} is {n.dtype} on {n.device}, net 0 is {a.dtype} on {a.device}")
+            for key in ("block_out_channels", "layers_per_block"):
+                if tuple(_as_tuple(n.cfg[key])) != tuple(_as_tuple(a.cfg[key])):
+                    raise ValueError(f"MultiControlNetModel: net {k} has {key} = {n.cfg[key]}, net 0 has {a.cfg[key]}: the residuals "
+                                     "of all nets must have the same shapes")
+        self.nets = nets
+        self.dtype, self.device, self.cfg, self.config = a.dtype, a.device, a.cfg, a.config
+
+    def __len__(self):
+        return len(self.nets)
+
+    def to(self, *args, **kwargs):
+        self.nets = [n.to(*args, **kwargs) for n in self.nets]
+        self.dtype, self.device = self.nets[0].dtype, self.nets[0].device
+        return self
+
+    def eval(self):
+        return self
+
+    def residual_shapes(self, B: int, H: int, W: int, depth: Optional[int] = None):
+        """the NHWC shapes of (down residuals, mid) of an H x W latent; ``depth``: a DeepCache shallow call -> (depth shapes, None)"""
+        boc, L = _as_tuple(self.cfg["block_out_channels"]), int(self.cfg["layers_per_block"])
+        if depth is not None:
+            return [(B, H, W, boc[0])] * depth, None
+        down, h, w = [(B, H, W, boc[0])], H, W
+        for lv, c in enumerate(boc):
+            down += [(B, h, w, c)] * L
+            if lv < len(boc) - 1:
+                h, w = (h + 1) // 2, (w + 1) // 2
+                down.append((B, h, w, c))
+        return down, (B, h, w, boc[-1])
+
+    def forward_nhwc(self, x, timestep, encoder_hidden_states, conds, scale_table_row, deepcache: Optional[DeepCache] = None, run=None):
+        """x [B, H, W, 8]; ``conds``: one cond per net ([Bc, 8H, 8W, 8], Bc == B or 1); ``scale_table_row``: device fp32 [nets, B], the
+        scale of every net for every batch row -> (down, mid) like ``ControlNetModel.forward_nhwc`` (``deepcache`` as there).
+        ``run``: None, or one flag per net -- a net at False is not run and the mix launch must find zeros in its row of the scales
+        (a source at 0 is never read: whether a gated net ran does not change a bit).  One net: that net's own rows route."""
+        K, B = len(self.nets), x.shape[0]
+        if len(conds) != K:
+            raise ValueError(f"MultiControlNetModel: {len(conds)} conditioning images for {K} nets")
+        if not isinstance(scale_table_row, torch.Tensor) or tuple(scale_table_row.shape) != (K, B):
+            raise ValueError(f"MultiControlNetModel: scale_table_row must be a device fp32 tensor [{K}, {B}] (nets x batch rows), got "
+                             f"{tuple(getattr(scale_table_row, 'shape', ()))}")
+        run = [True] * K if run is None else [bool(f) for f in run]
+        if len(run) != K:
+            raise ValueError(f"MultiControlNetModel: run has {len(run)} flags for {K} nets")
+        mode = {} if deepcache is None else {"deepcache": deepcache}
+        if K == 1:
+            return self.nets[0].forward_nhwc(x, timestep, encoder_hidden_states, conds[0], 1.0, scale_rows=scale_table_row[0], **mode)
+        outs = [None] * K
+        for k, net in enumerate(self.nets):
+            if run[k]:
+                down, mid = net.forward_nhwc(x, timestep, encoder_hidden_states, conds[k], 1.0, **mode)
+                outs[k] = down + ([mid] if mid is not None else [])
+        if deepcache is not None and deepcache.full:
+            deepcache.note_controlnet(x)          # (a later shallow call checks against it, whichever nets ran in this one)
+        ran = [o for o in outs if o is not None]
+        if ran:
+            dst = ran[0]                          # fresh tensors of this forward: mixed in place
+        else:                                     # every net gated: the same launch writes +0
+            shallow = deepcache is not None and not deepcache.full
+            shapes, mid_shape = self.residual_shapes(B, x.shape[1], x.shape[2], deepcache.depth if shallow else None)
+            dst = [torch.empty(s, dtype=self.dtype, device=x.device) for s in shapes + ([mid_shape] if mid_shape is not None else [])]
+        ops.residual_mix_rows([o if o is not None else dst for o in outs], scale_table_row, out=dst)
+        if deepcache is not None and not deepcache.full:
+            return dst, None
+        return dst[:-1], dst[-1]
+
+
+def _as_tuple(v):
+    return tuple(v) if isinstance(v, (list, tuple)) else (v,)
+
+
 def _scaled_conv1x1(conv: ConvOp, x, scale: float):
     """zero-conv: (W x + b) * scale  ==  out_scale applied after the bias in the epilogue."""
     return ops.conv2d_nhwc(x, conv.weight, conv.bias, taps=1, out_scale=scale)

@@ -457,6 +457,33 @@ typedef struct imd_scale_rows_params {
     int row_elems[16];     /* elements per row of each segment: positive multiples of 8 */
 } imd_scale_rows_params;
 
+/* The scaled sum of up to 4 sources on up to 16 tensors at once (imd_residual_mix_rows): the residuals of several ControlNets, every
+ * net with its own scale per batch row, mixed for the UNet in ONE launch.  The nets run with out_scale = 1 and this launch follows the
+ * last of them.  Segment j of source k is a contiguous 16-bit [rows, row_elems[j]] tensor; for every segment j and every row r
+ *   acc = nothing
+ *   for k = 0 .. sources - 1, in this order:
+ *       s = scales[k * rows + r]
+ *       if s == 0.0f: continue                      source k's row is NOT read (NaN and Inf in it stay out of the sum)
+ *       term = float(src[k][j][r]) * s              widen (exact), ONE fp32 multiply, rounded
+ *       acc  = term, or acc + term                  ONE fp32 add, rounded -- never a fused multiply-add
+ *   dst[j][r] = 16-bit(acc), round to nearest even; +0 where every source was skipped
+ * which is, bit for bit, the same chain of x.float() * torch.tensor(s, dtype=torch.float32) and + on the CPU.  Against K - 1 element-wise
+ * adds of 16-bit tensors the sum is rounded to 16 bits once, not K times.  dst[j] may BE src[k][j] (in place on one source; a thread
+ * reads all its vectors of a chunk before it stores any); any other overlap of a dst segment with a source or another dst segment is
+ * refused.  Sources are otherwise only read. */
+#define IMD_MIX_ROWS_MAX_SOURCES 4
+#define IMD_MIX_ROWS_MAX_SEGMENTS 16
+typedef struct imd_mix_rows_params {
+    uint32_t struct_bytes; /* sizeof(imd_mix_rows_params) in the caller's view; checked on entry */
+    int dtype;             /* IMD_DTYPE_*: the element type of every segment, sources and dst alike */
+    int rows, segments;    /* rows >= 1; segments in 1..IMD_MIX_ROWS_MAX_SEGMENTS */
+    int sources;           /* 1..IMD_MIX_ROWS_MAX_SOURCES */
+    const float* scales;   /* DEVICE [sources][rows] fp32, 4-byte aligned: source-major, the same array for all segments */
+    const void* src[4][16]; /* [IMD_MIX_ROWS_MAX_SOURCES][IMD_MIX_ROWS_MAX_SEGMENTS] bases, 16-byte aligned; entries past `sources` / `segments` are not read */
+    void* dst[16];         /* segment bases of the result, 16-byte aligned */
+    int row_elems[16];     /* elements per row of each segment: positive multiples of 8 */
+} imd_mix_rows_params;
+
 /* Device-side image input (imd_image_resample): separable antialiased resampling of uint8 images, bit-exact with Pillow's 8-bit
  * resampler (libImaging/Resample.c), with a fused output stage -- the work diffusers' VaeImageProcessor / transformers'
  * CLIPImageProcessor do on the host in front of IMAGDressing_v1_pipeline*.py.  Per axis whose size changes the caller passes a
@@ -822,6 +849,13 @@ int imd_lora_expand_rows(const imd_lora_rows_params* p, void* stream);
  * dtype, segments outside 1..16, rows < 1, scale_rows NULL or not 4-byte aligned, a row_elems that is not a positive multiple of 8,
  * a data pointer that is NULL or not 16-byte aligned, 2^31 chunks or more. */
 int imd_residual_scale_rows(const imd_scale_rows_params* p, void* stream);
+
+/* dst = the scaled sum of the sources, row by row, as ONE launch (the chunks of residual_scale_rows.hip; residual_mix_rows.hip); see
+ * imd_mix_rows_params.  Errors without launching: null params, a foreign struct_bytes, an unknown dtype, sources outside 1..4, segments
+ * outside 1..16, rows < 1, scales NULL or not 4-byte aligned, a row_elems that is not a positive multiple of 8, a src / dst pointer that
+ * is NULL or not 16-byte aligned, 2^31 chunks or more, a dst segment that overlaps a source segment (other than dst[j] == src[k][j]) or
+ * another dst segment. */
+int imd_residual_mix_rows(const imd_mix_rows_params* p, void* stream);
 
 /* Pillow-exact resize (+ crop, normalise, layout) of uint8 images on the device; see imd_image_resample_params.  Errors without
  * launching: a foreign struct size, null src / out, C outside {1, 3}, an incomplete table or a skipped axis whose size changes, a
